@@ -3,6 +3,7 @@
 bench.py — ELBO iterations/sec of the fused SVI engine (BASELINE.json metric).
 
   python bench.py --gpus N --steps K --warmup W [--workload cfg1|...|cfg5] [--mode auto|persistent|stepwise]
+                  [--dump-outputs DIR] [--full]
 
 A "step" is one complete SVI iteration of `brancher/inference.py:95-108`: draw number_samples
 reparameterised posterior samples (in-kernel Philox), evaluate log p + entropy over the model
@@ -15,10 +16,17 @@ Monte-Carlo sample axis — every GPU evaluates `number_samples` samples of the 
 iteration and ONE all-reduce (RCCL) of 4+P floats joins them.  `value` is whole-job
 throughput in 300-sample ELBO iterations per second:  (global samples per step / 300) * steps / s.
 
-One JSON line is printed by rank 0.  On one GPU with the default workload the same line also carries BASELINE
-configs 2-5 (`other_configs`: each timed for 50 iterations in this process after the headline's timed region, with its
-own roofline object), and `roofline.traffic` is measured live (rocprofv3 --pmc passes of this script as child
-processes before the GPU is touched here; see run_traffic_probe).
+One JSON line is printed by rank 0.  A plain run measures the headline only: set-up, W warm-up steps and the untimed
+spin-up, the K timed steps, the line.  `--full` adds everything else the line used to carry: on one GPU with the default
+workload BASELINE configs 2-5 (`other_configs`: each timed for 50 iterations in this process after the headline's timed
+region, with its own roofline object), `roofline.traffic` measured live (rocprofv3 --pmc passes of this script as child
+processes before the GPU is touched here; see run_traffic_probe), the CPU baseline, the `cold_start` figure and, on
+several GPUs, the second phase with the one-shot exchange (`value_alt`).
+
+--dump-outputs DIR writes what the headline's last timed step left to its caller — the loss curve and finite flags of
+the timed call and the parameters after it — as DIR/<name>.npy.  The parameters and the Philox offset that the warm-up
+steps left are restored when the time-limited spin-up ends, so the timed call's inputs do not depend on how many
+iterations the spin-up ran: the same arguments give the same inputs from run to run.
 """
 import argparse
 import json
@@ -325,9 +333,26 @@ def self_launch(n_gpus, argv=None, port=None):
     return subprocess.call(cmd, env=env)
 
 
-def measure(workload, args, steps, warmup, spinup_ms, world, rank, probe_rows=None, probe_iters=None, estimator=None):
+DUMP_MAX_ELEMENTS = 4 << 20     # per array (16 MB as float32): three arrays stay within 64 MB
+
+
+def dump_outputs(out_dir, **arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32; an array longer than DUMP_MAX_ELEMENTS is written as a
+    fixed sample of its entries (the same seeded choice of indices in every run, kept in order)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy().ravel()
+        if a.size > DUMP_MAX_ELEMENTS:
+            a = a[np.sort(np.random.RandomState(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
+
+
+def measure(workload, args, steps, warmup, spinup_ms, world, rank, probe_rows=None, probe_iters=None, estimator=None,
+            dump_dir=None):
     """Warm-up, spin-up and the timed region of ONE workload: exactly `steps` SVI iterations between two barriers.
-    Returns (the parts of the JSON line that describe this workload, what the CPU baseline needs)."""
+    Returns (the parts of the JSON line that describe this workload, what the CPU baseline needs).  dump_dir: write what
+    the timed call returned (dump_outputs)."""
     import gc
     import torch
     import torch.distributed as dist
@@ -391,10 +416,13 @@ def measure(workload, args, steps, warmup, spinup_ms, world, rank, probe_rows=No
     elif failed is not None:
         raise failed
     barrier()
+    # the state the warm-up left (parameters; every call starts a fresh optimizer): put back after the spin-up, whose number
+    # of iterations follows the clock, so that the timed steps — and what --dump-outputs writes — are the same from run to run
+    start_params, start_iteration = compiled.params.clone(), compiled.iteration
     # ---- the same K steps ONCE before any spin-up: what a caller sees on a GPU whose clocks have not ramped (reported next
-    #      to the hot figure as `cold_start`; the headline stays the contract's: W warm-up steps, then K timed steps)
+    #      to the hot figure as `cold_start`, --full only; the headline stays the contract's: W warm-up steps, then K timed steps)
     cold = None
-    if spinup_ms > 0:
+    if spinup_ms > 0 and args.full:
         c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         barrier()
         c0.record()
@@ -429,6 +457,9 @@ def measure(workload, args, steps, warmup, spinup_ms, world, rank, probe_rows=No
             train(chunk)
             torch.cuda.synchronize()
             spun += chunk
+    compiled.params.copy_(start_params)
+    compiled.iteration = start_iteration
+    del start_params
     barrier()
 
     # ---- timed region: exactly K steps
@@ -464,6 +495,8 @@ def measure(workload, args, steps, warmup, spinup_ms, world, rank, probe_rows=No
     ok = bool(torch.isfinite(losses).all()) and bool(finite.all())
     if rank != 0:
         return None, None
+    if dump_dir:
+        dump_outputs(dump_dir, loss_curve=losses, finite=finite, params=compiled.params)
 
     iters_per_sec = steps / dt
     value = iters_per_sec * (n_global / 300.0)
@@ -696,13 +729,18 @@ def main():
     ap.add_argument("--dataset-size", type=int, default=0, help="cfg4: override the synthetic dataset size")
     ap.add_argument("--mode", default="auto", choices=["auto", "persistent", "stepwise"])
     ap.add_argument("--samples", type=int, default=0, help="override number_samples per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline as well: the other configs, live traffic, the CPU baseline, "
+                         "the cold start and, on several GPUs, the one-shot exchange phase (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the loss curve, finite flags and final parameters of the headline's timed call as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--other-configs", default="auto", choices=["auto", "on", "off"],
                     help="after the headline workload, time BASELINE configs 2-5 in the same process and attach them under "
-                         "the `other_configs` key of the same JSON line (auto: when the headline is cfg1 on one GPU)")
+                         "the `other_configs` key of the same JSON line (auto: with --full, when the headline is cfg1 on one GPU)")
     ap.add_argument("--traffic", default="auto", choices=["auto", "on", "off"],
                     help="measure roofline.traffic live: rocprofv3 --pmc passes of this script as child processes before "
-                         "the timed regions (auto: on one GPU)")
+                         "the timed regions (auto: with --full, on one GPU)")
     ap.add_argument("--traffic-probe", default="", help=argparse.SUPPRESS)       # child mode: "cfg1:K:W,cfg2:K:W,..."
     ap.add_argument("--spinup-ms", type=float, default=300.0,
                     help="untimed iterations of the timed path after the W warm-up steps, to let the clocks ramp (0: off)")
@@ -738,7 +776,7 @@ def main():
 
     probing = bool(args.traffic_probe)
     others = [] if probing else list(OTHER_CONFIGS) if (args.other_configs == "on" or (
-        args.other_configs == "auto" and world == 1 and args.workload == "cfg1" and not args.samples)) else []
+        args.other_configs == "auto" and args.full and world == 1 and args.workload == "cfg1" and not args.samples)) else []
     plan = [(args.workload, args.steps, args.warmup, args.spinup_ms)] + \
            [(w, OTHER_STEPS, OTHER_WARMUP, OTHER_SPINUP_MS) for w in others]
     blackbox_plan = [(w, OTHER_STEPS, OTHER_WARMUP, OTHER_SPINUP_MS) for w in OTHER_BLACKBOX] if (others and args.estimator == "pathwise") else []
@@ -747,7 +785,7 @@ def main():
 
     # ---- live HBM traffic: PMC passes of this same script as children, BEFORE this process initialises the GPU
     probe_rows, probe_note, probe_iters = None, None, {}
-    if not probing and world == 1 and args.traffic != "off":
+    if not probing and world == 1 and (args.traffic == "on" or (args.traffic == "auto" and args.full)):
         t_probe = time.perf_counter()
         steps_of = {w: k for w, k, _, _ in plan}
         warm_of = {w: max(wu, 1) for w, _, wu, _ in plan}
@@ -756,7 +794,8 @@ def main():
         probe_iters = {w: steps_of[w] + warm_of[w] for w in steps_of}
         probe_seconds = time.perf_counter() - t_probe
     elif not probing:
-        probe_note = "not measured (%s)" % ("--traffic off" if args.traffic == "off" else "multi-GPU run")
+        probe_note = "not measured (%s)" % ("--traffic off" if args.traffic == "off" else "multi-GPU run" if world > 1 else
+                                            "measured with --full")
 
     # BSVI_BENCH_SHARE_GPU=1 with BSVI_BENCH_BACKEND=gloo: dry run of the N > 1 flow on a box with fewer GPUs than ranks
     # (the ranks share devices, collectives go through the host) — tests/test_gpu_two_ranks.py; never a measurement
@@ -778,7 +817,8 @@ def main():
     other_lines = {}
     for i, (workload, steps, warmup, spinup_ms) in enumerate(plan):
         if i == 0 or probing:
-            part, info = measure(workload, args, steps, warmup, spinup_ms, world, rank, probe_rows, probe_iters)
+            part, info = measure(workload, args, steps, warmup, spinup_ms, world, rank, probe_rows, probe_iters,
+                                 dump_dir=args.dump_outputs if i == 0 and not probing else None)
             if i == 0:
                 line, baseline_of = part, info
             continue
@@ -806,7 +846,7 @@ def main():
     #      nothing but that key: the exchange's waits are bounded, `measure` votes and falls back on any rank's failure, and a WATCHDOG in every
     #      rank ends the phase after BSVI_BENCH_ALT_TIMEOUT_S (default 120): rank 0 prints the line it already has, every rank leaves with 0.
     alt = None
-    if world > 1 and not probing and os.environ.get("BSVI_BENCH_ALT", "1") != "0" and engine_collective_is_default():
+    if world > 1 and args.full and not probing and os.environ.get("BSVI_BENCH_ALT", "1") != "0" and engine_collective_is_default():
         import threading
         done = threading.Event()
         limit = float(os.environ.get("BSVI_BENCH_ALT_TIMEOUT_S", "120"))
@@ -875,7 +915,7 @@ def finish_line(line, other_lines, baseline_of, args, world, probe_rows, probe_n
             line["roofline"]["traffic_probe_seconds"] = probe_seconds
         if other_lines:
             line["other_configs"] = other_lines
-        if world == 1 and not args.no_cpu_baseline and not skip_cpu:
+        if world == 1 and args.full and not args.no_cpu_baseline and not skip_cpu:
             b = baseline_of
             line["cpu_baseline"] = cpu_baseline_vae(b["kwargs"], b["optimizer"], b["opt_kwargs"]) if b["amort"] else \
                 cpu_baseline(b["builder"], b["kwargs"], b["n"], b["optimizer"], b["opt_kwargs"], dense=b["dense"])

@@ -212,8 +212,9 @@ def test_bench_with_two_ranks_dry_run(extra, samples):
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "BSVI_COLLECTIVE")}
     env.update(BSVI_BENCH_BACKEND="gloo", BSVI_BENCH_SHARE_GPU="1")
+    # (--full: the second phase below is not part of a plain run)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "5",
-                          "--spinup-ms", "0"] + extra, env=env, capture_output=True, text=True, timeout=600)
+                          "--spinup-ms", "0", "--full"] + extra, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
