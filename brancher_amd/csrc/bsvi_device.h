@@ -177,7 +177,9 @@ __device__ __forceinline__ void optimizer_apply(const bsvi_opt_cfg& cfg, float& 
     if (cfg.kind == BSVI_OPT_SGD) {
         if (cfg.weight_decay != 0.0f) grad += cfg.weight_decay * p;
         if (cfg.momentum != 0.0f) {
-            const float buf = (step == 1.0f) ? grad : cfg.momentum * s0 + (1.0f - cfg.dampening) * grad;
+            // (the fused multiply-add spelled out: with two products in the sum the compiler picks which one to fuse by the
+            //  code around the inlined call, and two callers of the same step rounded differently)
+            const float buf = (step == 1.0f) ? grad : __builtin_fmaf(cfg.momentum, s0, (1.0f - cfg.dampening) * grad);
             s0 = buf;
             grad = cfg.nesterov ? grad + cfg.momentum * buf : buf;
         }
@@ -205,27 +207,42 @@ __device__ __forceinline__ void optimizer_apply(const bsvi_opt_cfg& cfg, float& 
 // state — the in-kernel training loop: one multiply per step instead of a double-precision pow (two of them were a fifth
 // of an iteration of BASELINE config 1 under Adam).  The products differ from pow() by the rounding of at most `st`
 // multiplies (~st * 1e-16 relative): far below the single-precision rounding of the step size they end up in.
-__device__ __forceinline__ void optimizer_apply_running(const bsvi_opt_cfg& cfg, float& p, float& s0, float& s1, float& s2, float& st,
-                                                        float grad, double& p1, double& p2) {
-    if (cfg.kind == BSVI_OPT_SGD) { optimizer_apply(cfg, p, s0, s1, s2, st, grad); return; }
+// Adam's factors of the NEXT step, a function of the running products alone: the in-kernel loop may evaluate them before the
+// gradient exists (spec_main.h, SPEC_DRAW_OWNERS) and keep them only when the step is taken.
+struct AdamBias { double p1, p2; float step_size, bc2_sqrt; };
+__device__ __forceinline__ AdamBias optimizer_adam_bias(const bsvi_opt_cfg& cfg, double p1, double p2) {
+    AdamBias b;
+    b.p1 = p1 * (double)cfg.beta1;
+    b.p2 = p2 * (double)cfg.beta2;
+    b.step_size = (float)((double)cfg.lr / (1.0 - b.p1));
+    b.bc2_sqrt = (float)sqrt(1.0 - b.p2);
+    return b;
+}
+// the Adam step on those factors (the caller stores b.p1 / b.p2 as its new running products)
+__device__ __forceinline__ void optimizer_apply_adam_biased(const bsvi_opt_cfg& cfg, float& p, float& s0, float& s1, float& s2, float& st,
+                                                            float grad, const AdamBias& b) {
     if (cfg.maximize) grad = -grad;
     st = st + 1.0f;
-    p1 *= (double)cfg.beta1;
-    p2 *= (double)cfg.beta2;
     if (cfg.weight_decay != 0.0f) grad += cfg.weight_decay * p;
     const float m = s0 + (grad - s0) * (1.0f - cfg.beta1);
     const float v = cfg.beta2 * s1 + (1.0f - cfg.beta2) * grad * grad;
     s0 = m;
     s1 = v;
-    const float step_size = (float)((double)cfg.lr / (1.0 - p1));
-    const float bc2_sqrt = (float)sqrt(1.0 - p2);
     float vhat = v;
     if (cfg.amsgrad) {
         vhat = fmaxf(s2, v);
         s2 = vhat;
     }
-    const float denom = sqrtf(vhat) / bc2_sqrt + cfg.eps;
-    p = p - step_size * (m / denom);
+    const float denom = sqrtf(vhat) / b.bc2_sqrt + cfg.eps;
+    p = p - b.step_size * (m / denom);
+}
+__device__ __forceinline__ void optimizer_apply_running(const bsvi_opt_cfg& cfg, float& p, float& s0, float& s1, float& s2, float& st,
+                                                        float grad, double& p1, double& p2) {
+    if (cfg.kind == BSVI_OPT_SGD) { optimizer_apply(cfg, p, s0, s1, s2, st, grad); return; }
+    const AdamBias b = optimizer_adam_bias(cfg, p1, p2);
+    optimizer_apply_adam_biased(cfg, p, s0, s1, s2, st, grad, b);
+    p1 = b.p1;
+    p2 = b.p2;
 }
 // on memory: state planes `n_params` words apart
 __device__ __forceinline__ void optimizer_update(const bsvi_opt_cfg& cfg, float* params, float* state,

@@ -394,15 +394,35 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
     const bool has_draw_wave = false, draw_wave = false, fed_wave = false;
     const uint32_t fed_index = 1u;
 #endif
+    // The owners on a draw wave (round 7; a kernel variant of its own, SPEC_WITH_DRAW_OWNERS, launched with the draw service only):
+    // the owners' epilogue leaves sample wave 1 for the service's draw wave on the same SIMD (wave 5), whose loop of its own keeps
+    // the owner state in registers for the whole launch, evaluates what depends on theta and the step count alone while the bodies
+    // run, and after the second barrier is left with the sums -> gradient -> step -> new table.  The sample waves go straight from
+    // the second barrier to the next first one.  Every set of normals is drawn while the bodies run (see the draw loop below).
+#if SPEC_DRAW_WAVE && defined(SPEC_WITH_DRAW_OWNERS) && !SPEC_EXCHANGE
+#define SPEC_DRAW_OWNERS 1
+    const uint32_t own_wave = WSN + ((1u - WSN) & 3u);        // the first draw wave on the owners' SIMD (wave & 3 == 1)
+#else
+#define SPEC_DRAW_OWNERS 0
+#endif
+#if SPEC_DRAW_OWNERS
+    const uint32_t own_base = own_wave * 64u;
+#else
     const uint32_t own_base = has_draw_wave ? fed_index * 64u
                             : (!SPEC_GENERIC_OWNERS && SPEC_OWNER_WAVE * 64u + SPEC_N_PARAMS <= nthreads) ? SPEC_OWNER_WAVE * 64u : 0u;
+#endif
     const uint32_t oid = tid - own_base;                      // the parameter this thread owns (if < SPEC_N_PARAMS)
     bool own_fast = false;
+#if SPEC_DRAW_OWNERS
+    SpecOwn own = {};                                         // (the owners' registers: never written to LDS)
+#endif
     if (oid < SPEC_N_PARAMS) {
         const uint32_t j0 = TAB[SPEC_TAB_PTR + oid], j1 = TAB[SPEC_TAB_PTR + oid + 1];
         if (j1 - j0 <= 2u) {
             own_fast = true;
+#if !SPEC_DRAW_OWNERS
             SpecOwn own;
+#endif
             own.n = j1 - j0;
             own.mask = 0;
             own.theta = PS[oid];
@@ -431,7 +451,9 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
                     own.b[e] = __uint_as_float(TAB[4 * k + 3]);
                 }
             }
+#if !SPEC_DRAW_OWNERS
             spec_own_store(OWN + 5 * oid, own);
+#endif
         }
     }
 
@@ -480,8 +502,22 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
 #if defined(SPEC_DEBUG_STAMPS)        // timing experiment (tools/spec_stamps.py): s_memtime at the phase boundaries of one iteration
     unsigned long long stamp[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #define SPEC_STAMP(i) if (it == n_it / 2) stamp[i] = __builtin_amdgcn_s_memtime()
+    // per wave, whatever its role (tools/spec_role_stamps.py): 0 past the first barrier, 1 at the second, 2 past it, 3 the owners'
+    // sums read, 4 the iteration's work done, 5 past the NEXT first barrier; written by lane 0 of every wave at the end
+    unsigned long long rstamp[6] = {0, 0, 0, 0, 0, 0};
+#define SPEC_RSTAMP(i) if (it == n_it / 2) rstamp[i] = __builtin_amdgcn_s_memtime()
+#define SPEC_RSTAMP_NEXT() if (it == n_it / 2 + 1u) rstamp[5] = __builtin_amdgcn_s_memtime()
+#define SPEC_RSTAMP_WRITE()                                                                                              \
+    if (lane == 0u && SPEC_A->loss_slot && n_it > 16u + 8u * SPEC_MAX_WAVES) {                                           \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                                 \
+        for (int i = 1; i < 6; ++i) SPEC_A->loss_slot[16u + 8u * wave + i] = (float)(rstamp[i] - rstamp[0]);               \
+        SPEC_A->loss_slot[16u + 8u * wave] = 1.0f;                                                                       \
+    }
 #else
 #define SPEC_STAMP(i)
+#define SPEC_RSTAMP(i)
+#define SPEC_RSTAMP_NEXT()
+#define SPEC_RSTAMP_WRITE()
 #endif
     // One workgroup, noise kept in registers, lean build: the NEXT iteration's standard normals do not depend on anything
     // this iteration computes, and most waves have idle time right after their body — N = 300 is five waves on four SIMDs,
@@ -518,12 +554,136 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
             Tn.vz = T.vz;
             spec_draw(B0, Tn, Zd);
         };
+#if SPEC_DRAW_OWNERS
+        (void)has_first; (void)has_second;
+        // Whole sets, all drawn while the bodies run (tools/spec_role_stamps.py: a set of 21 rows is ~3 000 cycles of a draw
+        // wave, the bodies ~6 500): the owners' wave draws set 0 in front of its epilogue work and stores it at once, into the
+        // buffer of the iteration's parity (set 0 has two, the second behind the WSN sets: sample wave 0 reads the other one
+        // meanwhile), so nothing of the draws is left on the owners' chain; the other draw waves share the remaining sets
+        // evenly (five sample waves: 1, 2 | 3, 4; four: one each), keep them in registers and store them behind the second
+        // barrier, beside the owners' epilogue.
+        const uint32_t kown = own_wave - WSN, n_other = n_draw - 1u, rest = WSN - 1u;
+        const uint32_t j = k < kown ? k : k - 1u, per = rest / n_other, extra = rest % n_other;
+        const uint32_t set_a = __builtin_amdgcn_readfirstlane(1u + j * per + (j < extra ? j : extra));
+        const uint32_t n_sets = __builtin_amdgcn_readfirstlane(per + (j < extra ? 1u : 0u));     // (<= 2: rest <= 4, n_other >= 2)
+        const bool owners = __builtin_amdgcn_readfirstlane(wave == own_wave ? 1 : 0) != 0;     // (wave-uniform: the branches below are scalar)
+        for (uint32_t it = 0; it < n_it; ++it) {
+            const bool more = it + 1u < n_it, last = !more;
+            spec_lds_barrier();                                // (the main loop's first barrier: the sample waves read their buffers behind it)
+            SPEC_RSTAMP(0);
+            SPEC_RSTAMP_NEXT();
+            SpecNoise Za, Zb;
+            float fac[2] = {0.0f, 0.0f};
+            AdamBias bias = {1.0, 1.0, 0.0f, 0.0f};
+            if (owners) {
+                // ---- beside the bodies: what depends on this iteration's theta and the step count only, then set 0
+                SPEC_RELOAD_ARGS();
+                const bsvi_opt_cfg cfg = SPEC_A->cfg;
+#pragma unroll
+                for (uint32_t e = 0; e < 2u; ++e) fac[e] = own.b[e] * spec_utransform_grad(own.tr[e], own.theta);
+                if (cfg.kind != BSVI_OPT_SGD) bias = optimizer_adam_bias(cfg, own.p1, own.p2);     // (kept when the step is taken)
+                if (more) {
+                    draw_for(0u, off0 + it + 1u, Za);
+                    float* const buf = NZB + (((it + 1u) & 1u) ? WSN * (SPEC_KEEP_NOISE * 64u) : 0u);
+#pragma unroll
+                    for (uint32_t r = 0; r < SPEC_KEEP_NOISE; ++r) buf[64u * r] = Za.z[r];
+                }
+            } else if (more) {
+                draw_for(set_a, off0 + it + 1u, Za);          // in registers
+                if (n_sets > 1u) draw_for(set_a + 1u, off0 + it + 1u, Zb);
+            }
+            SPEC_RSTAMP(1);
+            spec_lds_barrier();                                // (the second: every wave's sums are in WS / RED, the buffers are free)
+            SPEC_RSTAMP(2);
+            if (owners) {
+                // ---- the owners' epilogue (as the main loop's below, on registers): the loss rows and both positions' rows
+                //      requested together, gradient, step, the new table
+                SPEC_RELOAD_ARGS();
+                float* const out = SPEC_A->out;
+                float* const loss_slot = SPEC_A->loss_slot;
+                float* const finite_slot = SPEC_A->finite_slot;
+                const bsvi_opt_cfg cfg = SPEC_A->cfg;
+                float vs = 0.0f, vb = 0.0f;
+#pragma unroll
+                for (uint32_t w = 0; w < SPEC_MAX_WAVES; ++w) {
+                    const float a = RED[8 + 2 * w], b = RED[9 + 2 * w];
+                    vs += w < W ? a : 0.0f;
+                    vb += w < W ? b : 0.0f;
+                }
+                float tot[2];
+#pragma unroll
+                for (uint32_t e = 0; e < 2u; ++e) tot[e] = spec_pos_total(WS, own.pos[e], W);
+                const float finite = isfinite(vs) ? 1.0f : 0.0f;
+                const float loss = -vs / (float)n_global;
+                if (oid == 0u) {
+                    if (last) { out[0] = vs; out[1] = vb; out[2] = loss; out[3] = finite; }
+                    if (loss_slot) loss_slot[it] = loss;
+                    if (finite_slot) finite_slot[it] = finite;
+                }
+                const float scale = -1.0f / (float)n_global;   // (the loop mode always steps)
+                const uint32_t mask_bit = it <= pretraining ? 2u : 1u;
+                if (own_fast) {
+                    float gsum = 0.0f;
+#pragma unroll
+                    for (uint32_t e = 0; e < 2u; ++e) {
+                        const float term = tot[e] * fac[e];
+                        gsum += e < own.n ? term : 0.0f;
+                    }
+                    const float grad = gsum * scale;
+                    SPEC_RSTAMP(3);
+                    if (last) out[BSVI_OUT_HEADER + oid] = grad;
+                    if (finite != 0.0f && (own.mask & mask_bit)) {
+                        if (cfg.kind == BSVI_OPT_SGD) {
+                            optimizer_apply(cfg, own.theta, own.s0, own.s1, own.s2, own.st, grad);
+                        } else {
+                            optimizer_apply_adam_biased(cfg, own.theta, own.s0, own.s1, own.s2, own.st, grad, bias);
+                            own.p1 = bias.p1;
+                            own.p2 = bias.p2;
+                        }
+                    }
+                    if (last) {
+                        float* const params = SPEC_A->params;
+                        float* const state = SPEC_A->state;
+                        params[oid] = own.theta;
+                        if (state) {
+                            state[oid] = own.s0;
+                            state[(size_t)SPEC_N_PARAMS + oid] = own.s1;
+                            state[2 * (size_t)SPEC_N_PARAMS + oid] = own.s2;
+                            state[3 * (size_t)SPEC_N_PARAMS + oid] = own.st;
+                        }
+                    } else {
+                        // g(theta) once when both entries carry the same transform (the prior's scale entries reuse the
+                        // posterior's parameter): the same function of the same value
+                        const float g0 = utransform_common(own.tr[0], own.theta);
+                        float g1 = g0;
+                        if (own.n == 2u && own.tr[1] != own.tr[0]) g1 = utransform_common(own.tr[1], own.theta);
+                        if (own.n > 0u) spec_store_uniform(own.k[0], own.a[0] + own.b[0] * g0);
+                        if (own.n > 1u) spec_store_uniform(own.k[1], own.a[1] + own.b[1] * g1);
+                    }
+                }
+            } else if (more) {
+#pragma unroll
+                for (uint32_t r = 0; r < SPEC_KEEP_NOISE; ++r) NZB[set_a * (SPEC_KEEP_NOISE * 64u) + 64u * r] = Za.z[r];
+                if (n_sets > 1u) {
+#pragma unroll
+                    for (uint32_t r = 0; r < SPEC_KEEP_NOISE; ++r) NZB[(set_a + 1u) * (SPEC_KEEP_NOISE * 64u) + 64u * r] = Zb.z[r];
+                }
+            }
+            SPEC_RSTAMP(4);
+        }
+        SPEC_RSTAMP_WRITE();
+        return;
+#else
         for (uint32_t it = 0; it < n_it; ++it) {
             const bool more = it + 1u < n_it;
             spec_lds_barrier();                                // (the main loop's first barrier: the sample waves read their buffers behind it)
+            SPEC_RSTAMP(0);
+            SPEC_RSTAMP_NEXT();
             SpecNoise Za;
             if (more && has_first) draw_for(first, off0 + it + 1u, Za);     // beside the bodies, in registers
+            SPEC_RSTAMP(1);
             spec_lds_barrier();                                // (the second: the buffers are free)
+            SPEC_RSTAMP(2);
             if (more) {
                 if (has_first) {
 #pragma unroll
@@ -536,8 +696,11 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
                     for (uint32_t r = 0; r < SPEC_KEEP_NOISE; ++r) NZB[second * (SPEC_KEEP_NOISE * 64u) + 64u * r] = Zb.z[r];
                 }
             }
+            SPEC_RSTAMP(4);
         }
+        SPEC_RSTAMP_WRITE();
         return;
+#endif
     }
 #endif
     for (uint32_t it = 0; it < n_it; ++it) {
@@ -584,14 +747,21 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
             SPEC_STAMP(1);
             if (chunk == 0) {
                 spec_lds_barrier();                            // the uniform table of this iteration is complete ...
+                SPEC_RSTAMP(0);
+                SPEC_RSTAMP_NEXT();
 #if SPEC_ACCUMULATE_CHUNKS
                 for (uint32_t k = lane; k < SPEC_WS_CELLS; k += 64u) WSw[k] = 0.0f;     // ... and the last one's sums are consumed
 #endif
             }
 #if SPEC_DRAW_WAVE
             if (fed_wave && it > 0u) {                         // drawn by the draw wave beside the last epilogue
+#if SPEC_DRAW_OWNERS
+                const float* const nz = NZ + ((wave == 0u && (it & 1u)) ? WSN * (SPEC_KEEP_NOISE * 64u) : 0u);     // (set 0: two buffers)
+#else
+                const float* const nz = NZ;
+#endif
 #pragma unroll
-                for (uint32_t r = 0; r < SPEC_KEEP_NOISE; ++r) Z.z[r] = NZ[64u * r];
+                for (uint32_t r = 0; r < SPEC_KEEP_NOISE; ++r) Z.z[r] = nz[64u * r];
             }
 #endif
             SPEC_STAMP(2);
@@ -630,8 +800,14 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
             noise_ready = true;
         }
 #endif
+        SPEC_RSTAMP(1);
         spec_lds_barrier();                                    // every wave's sums are in WS / RED
         SPEC_STAMP(5);
+        SPEC_RSTAMP(2);
+#if SPEC_DRAW_OWNERS
+        SPEC_RSTAMP(4);
+        continue;                                              // (the epilogue runs on the owners' draw wave)
+#endif
 #if SPEC_DRAW_WAVE
         if (draw_wave && it + 1u < n_it) {                     // (the owners' wave read the last set behind the barrier before the body)
             const unsigned long long off = off0 + it + 1u;
@@ -895,6 +1071,7 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
 #endif
             const float grad = gsum * scale;
             SPEC_STAMP(8);
+            SPEC_RSTAMP(3);
             if (last || !step) out[BSVI_OUT_HEADER + oid] = grad;
             if (step) {
                 if (finite != 0.0f && (own.mask & mask_bit))
@@ -969,7 +1146,9 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
         }
 #endif
         SPEC_STAMP(6);
+        SPEC_RSTAMP(4);
     }
+    SPEC_RSTAMP_WRITE();
 #if defined(SPEC_DEBUG_STAMPS)
     float* const loss_slot = SPEC_A->loss_slot;
     if (tid == 0 && loss_slot && n_it > 16) {

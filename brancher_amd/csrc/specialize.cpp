@@ -619,8 +619,9 @@ struct Spec {
     uint32_t n_pos = 0;                                   // positions of the transpose tile (>= n_ugrad)
     Geom geom[2];
     std::vector<uint32_t> pu_ptr_host, pu_pos_host, pu_idx_host;   // CSR theta -> (position, uniform entry)
-    Variant variant[6];                                   // [geometry][0 lean, 1 diagnostic]; 4: lean one-workgroup kernel with the draw wave;
-                                                          // 5: the same with the cross-rank exchange inside the training loop (spec_main.h)
+    Variant variant[7];                                   // [geometry][0 lean, 1 diagnostic]; 4: lean one-workgroup kernel with the draw wave;
+                                                          // 5: the same with the cross-rank exchange inside the training loop (spec_main.h);
+                                                          // 6: 4 with the owners' epilogue on a draw wave of the draw service
     bool exchange_ok = false;                             // every parameter has its owner in one wave: the in-loop exchange serves
     void* dev = nullptr;                                  // [tickets: 256 B][pu_ptr][pu_pos][pu_idx]
     unsigned int* tickets = nullptr;
@@ -747,6 +748,7 @@ Spec* create(const bsvi_program_desc& d, std::string& why) {
     }
     // (a kernel of its own: the extra roles cost the plain loop 3 % when they are merely compiled in)
     s->variant[4].src = "#define SPEC_WITH_DRAW_WAVE 1\n" + s->variant[0].src;
+    s->variant[6].src = "#define SPEC_WITH_DRAW_WAVE 1\n#define SPEC_WITH_DRAW_OWNERS 1\n" + s->variant[0].src;
     s->exchange_ok = true;       // (owners in one wave: the wave exchanges; otherwise every thread exchanges its own parameters' entries)
     s->variant[5].src = std::string("#define SPEC_WITH_EXCHANGE 1\n") + (s->draw_wave_ok ? "#define SPEC_WITH_DRAW_WAVE 1\n" : "") + s->variant[0].src;
     return s;
@@ -782,7 +784,7 @@ int upload(Spec* s) {
 }
 
 // variant: 0 training kernel, 1 diagnostic kernel of the one-workgroup geometry; 2, 3 the same of the many-workgroup one
-const std::string& source(const Spec* s, int variant) { return s->variant[(variant == 4 || variant == 5) ? variant : (variant & 3)].src; }
+const std::string& source(const Spec* s, int variant) { return s->variant[(variant >= 4 && variant <= 6) ? variant : (variant & 3)].src; }
 
 // ---------------------------------------------------------------------------------------------------------------
 //  hiprtc
@@ -1043,7 +1045,7 @@ static int ensure_compiled(Spec* s, int v) {
 // ---------------------------------------------------------------------------------------------------------------
 //  launch
 // ---------------------------------------------------------------------------------------------------------------
-struct Geo { uint32_t blocks, threads; int geom; bool draw_wave = false; uint32_t extra_waves = 0; };
+struct Geo { uint32_t blocks, threads; int geom; bool draw_wave = false; uint32_t extra_waves = 0; bool draw_owners = false; };
 // The in-kernel loop is given one wave more than the samples need: it carries no samples and draws the next iteration's
 // normals of the owners' wave, whose chain — draw, body, sums, epilogue — is what an iteration takes (spec_main.h).
 static bool draw_wave() {
@@ -1052,6 +1054,11 @@ static bool draw_wave() {
 }
 static bool draw_service() {
     const char* e = getenv("BSVI_SPEC_DRAW_SERVICE");     // (read per call: the tests switch it within a process)
+    return !(e && e[0] == '0');
+}
+// The draw service's owners' epilogue on a draw wave (spec_main.h, SPEC_DRAW_OWNERS; BSVI_SPEC_OWNER_WAVE=0: on sample wave 1 as before)
+static bool owner_wave() {
+    const char* e = getenv("BSVI_SPEC_OWNER_WAVE");       // (read per call: the tests switch it within a process)
     return !(e && e[0] == '0');
 }
 static Geo geo(const Spec* s, uint32_t n_local, int mode = MODE_SUMS, bool exchange = false) {
@@ -1068,7 +1075,9 @@ static Geo geo(const Spec* s, uint32_t n_local, int mode = MODE_SUMS, bool excha
                              && waves + n_service <= s->geom[GEOM_ONE].max_threads / 64 && (size_t)s->n_noise * 64u * waves <= (size_t)n_service * 64u * 68u
                              && !s->variant[exchange ? 5 : 4].failed;
         const uint32_t more = service ? n_service : extra ? 1u : 0u;
-        return Geo{1, (waves + more) * 64, GEOM_ONE, more != 0u, more};
+        // (the owners on a draw wave: one more buffer, for the set the owners' wave draws — spec_main.h, SPEC_DRAW_OWNERS)
+        const bool owners = service && (size_t)s->n_noise * 64u * (waves + 1u) <= (size_t)n_service * 64u * 68u;
+        return Geo{1, (waves + more) * 64, GEOM_ONE, more != 0u, more, owners};
     }
     // many samples: 256-thread workgroups (one wave per SIMD), two per CU at most; beyond that every workgroup walks
     // several chunks of 256 samples
@@ -1124,6 +1133,11 @@ int launch(Spec* s, const bsvi_program* p, const Launch& L) {
             const int rc5 = ensure_compiled(s, 5);
             if (rc5) return rc5;
             v = 5;
+        }
+        else if (g.draw_owners && v == 0 && owner_wave()) {
+            const int rc6 = ensure_compiled(s, 6);
+            if (rc6) return rc6;
+            v = 6;
         }
         else if (g.draw_wave && v == 0 && ensure_compiled(s, 4) == BSVI_OK) v = 4;
         else if (g.draw_wave) { g.threads -= 64 * g.extra_waves; g.draw_wave = false; }        // (diagnostic kernel, or the variant did not compile)
