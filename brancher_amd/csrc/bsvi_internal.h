@@ -68,6 +68,7 @@ int compile(const std::string& src, std::vector<char>& code, std::string& log);
 // origin: 1 hiprtc, 2 process cache, 3 disk cache
 int obtain(const std::string& src, std::vector<char>& code, std::string& log, int* origin);
 int last_origin();
+int last_variant();     // variant of this thread's last launch of a specialised kernel, -1: none yet
 std::string cache_directory();
 std::string compiler_identity();
 // bytes of workspace a launch over n_local samples needs behind the interpreter's region

@@ -2308,6 +2308,7 @@ extern "C" int bsvi_jit_load(const char* source, size_t* code_bytes, int* origin
 }
 
 extern "C" int bsvi_jit_last_origin(void) { return bsvi_spec::last_origin(); }
+extern "C" int bsvi_spec_last_variant(void) { return bsvi_spec::last_variant(); }
 
 extern "C" size_t bsvi_jit_cache_dir(char* buf, size_t capacity) {
     const std::string dir = bsvi_spec::cache_directory();

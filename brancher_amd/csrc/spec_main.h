@@ -20,9 +20,11 @@ namespace bsvi {
 // pointer the optimiser cannot see through.
 #if defined(__HIP_DEVICE_COMPILE__)
 #define SPEC_CONST_AS __attribute__((address_space(4)))
+#define SPEC_GLOBAL_AS __attribute__((address_space(1)))
 #define SPEC_RELOAD_ARGS() asm volatile("" : "+s"(ka))
 #else
 #define SPEC_CONST_AS
+#define SPEC_GLOBAL_AS
 #define SPEC_RELOAD_ARGS()
 #endif
 
@@ -82,6 +84,19 @@ __device__ __forceinline__ void spec_publish_uniform(const uint32_t* TAB, uint32
     spec_store_uniform(k, __uint_as_float(TAB[4 * k + 2]) + __uint_as_float(TAB[4 * k + 3]) * utransform_common(w1 & 0xFFu, x));
 }
 
+// The most uniform entries a parameter of this program owns, 1 or 2 (specialize.cpp): the owners' code handles that many.
+// Every parameter of a scalar model owns one — the second position's row of sums, its chain-rule factor and its guarded
+// store were read, multiplied and not selected in every iteration.
+#ifndef SPEC_OWN_ENTRIES
+#define SPEC_OWN_ENTRIES 2
+#endif
+// rows of sums already in registers, added waves in order (every row is a wave's: the caller runs with a full workgroup)
+__device__ __forceinline__ float spec_rows_total(const float (&r)[SPEC_MAX_WAVES]) {
+    float s = 0.0f;
+#pragma unroll
+    for (uint32_t w = 0; w < SPEC_MAX_WAVES; ++w) s += r[w];
+    return s;
+}
 // What the thread that owns parameter `tid` keeps in registers across the iterations of a launch (parameters beyond
 // the workgroup size, or with more than two uniform entries, go through the LDS working copy instead)
 struct SpecOwn {
@@ -405,6 +420,15 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
 #else
 #define SPEC_DRAW_OWNERS 0
 #endif
+// The lean chain (SPEC_LEAN_CHAIN, a define of the generated source): behind the second barrier the owners' wave is the
+// iteration, so it does there only what the next table needs — the argument words are loaded beside the bodies and kept, the
+// LDS rows are requested in one batch, and the loss bookkeeping (a full-precision division, the stores) follows the table.
+// Programs with a two-entry parameter keep the epilogue as it was.
+#if SPEC_DRAW_OWNERS && defined(SPEC_LEAN_CHAIN) && !defined(SPEC_DEBUG_NO_LEAN_CHAIN) && SPEC_OWN_ENTRIES == 1
+#define SPEC_LEAN_OWNERS 1
+#else
+#define SPEC_LEAN_OWNERS 0
+#endif
 #if SPEC_DRAW_OWNERS
     const uint32_t own_base = own_wave * 64u;
 #else
@@ -441,7 +465,7 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
                 }
             }
 #pragma unroll
-            for (uint32_t e = 0; e < 2u; ++e) {
+            for (uint32_t e = 0; e < SPEC_OWN_ENTRIES; ++e) {
                 if (e < own.n) {
                     const uint32_t k = TAB[SPEC_TAB_IDX + j0 + e];
                     own.pos[e] = TAB[SPEC_TAB_POS + j0 + e];
@@ -504,13 +528,14 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
 #define SPEC_STAMP(i) if (it == n_it / 2) stamp[i] = __builtin_amdgcn_s_memtime()
     // per wave, whatever its role (tools/spec_role_stamps.py): 0 past the first barrier, 1 at the second, 2 past it, 3 the owners'
     // sums read, 4 the iteration's work done, 5 past the NEXT first barrier; written by lane 0 of every wave at the end
-    unsigned long long rstamp[6] = {0, 0, 0, 0, 0, 0};
+    // (6: the owners' new table published — lean chain: what is left behind it is bookkeeping)
+    unsigned long long rstamp[7] = {0, 0, 0, 0, 0, 0, 0};
 #define SPEC_RSTAMP(i) if (it == n_it / 2) rstamp[i] = __builtin_amdgcn_s_memtime()
 #define SPEC_RSTAMP_NEXT() if (it == n_it / 2 + 1u) rstamp[5] = __builtin_amdgcn_s_memtime()
 #define SPEC_RSTAMP_WRITE()                                                                                              \
     if (lane == 0u && SPEC_A->loss_slot && n_it > 16u + 8u * SPEC_MAX_WAVES) {                                           \
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                                 \
-        for (int i = 1; i < 6; ++i) SPEC_A->loss_slot[16u + 8u * wave + i] = (float)(rstamp[i] - rstamp[0]);               \
+        for (int i = 1; i < 7; ++i) SPEC_A->loss_slot[16u + 8u * wave + i] = rstamp[i] ? (float)(rstamp[i] - rstamp[0]) : 0.0f; \
         SPEC_A->loss_slot[16u + 8u * wave] = 1.0f;                                                                       \
     }
 #else
@@ -567,6 +592,12 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
         const uint32_t set_a = __builtin_amdgcn_readfirstlane(1u + j * per + (j < extra ? j : extra));
         const uint32_t n_sets = __builtin_amdgcn_readfirstlane(per + (j < extra ? 1u : 0u));     // (<= 2: rest <= 4, n_other >= 2)
         const bool owners = __builtin_amdgcn_readfirstlane(wave == own_wave ? 1 : 0) != 0;     // (wave-uniform: the branches below are scalar)
+        const float own_scale = -1.0f / (float)n_global;       // (the loop mode always steps)
+        (void)own_scale;
+#if SPEC_LEAN_OWNERS
+        // (the lean epilogue adds the rows of all SPEC_MAX_WAVES waves: the host launches the service with a full workgroup only)
+        if (W != SPEC_MAX_WAVES) __builtin_trap();
+#endif
         for (uint32_t it = 0; it < n_it; ++it) {
             const bool more = it + 1u < n_it, last = !more;
             spec_lds_barrier();                                // (the main loop's first barrier: the sample waves read their buffers behind it)
@@ -580,7 +611,7 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
                 SPEC_RELOAD_ARGS();
                 const bsvi_opt_cfg cfg = SPEC_A->cfg;
 #pragma unroll
-                for (uint32_t e = 0; e < 2u; ++e) fac[e] = own.b[e] * spec_utransform_grad(own.tr[e], own.theta);
+                for (uint32_t e = 0; e < SPEC_OWN_ENTRIES; ++e) fac[e] = own.b[e] * spec_utransform_grad(own.tr[e], own.theta);
                 if (cfg.kind != BSVI_OPT_SGD) bias = optimizer_adam_bias(cfg, own.p1, own.p2);     // (kept when the step is taken)
                 if (more) {
                     draw_for(0u, off0 + it + 1u, Za);
@@ -592,9 +623,109 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
                 draw_for(set_a, off0 + it + 1u, Za);          // in registers
                 if (n_sets > 1u) draw_for(set_a + 1u, off0 + it + 1u, Zb);
             }
+#if SPEC_LEAN_OWNERS
+            // The epilogue's words of the argument block, loaded HERE (behind the draw: they are not live across its key
+            // schedule) and kept in scalar registers across the barrier — a scalar load behind it is a round trip to the
+            // scalar cache in front of the LDS reads, which wait on the same counter.  This loop has no spec_body, which is
+            // what the main loop re-reads them for.  (Through an empty statement: the loads cannot sink to their uses.)
+            //  The pointers as global-memory pointers: behind the empty statement the compiler no longer knows where they came
+            //  from, and a store through a generic pointer also counts on the LDS counter the next barrier waits for.)
+            typedef SPEC_GLOBAL_AS float* spec_gptr;
+            spec_gptr e_out = nullptr, e_loss = nullptr, e_finite = nullptr, e_params = nullptr, e_state = nullptr;
+            bsvi_opt_cfg e_cfg = {};
+            if (owners) {
+                SPEC_RELOAD_ARGS();
+                e_out = (spec_gptr)SPEC_A->out; e_loss = (spec_gptr)SPEC_A->loss_slot; e_finite = (spec_gptr)SPEC_A->finite_slot;
+                e_params = (spec_gptr)SPEC_A->params; e_state = (spec_gptr)SPEC_A->state;
+                e_cfg = SPEC_A->cfg;
+#if defined(__HIP_DEVICE_COMPILE__)
+                asm volatile("" : "+s"(e_out), "+s"(e_loss), "+s"(e_finite), "+s"(e_params), "+s"(e_state));
+                asm volatile("" : "+s"(e_cfg.kind), "+s"(e_cfg.lr), "+s"(e_cfg.momentum), "+s"(e_cfg.dampening), "+s"(e_cfg.weight_decay),
+                             "+s"(e_cfg.nesterov), "+s"(e_cfg.beta1), "+s"(e_cfg.beta2), "+s"(e_cfg.eps), "+s"(e_cfg.amsgrad), "+s"(e_cfg.maximize));
+#endif
+            }
+#endif
             SPEC_RSTAMP(1);
             spec_lds_barrier();                                // (the second: every wave's sums are in WS / RED, the buffers are free)
             SPEC_RSTAMP(2);
+#if SPEC_LEAN_OWNERS
+            if (owners) {
+                // ---- the owners' epilogue, lean: every LDS word it needs requested in one batch — the waves' loss rows and
+                //      the position's rows (literal addresses; the service fills the workgroup, W == SPEC_MAX_WAVES, checked at
+                //      the top of this loop: every row is a wave's, none is read and not selected) — then sums (waves in order)
+                //      -> gradient -> step -> the new table, and only then the bookkeeping.  One entry per parameter.
+                float ra[SPEC_MAX_WAVES], rb[SPEC_MAX_WAVES], rp[SPEC_MAX_WAVES];
+                spec_f4 rq[SPEC_MAX_WAVES / 2];               // (RED + 8: value and non-finite count per wave, two waves per 16 bytes)
+#pragma unroll
+                for (uint32_t q = 0; q < SPEC_MAX_WAVES / 2; ++q) rq[q] = reinterpret_cast<const spec_f4*>(RED + 8)[q];
+#pragma unroll
+                for (uint32_t w = 0; w < SPEC_MAX_WAVES; ++w) rp[w] = WS[w * SPEC_WS_PAD + own.pos[0]];
+                // (one statement that needs them all: every read is issued in front of it and waited for once — left to itself
+                //  the compiler sinks the position rows into the branch below and waits for each pair of them in turn)
+#if defined(__HIP_DEVICE_COMPILE__) && SPEC_MAX_WAVES == 8
+#define SPEC_PIN8(a) "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7])
+                asm volatile("" : "+v"(rq[0]), "+v"(rq[1]), "+v"(rq[2]), "+v"(rq[3]), SPEC_PIN8(rp));
+#undef SPEC_PIN8
+#endif
+#pragma unroll
+                for (uint32_t w = 0; w < SPEC_MAX_WAVES; ++w) {
+                    ra[w] = (w & 1u) ? rq[w / 2].z : rq[w / 2].x;
+                    rb[w] = (w & 1u) ? rq[w / 2].w : rq[w / 2].y;
+                }
+                const float tot = spec_rows_total(rp);
+                const float vs = spec_rows_total(ra);
+                const float finite = isfinite(vs) ? 1.0f : 0.0f;       // (all the step needs of the loss)
+                const uint32_t mask_bit = it <= pretraining ? 2u : 1u;
+                float grad = 0.0f;
+                if (own_fast) {
+                    float gsum = 0.0f;
+                    const float term = tot * fac[0];
+                    gsum += own.n > 0u ? term : 0.0f;
+                    grad = gsum * own_scale;
+                    SPEC_RSTAMP(3);
+                    if (finite != 0.0f && (own.mask & mask_bit)) {
+                        if (e_cfg.kind == BSVI_OPT_SGD) {
+                            optimizer_apply(e_cfg, own.theta, own.s0, own.s1, own.s2, own.st, grad);
+                        } else {
+                            optimizer_apply_adam_biased(e_cfg, own.theta, own.s0, own.s1, own.s2, own.st, grad, bias);
+                            own.p1 = bias.p1;
+                            own.p2 = bias.p2;
+                        }
+                    }
+                    if (more) {
+                        const float g0 = utransform_common(own.tr[0], own.theta);
+                        if (own.n > 0u) spec_store_uniform(own.k[0], own.a[0] + own.b[0] * g0);
+                    }
+                }
+                asm volatile("" ::: "memory");                 // (the table's stores stay in front of the bookkeeping's)
+                SPEC_RSTAMP(6);
+                // ---- behind the table: the loss (a full-precision division), the curve, the launch's output block
+                const float loss = -vs / (float)n_global;
+                if (oid == 0u) {
+                    const float vb = spec_rows_total(rb);
+                    if (last) { e_out[0] = vs; e_out[1] = vb; e_out[2] = loss; e_out[3] = finite; }
+                    if (e_loss) e_loss[it] = loss;
+                    if (e_finite) e_finite[it] = finite;
+                }
+                if (own_fast && last) {
+                    e_out[BSVI_OUT_HEADER + oid] = grad;
+                    e_params[oid] = own.theta;
+                    if (e_state) {
+                        e_state[oid] = own.s0;
+                        e_state[(size_t)SPEC_N_PARAMS + oid] = own.s1;
+                        e_state[2 * (size_t)SPEC_N_PARAMS + oid] = own.s2;
+                        e_state[3 * (size_t)SPEC_N_PARAMS + oid] = own.st;
+                    }
+                }
+            } else if (more) {
+#pragma unroll
+                for (uint32_t r = 0; r < SPEC_KEEP_NOISE; ++r) NZB[set_a * (SPEC_KEEP_NOISE * 64u) + 64u * r] = Za.z[r];
+                if (n_sets > 1u) {
+#pragma unroll
+                    for (uint32_t r = 0; r < SPEC_KEEP_NOISE; ++r) NZB[(set_a + 1u) * (SPEC_KEEP_NOISE * 64u) + 64u * r] = Zb.z[r];
+                }
+            }
+#else
             if (owners) {
                 // ---- the owners' epilogue (as the main loop's below, on registers): the loss rows and both positions' rows
                 //      requested together, gradient, step, the new table
@@ -612,7 +743,7 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
                 }
                 float tot[2];
 #pragma unroll
-                for (uint32_t e = 0; e < 2u; ++e) tot[e] = spec_pos_total(WS, own.pos[e], W);
+                for (uint32_t e = 0; e < SPEC_OWN_ENTRIES; ++e) tot[e] = spec_pos_total(WS, own.pos[e], W);
                 const float finite = isfinite(vs) ? 1.0f : 0.0f;
                 const float loss = -vs / (float)n_global;
                 if (oid == 0u) {
@@ -625,7 +756,7 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
                 if (own_fast) {
                     float gsum = 0.0f;
 #pragma unroll
-                    for (uint32_t e = 0; e < 2u; ++e) {
+                    for (uint32_t e = 0; e < SPEC_OWN_ENTRIES; ++e) {
                         const float term = tot[e] * fac[e];
                         gsum += e < own.n ? term : 0.0f;
                     }
@@ -669,6 +800,7 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
                     for (uint32_t r = 0; r < SPEC_KEEP_NOISE; ++r) NZB[(set_a + 1u) * (SPEC_KEEP_NOISE * 64u) + 64u * r] = Zb.z[r];
                 }
             }
+#endif
             SPEC_RSTAMP(4);
         }
         SPEC_RSTAMP_WRITE();
@@ -996,7 +1128,7 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
                 const SpecOwn own = spec_own_load(OWN + 5 * oid);
                 float g = 0.0f;
 #pragma unroll
-                for (uint32_t e = 0; e < 2u; ++e) {
+                for (uint32_t e = 0; e < SPEC_OWN_ENTRIES; ++e) {
                     const float term = spec_pos_total(WS, own.pos[e], rows) * (own.b[e] * spec_utransform_grad(own.tr[e], own.theta));
                     g += e < own.n ? term : 0.0f;
                 }
@@ -1027,9 +1159,9 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
                 const SpecOwn own = spec_own_load(OWN + 5 * oid);
                 float tot[2];
 #pragma unroll
-                for (uint32_t e = 0; e < 2u; ++e) tot[e] = spec_pos_total(WS, own.pos[e], rows);
+                for (uint32_t e = 0; e < SPEC_OWN_ENTRIES; ++e) tot[e] = spec_pos_total(WS, own.pos[e], rows);
 #pragma unroll
-                for (uint32_t e = 0; e < 2u; ++e) {
+                for (uint32_t e = 0; e < SPEC_OWN_ENTRIES; ++e) {
                     const float term = tot[e] * (own.b[e] * spec_utransform_grad(own.tr[e], own.theta));
                     xgsum += e < own.n ? term : 0.0f;
                 }
@@ -1059,10 +1191,10 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
             // (both positions' rows requested before either sum: an unused entry has position 0, read and not selected)
             float tot[2];
 #pragma unroll
-            for (uint32_t e = 0; e < 2u; ++e) tot[e] = spec_pos_total(WS, own.pos[e], rows);
+            for (uint32_t e = 0; e < SPEC_OWN_ENTRIES; ++e) tot[e] = spec_pos_total(WS, own.pos[e], rows);
             float gsum = 0.0f;
 #pragma unroll
-            for (uint32_t e = 0; e < 2u; ++e) {
+            for (uint32_t e = 0; e < SPEC_OWN_ENTRIES; ++e) {
                 const float term = tot[e] * (own.b[e] * spec_utransform_grad(own.tr[e], own.theta));
                 gsum += e < own.n ? term : 0.0f;
             }
@@ -1092,7 +1224,7 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
                     }
                 } else {
 #pragma unroll
-                    for (uint32_t e = 0; e < 2u; ++e)
+                    for (uint32_t e = 0; e < SPEC_OWN_ENTRIES; ++e)
                         if (e < own.n) spec_store_uniform(own.k[e], own.a[e] + own.b[e] * utransform_common(own.tr[e], own.theta));
                     OWN[5 * oid] = spec_f4{own.theta, own.s0, own.s1, own.s2};
                     spec_lds[SPEC_OFF_OWN + SPEC_OWN_WORDS * oid + 4] = own.st;

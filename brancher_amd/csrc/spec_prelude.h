@@ -94,6 +94,14 @@ __device__ __forceinline__ uint32_t spec_opaque(uint32_t x) {
 #endif
     return x;
 }
+// Sums that stand for a multiply-add with a literal factor of 1 (specialize.cpp, folded constants): a + b exactly as
+// fma(a, 1, b) rounded it.  The compiler fuses a multiply into a neighbouring add where BOTH allow it; these adds do not, so
+// a product that was rounded before the fold is still rounded after it.
+__device__ __forceinline__ float spec_plus(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ float spec_exact(float x) { return spec_plus(x, 0.0f); }
 __device__ __forceinline__ PhiloxKey spec_key(const SpecBody& A, const SpecLane& T) {
     return PhiloxKey{T.nidx, A.seed_lo, A.seed_hi, T.off_lo, T.off_hi};
 }

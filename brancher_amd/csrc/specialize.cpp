@@ -76,7 +76,7 @@ std::string flit(uint32_t bits) {       // a float literal that round-trips
 
 class Emitter {
 public:
-    Emitter(const bsvi_program_desc& d, bool diag) : d_(d), diag_(diag) {
+    Emitter(const bsvi_program_desc& d, bool diag, bool fold = true) : d_(d), diag_(diag), fold_(fold) {
         keep_eps_ = d.n_noise <= kKeepEpsRows;
         // long programs: a gradient contribution leaves through its own position of the transpose tile instead of
         // waiting in an accumulator register for the entry's last contribution
@@ -148,12 +148,13 @@ public:
 
 private:
     const bsvi_program_desc& d_;
-    bool diag_;
+    bool diag_, fold_;
     bool keep_eps_ = true, counting_ = true, direct_du_ = false, reschedule_ = true, two_pass_ = false;
     int sink_mode_ = 0;         // two_pass_: 1 = a sink's value only (forward sweep), 2 = its adjoints only (reverse sweep); 0 = both
     size_t visits_ = 0;
     std::string body_;
     std::vector<uint32_t> du_total_, du_seen_, order_;
+    std::set<uint32_t> sum_defined_;      // slots whose value is a sum (loc + eps * scale): never the result of a multiply
     std::set<uint32_t> fwd_groups_, rev_groups_, all_groups_, eps_rows_, node_rows_, all_node_rows_, normal_rows_;
 
     Insn insn(uint32_t pc) const {
@@ -175,6 +176,45 @@ private:
         const Opnd p = resolve(o, e);
         return p.lane ? fmt("v_%u", p.idx) : fmt("SPEC_U(%u)", p.idx);
     }
+    // Literal constants of the model.  "An absent factor / addend is encoded as the constant 1.0 / 0.0 of the uniform table"
+    // (include/bsvi.h): an entry sourced from the program's constants with the identity transform, a = 0, b = 1 and a value
+    // of exactly 1.0f or 0.0f is known here and never changes — the program is immutable and this source is a function of it —
+    // so `x * U + U'` with such entries is x: no table reads, no multiply-add.  Exact except for the sign of a zero
+    // (-0.0f + 0.0f is 0.0f).  Returns 1, 0, or -1 for anything else.
+    int literal(uint32_t o, uint32_t e) const {
+        if (!fold_) return -1;
+        const Opnd p = resolve(o, e);
+        if (p.lane || p.idx >= d_.n_uniform || !d_.consts) return -1;
+        const bsvi_uniform_entry& u = d_.uniform[p.idx];
+        if (u.is_param || u.transform != BSVI_UT_IDENTITY || u.a != 0.0f || u.b != 1.0f || u.src >= d_.n_consts) return -1;
+        uint32_t bits;
+        memcpy(&bits, d_.consts + u.src, 4);
+        return bits == 0x3f800000u ? 1 : (bits == 0u ? 0 : -1);
+    }
+    // The folded forms keep every rounding point of the product they replace.  The compiler fuses a multiply into a
+    // neighbouring add or subtract where both allow it, and `v - a * b` rounds once where `v - (a * b + 0)` rounded twice: so
+    // a * b + 0 stays ONE fused multiply-add with a literal zero, x * 1 + c is an add that does not fuse (spec_plus,
+    // spec_prelude.h), and x * 1 + 0 is x itself only where x cannot be the result of a multiply — a table read, or a latent
+    // that was sampled as loc + eps * scale — and x + 0.0f unfused otherwise.
+    std::string exact_value(uint32_t o, uint32_t e) const {
+        const Opnd p = resolve(o, e);
+        return (!p.lane || sum_defined_.count(p.idx)) ? val(o, e) : "spec_exact(" + val(o, e) + ")";
+    }
+    // a * b + c of a Normal node's location
+    std::string affine(uint32_t a, uint32_t b, uint32_t c, uint32_t e) const {
+        const int la = literal(a, e), lb = literal(b, e), lc = literal(c, e);
+        if (lb == 1 || la == 1) {
+            const uint32_t x = lb == 1 ? a : b;
+            return lc == 0 ? exact_value(x, e) : "spec_plus(" + val(x, e) + ", " + val(c, e) + ")";
+        }
+        if (lc == 0) return "__builtin_fmaf(" + val(a, e) + ", " + val(b, e) + ", 0.0f)";
+        return val(a, e) + " * " + val(b, e) + " + " + val(c, e);
+    }
+    // scatter g * (operand `factor`) to the adjoint of operand o
+    void add_adj_times(uint32_t o, uint32_t e, const std::string& g, uint32_t factor) {
+        if (literal(factor, e) == 1) add_adj(o, e, g, true);
+        else add_adj(o, e, g + " * " + val(factor, e));
+    }
     void complete(uint32_t k, const std::string& expr) {
         if (counting_) return;
         const uint32_t pos = (uint32_t)order_.size();
@@ -183,13 +223,15 @@ private:
     }
     // scatter an adjoint: slots accumulate in their register; parameter-sourced uniform entries in theirs, leaving
     // through the transpose tile at their last contribution; constants and observed data take none
-    void add_adj(uint32_t o, uint32_t e, const std::string& expr) {
+    // (unfused: expr stands for expr * 1.0f — the add must not fuse with the multiply that produced it)
+    void add_adj(uint32_t o, uint32_t e, const std::string& expr, bool unfused = false) {
         const Opnd p = resolve(o, e);
-        if (p.lane) { line(fmt("a_%u += %s;", p.idx, expr.c_str())); return; }
+        const char* const form = unfused ? "%s_%u = spec_plus(%s_%u, %s);" : "%s_%u += %s;";
+        if (p.lane) { line(unfused ? fmt(form, "a", p.idx, "a", p.idx, expr.c_str()) : fmt(form, "a", p.idx, expr.c_str())); return; }
         if (p.idx >= d_.n_uniform_grad) return;
         if (counting_) { ++du_total_[p.idx]; return; }
         if (direct_du_) { complete(p.idx, expr); return; }
-        line(fmt("du_%u += %s;", p.idx, expr.c_str()));
+        line(unfused ? fmt(form, "du", p.idx, "du", p.idx, expr.c_str()) : fmt(form, "du", p.idx, expr.c_str()));
         if (++du_seen_[p.idx] == du_total_[p.idx]) complete(p.idx, fmt("du_%u", p.idx));
     }
 
@@ -249,13 +291,13 @@ private:
             ++visits_;
             if (counting_) return;
             line("{");
-            line(fmt("  const float loc = %s * %s + %s;", val(I.a, e).c_str(), val(I.b, e).c_str(), val(I.c, e).c_str()));
+            line(fmt("  const float loc = %s;", affine(I.a, I.b, I.c, e).c_str()));
             std::string v = val(I.dst, e);
             if (flags & BSVI_F_SAMPLE) {
                 const uint32_t row = resolve(I.dst, e).idx;
                 const std::string eps = eps_forward(row);
                 if (flags & BSVI_F_GIVEN) line(fmt("  %s = %s;", v.c_str(), eps.c_str()));
-                else line(fmt("  %s = loc + %s * %s;", v.c_str(), eps.c_str(), val(I.s, e).c_str()));
+                else { line(fmt("  %s = loc + %s * %s;", v.c_str(), eps.c_str(), val(I.s, e).c_str())); sum_defined_.insert(row); }
                 diag_outputs(row, v, eps);
             }
             if (flags & (BSVI_F_ENT | BSVI_F_LOGP | BSVI_F_WF)) line(fmt("  const float lS = %s;", log_of(I.s, e).c_str()));
@@ -323,21 +365,21 @@ private:
     // ---- a model log-prob term N(value | A*B + C, S) finished in the forward sweep (elbo_kernel.hip naff_sink)
     void naff_sink(const Insn& I, uint32_t e) {
         ++visits_;
-        const std::string A = val(I.a, e), B = val(I.b, e);
+        const std::string loc = affine(I.a, I.b, I.c, e);
         if (sink_mode_ == 1) {      // the value alone
-            line(fmt("T.f += %s * spec_naff_lp(%s, %s * %s + %s, %s, %s);", flit(I.imm0).c_str(), val(I.dst, e).c_str(), A.c_str(), B.c_str(),
-                     val(I.c, e).c_str(), rcp_of(I.s, e).c_str(), log_of(I.s, e).c_str()));
+            line(fmt("T.f += %s * spec_naff_lp(%s, %s, %s, %s);", flit(I.imm0).c_str(), val(I.dst, e).c_str(), loc.c_str(),
+                     rcp_of(I.s, e).c_str(), log_of(I.s, e).c_str()));
             return;
         }
         if (!counting_) {
             line("{");
-            line(fmt("  float gl, gs; spec_naff_sink(%s, %s, %s * %s + %s, %s, %s, %s, gl, gs);", flit(I.imm0).c_str(), val(I.dst, e).c_str(),
-                     A.c_str(), B.c_str(), val(I.c, e).c_str(), rcp_of(I.s, e).c_str(), log_of(I.s, e).c_str(), ftarget()));
+            line(fmt("  float gl, gs; spec_naff_sink(%s, %s, %s, %s, %s, %s, gl, gs);", flit(I.imm0).c_str(), val(I.dst, e).c_str(),
+                     loc.c_str(), rcp_of(I.s, e).c_str(), log_of(I.s, e).c_str(), ftarget()));
             if (diag_) line("  gl *= T.gw; gs *= T.gw;");
         }
         add_adj(I.dst, e, "-gl");
-        add_adj(I.a, e, "gl * " + B);
-        add_adj(I.b, e, "gl * " + A);
+        add_adj_times(I.a, e, "gl", I.b);
+        add_adj_times(I.b, e, "gl", I.a);
         add_adj(I.c, e, "gl");
         add_adj(I.s, e, "gs");
         line("}");
@@ -348,10 +390,10 @@ private:
         const uint32_t op = I.w0 & 0xFFu, flags = (I.w0 >> 8) & 0xFFu, dist = (I.w0 >> 16) & 0xFFu;
         ++visits_;
         if (op == BSVI_OP_NAFF) {
-            const std::string A = val(I.a, e), B = val(I.b, e), v = val(I.dst, e);
+            const std::string v = val(I.dst, e);
             if (!counting_) {
                 line("{");
-                line(fmt("  const float rS = %s, loc = %s * %s + %s;", rcp_of(I.s, e).c_str(), A.c_str(), B.c_str(), val(I.c, e).c_str()));
+                line(fmt("  const float rS = %s, loc = %s;", rcp_of(I.s, e).c_str(), affine(I.a, I.b, I.c, e).c_str()));
                 line("  float gv = 0.0f, gl = 0.0f, gs = 0.0f;");
                 if (flags & (BSVI_F_LOGP | BSVI_F_WF)) {
                     const std::string gw = (flags & BSVI_F_WF) ? fmt("(%s + fweight)", wg(I.imm0).c_str()) : wg(I.imm0);
@@ -371,8 +413,8 @@ private:
             } else {
                 add_adj(I.dst, e, "gv");
             }
-            add_adj(I.a, e, "gl * " + B);
-            add_adj(I.b, e, "gl * " + A);
+            add_adj_times(I.a, e, "gl", I.b);
+            add_adj_times(I.b, e, "gl", I.a);
             add_adj(I.c, e, "gl");
             add_adj(I.s, e, "gs");
             line("}");
@@ -619,9 +661,10 @@ struct Spec {
     uint32_t n_pos = 0;                                   // positions of the transpose tile (>= n_ugrad)
     Geom geom[2];
     std::vector<uint32_t> pu_ptr_host, pu_pos_host, pu_idx_host;   // CSR theta -> (position, uniform entry)
-    Variant variant[7];                                   // [geometry][0 lean, 1 diagnostic]; 4: lean one-workgroup kernel with the draw wave;
+    Variant variant[8];                                   // [geometry][0 lean, 1 diagnostic]; 4: lean one-workgroup kernel with the draw wave;
                                                           // 5: the same with the cross-rank exchange inside the training loop (spec_main.h);
-                                                          // 6: 4 with the owners' epilogue on a draw wave of the draw service
+                                                          // 6: 4 with the owners' epilogue on a draw wave of the draw service;
+                                                          // 7: 6 as it was before the lean chain (BSVI_SPEC_LEAN_CHAIN=0: comparisons)
     bool exchange_ok = false;                             // every parameter has its owner in one wave: the in-loop exchange serves
     void* dev = nullptr;                                  // [tickets: 256 B][pu_ptr][pu_pos][pu_idx]
     unsigned int* tickets = nullptr;
@@ -693,10 +736,23 @@ Spec* create(const bsvi_program_desc& d, std::string& why) {
     uint32_t ut_mask = 0;                  // the transforms the program's uniform table uses
     for (uint32_t k = 0; k < d.n_uniform; ++k) ut_mask |= 1u << (d.uniform[k].transform & 31u);
     const bool rare_transforms = (ut_mask >> (BSVI_UT_SIGMOID + 1)) != 0;
+    // the most table entries any parameter owns: the owners' code is compiled for that many (spec_main.h, SPEC_OWN_ENTRIES)
+    uint32_t own_entries = 1;
+    for (uint32_t i = 0; i < d.n_params; ++i) own_entries = std::max(own_entries, std::min(2u, s->pu_ptr_host[i + 1] - s->pu_ptr_host[i]));
+    // The lean body (literal constants folded) is what every variant gets; BSVI_SPEC_LEAN_BODY=0, read when the program is
+    // created, generates the body as it was (measurements).
+    const char* const lean_env = getenv("BSVI_SPEC_LEAN_BODY");
+    const bool lean_body = !(lean_env && lean_env[0] == '0');
+    // The lean one-workgroup source as it was before the lean chain (variant 7) exists for comparisons only: it is generated
+    // when BSVI_SPEC_LEAN_CHAIN is set, to either value, while the program is created — nobody else pays the third pass.
+    const bool want_previous = getenv("BSVI_SPEC_LEAN_CHAIN") != nullptr;
+    std::string previous;
     for (int gi = 0; gi < 2; ++gi) {
         const Geom& G = s->geom[gi];
-        for (int v = 0; v < 2; ++v) {
-            Emitter E(d, v == 1);
+        for (int v = 0; v < (gi == GEOM_ONE && want_previous ? 3 : 2); ++v) {
+            const bool old = v == 2;       // (v == 2: variant 0 once more, in its previous form)
+            const bool lean = lean_body && !old;
+            Emitter E(d, v == 1, lean);
             if (!E.run(why)) { delete s; return nullptr; }
             std::string src;
             src += "// generated by libbsvi (specialize.cpp) from a model program: do not edit\n";
@@ -722,7 +778,7 @@ Spec* create(const bsvi_program_desc& d, std::string& why) {
             src += fmt("#define SPEC_N_PARAMS %u\n#define SPEC_N_UNIFORM %u\n#define SPEC_N_UGRAD %u\n#define SPEC_N_OBS %u\n#define SPEC_N_NOISE %u\n",
                        d.n_params, d.n_uniform, d.n_uniform_grad, d.n_obs, d.n_noise);
             src += fmt("#define SPEC_N_POS %u\n", s->n_pos);
-            src += fmt("#define SPEC_ESTIMATOR %u\n#define SPEC_MAX_THREADS %u\n#define SPEC_DIAG %d\n", d.estimator, G.max_threads, v);
+            src += fmt("#define SPEC_ESTIMATOR %u\n#define SPEC_MAX_THREADS %u\n#define SPEC_DIAG %d\n", d.estimator, G.max_threads, v == 1 ? 1 : 0);
             src += fmt("#define SPEC_ACCUMULATE_CHUNKS %d\n#define SPEC_TILE %d\n", gi == GEOM_MANY ? 1 : 0, tiled(s->n_pos, gi) ? 1 : 0);
             if (gi == GEOM_MANY && many_waves() > 2) src += fmt("#define SPEC_BOUND_THREADS %u\n", 256u * many_waves());
             src += fmt("#define SPEC_KEEP_NOISE %u\n", E.keeps_noise() ? d.n_noise : 0u);
@@ -730,6 +786,7 @@ Spec* create(const bsvi_program_desc& d, std::string& why) {
             src += fmt("#define SPEC_GENERIC_OWNERS %d\n", all_fast ? 0 : 1);
             // (the out-of-line transforms — exp, log, tanh, sqrt, square — are calls: programs without them compile none)
             src += fmt("#define SPEC_RARE_TRANSFORMS %d\n#define SPEC_UT_MASK 0x%xu\n", rare_transforms ? 1 : 0, ut_mask);
+            if (!old) src += fmt("#define SPEC_OWN_ENTRIES %u\n", own_entries);
             src += "#include \"spec_prelude.h\"\n";
             src += "namespace bsvi {\n";
             src += "__device__ __forceinline__ void spec_draw(const SpecBody& A, const SpecLane& T, SpecNoise& Z) {\n";
@@ -739,6 +796,7 @@ Spec* create(const bsvi_program_desc& d, std::string& why) {
             src += "__device__ __forceinline__ void spec_body(const SpecBody& A, SpecLane& T, const SpecNoise& Z, float* WSw) {\n";
             src += "    (void)Z;\n";
             if (v == 1) src += "    const float* const noise = A.noise;\n";
+            if (old) { previous = std::move(src); previous += E.declarations() + E.body() + "}\n}  // namespace bsvi\n#include \"spec_main.h\"\n"; continue; }
             src += E.declarations();
             src += E.body();
             src += "}\n}  // namespace bsvi\n";
@@ -748,7 +806,8 @@ Spec* create(const bsvi_program_desc& d, std::string& why) {
     }
     // (a kernel of its own: the extra roles cost the plain loop 3 % when they are merely compiled in)
     s->variant[4].src = "#define SPEC_WITH_DRAW_WAVE 1\n" + s->variant[0].src;
-    s->variant[6].src = "#define SPEC_WITH_DRAW_WAVE 1\n#define SPEC_WITH_DRAW_OWNERS 1\n" + s->variant[0].src;
+    s->variant[6].src = "#define SPEC_WITH_DRAW_WAVE 1\n#define SPEC_WITH_DRAW_OWNERS 1\n#define SPEC_LEAN_CHAIN 1\n" + s->variant[0].src;
+    if (want_previous) s->variant[7].src = "#define SPEC_WITH_DRAW_WAVE 1\n#define SPEC_WITH_DRAW_OWNERS 1\n" + previous;
     s->exchange_ok = true;       // (owners in one wave: the wave exchanges; otherwise every thread exchanges its own parameters' entries)
     s->variant[5].src = std::string("#define SPEC_WITH_EXCHANGE 1\n") + (s->draw_wave_ok ? "#define SPEC_WITH_DRAW_WAVE 1\n" : "") + s->variant[0].src;
     return s;
@@ -784,7 +843,7 @@ int upload(Spec* s) {
 }
 
 // variant: 0 training kernel, 1 diagnostic kernel of the one-workgroup geometry; 2, 3 the same of the many-workgroup one
-const std::string& source(const Spec* s, int variant) { return s->variant[(variant >= 4 && variant <= 6) ? variant : (variant & 3)].src; }
+const std::string& source(const Spec* s, int variant) { return s->variant[(variant >= 4 && variant <= 7) ? variant : (variant & 3)].src; }
 
 // ---------------------------------------------------------------------------------------------------------------
 //  hiprtc
@@ -985,6 +1044,7 @@ static void store(const std::string& key, const std::vector<char>& code) {
 
 // what the last ensure_compiled of this thread did (bsvi_jit_cache_stats): tests and tools read it
 static thread_local int t_last_source = 0;      // 0 none yet, 1 hiprtc, 2 process cache, 3 disk cache
+static thread_local int t_last_variant = -1;    // the kernel variant of this thread's last launch (bsvi_spec_last_variant): tests read it
 
 // the code object of a translation unit: this process's cache, the disk cache, or hiprtc (and then both caches)
 int obtain(const std::string& text, std::vector<char>& code, std::string& log, int* origin) {
@@ -1018,6 +1078,7 @@ int obtain(const std::string& text, std::vector<char>& code, std::string& log, i
 }
 
 int last_origin() { return t_last_source; }
+int last_variant() { return t_last_variant; }
 std::string cache_directory() { return disk_cache::enabled() ? disk_cache::directory() : std::string(); }
 std::string compiler_identity() { return disk_cache::compiler_identity(); }
 
@@ -1061,6 +1122,12 @@ static bool owner_wave() {
     const char* e = getenv("BSVI_SPEC_OWNER_WAVE");       // (read per call: the tests switch it within a process)
     return !(e && e[0] == '0');
 }
+// The owners' wave with the lean chain (spec_main.h, SPEC_LEAN_CHAIN) and the lean body; BSVI_SPEC_LEAN_CHAIN=0: the kernel as it
+// was before both — same draws, same arithmetic, same bits (its source exists when the variable was set at the program's creation)
+static bool lean_chain() {
+    const char* e = getenv("BSVI_SPEC_LEAN_CHAIN");       // (read per call: the tests switch it within a process)
+    return !(e && e[0] == '0');
+}
 static Geo geo(const Spec* s, uint32_t n_local, int mode = MODE_SUMS, bool exchange = false) {
     const uint32_t waves = (n_local + 63) / 64;
     if (waves <= s->geom[GEOM_ONE].max_threads / 64) {
@@ -1076,7 +1143,9 @@ static Geo geo(const Spec* s, uint32_t n_local, int mode = MODE_SUMS, bool excha
                              && !s->variant[exchange ? 5 : 4].failed;
         const uint32_t more = service ? n_service : extra ? 1u : 0u;
         // (the owners on a draw wave: one more buffer, for the set the owners' wave draws — spec_main.h, SPEC_DRAW_OWNERS)
-        const bool owners = service && (size_t)s->n_noise * 64u * (waves + 1u) <= (size_t)n_service * 64u * 68u;
+        // (and a full workgroup: the lean epilogue adds the rows of all waves the kernel is compiled for)
+        const bool owners = service && (size_t)s->n_noise * 64u * (waves + 1u) <= (size_t)n_service * 64u * 68u
+                            && waves + n_service == s->geom[GEOM_ONE].max_threads / 64;
         return Geo{1, (waves + more) * 64, GEOM_ONE, more != 0u, more, owners};
     }
     // many samples: 256-thread workgroups (one wave per SIMD), two per CU at most; beyond that every workgroup walks
@@ -1135,9 +1204,11 @@ int launch(Spec* s, const bsvi_program* p, const Launch& L) {
             v = 5;
         }
         else if (g.draw_owners && v == 0 && owner_wave()) {
-            const int rc6 = ensure_compiled(s, 6);
+            v = lean_chain() ? 6 : 7;
+            if (v == 7 && s->variant[7].src.empty())
+                return bsvi_fail(BSVI_ERR_UNSUPPORTED, "BSVI_SPEC_LEAN_CHAIN=0 needs the variable set when the program is created (the previous source is generated then)");
+            const int rc6 = ensure_compiled(s, v);
             if (rc6) return rc6;
-            v = 6;
         }
         else if (g.draw_wave && v == 0 && ensure_compiled(s, 4) == BSVI_OK) v = 4;
         else if (g.draw_wave) { g.threads -= 64 * g.extra_waves; g.draw_wave = false; }        // (diagnostic kernel, or the variant did not compile)
@@ -1191,6 +1262,7 @@ int launch(Spec* s, const bsvi_program* p, const Launch& L) {
     void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &A, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
     const hipError_t e = hipModuleLaunchKernel(s->variant[v].fn, g.blocks, 1, 1, g.threads, 1, 1, 0, (hipStream_t)a->stream, nullptr, config);
     if (e != hipSuccess) return bsvi_fail(BSVI_ERR_HIP, std::string("hipModuleLaunchKernel (specialised kernel): ") + hipGetErrorString(e));
+    t_last_variant = v;
     return BSVI_OK;
 }
 

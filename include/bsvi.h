@@ -413,6 +413,8 @@ size_t bsvi_program_source(const bsvi_program_desc* desc, int variant, char* buf
 int bsvi_jit_compile(const char* source, size_t* code_bytes);
 int bsvi_jit_load(const char* source, size_t* code_bytes, int* origin);
 int bsvi_jit_last_origin(void);
+/* the kernel variant of this thread's last launch of a specialised kernel (specialize.cpp, Spec::variant; -1: none yet): tests */
+int bsvi_spec_last_variant(void);
 size_t bsvi_jit_cache_dir(char* buf, size_t capacity);
 size_t bsvi_jit_compiler_identity(char* buf, size_t capacity);
 int bsvi_program_engine(const bsvi_program* prog, uint32_t n_local, int mode, uint32_t* n_blocks, uint32_t* n_threads,

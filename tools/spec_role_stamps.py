@@ -1,16 +1,18 @@
 """Per-ROLE time stamps of one iteration of the specialised kernel's training loop (diagnostic build: BSVI_SPEC_DEFINES adds
 SPEC_DEBUG_STAMPS; every wave's lane 0 writes its stamps into the loss curve at 16 + 8 * wave).  Cycles of s_memtime after the
 wave leaves the iteration's first barrier (the barrier releases all waves together): at the second barrier, past it, the
-owners' sums read (owners only), the iteration's work done, past the next first barrier.  Roles at the draw service's five
+owners' sums read (owners only), their new table published (lean chain: what follows is the loss bookkeeping), the
+iteration's work done, past the next first barrier.  Roles at the draw service's five
 sample waves: 0-4 sample waves (the owners on wave 1 with BSVI_SPEC_OWNER_WAVE=0), 5-7 draw waves (the owners on wave 5
 by default).  B = first barrier -> second (bodies, sums, draws beside them), E = second -> next first (epilogue).
 
-usage: python3 tools/spec_role_stamps.py [n_samples] [optimizer]"""
+usage: python3 tools/spec_role_stamps.py [n_samples] [optimizer] [define ...]"""
 import os
 import sys
 import time
 
-os.environ["BSVI_SPEC_DEFINES"] = "#define SPEC_DEBUG_STAMPS 1"
+# (further arguments are defines for the diagnostic build, e.g. SPEC_DEBUG_NO_LEAN_CHAIN: the lean body with the previous epilogue)
+os.environ["BSVI_SPEC_DEFINES"] = "\n".join(["#define SPEC_DEBUG_STAMPS 1"] + ["#define %s 1" % d for d in sys.argv[3:]])
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch                                        # noqa: E402
 from brancher_amd import engine, workloads as W     # noqa: E402
@@ -21,7 +23,9 @@ kw = dict(lr=1e-3) if optimizer == "SGD" else dict(lr=1e-2)
 api = W.native_api()
 c = engine.compile_model(W.build_readme_ar(api, T=20), None, "pathwise")
 n_it = 20000
-print("BSVI_SPEC_OWNER_WAVE=%s, %d samples, %s" % (os.environ.get("BSVI_SPEC_OWNER_WAVE", "1"), n_samples, optimizer))
+print("BSVI_SPEC_OWNER_WAVE=%s BSVI_SPEC_LEAN_CHAIN=%s BSVI_SPEC_LEAN_BODY=%s, %d samples, %s"
+      % (os.environ.get("BSVI_SPEC_OWNER_WAVE", "1"), os.environ.get("BSVI_SPEC_LEAN_CHAIN", "1"),
+         os.environ.get("BSVI_SPEC_LEAN_BODY", "1"), n_samples, optimizer) + "".join(" " + d for d in sys.argv[3:]))
 for rep in range(3):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -31,11 +35,12 @@ for rep in range(3):
     s = losses[:16 + 8 * 8].cpu().numpy()
     rows = []
     for w in range(8):
-        r = s[16 + 8 * w: 16 + 8 * w + 6]
+        r = s[16 + 8 * w: 16 + 8 * w + 7]
         if r[0] != 1.0:
             continue
-        at2, past2, sums, done, next1 = r[1:6]
-        rows.append("  wave %d: B %6d | E work %6d (sums read %6s) | wait %6d | iteration %6d"
-                    % (w, at2, done - past2, "%d" % (sums - past2) if 0 < sums < 1e8 else "-", next1 - done, next1))
+        at2, past2, sums, done, next1, table = r[1:7]
+        rows.append("  wave %d: B %6d | E work %6d (sums read %6s, table published %6s) | wait %6d | iteration %6d"
+                    % (w, at2, done - past2, "%d" % (sums - past2) if 0 < sums < 1e8 else "-",
+                       "%d" % (table - past2) if 0 < table < 1e8 else "-", next1 - done, next1))
     print("wall %.3f us/it" % (wall * 1e6 / n_it))
     print("\n".join(rows))
