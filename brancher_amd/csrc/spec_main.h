@@ -293,6 +293,9 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
     const bool step = mode != SPEC_MODE_SUMS;
     const uint32_t n_it = (mode == SPEC_MODE_LOOP) ? SPEC_A->n_iterations : 1u;
 
+#if defined(SPEC_DEBUG_STAMPS)
+    const unsigned long long stamp_entry = __builtin_amdgcn_s_memtime();
+#endif
     // ---- once per launch: tables, observed data, theta and the optimizer state into LDS; the uniform table
     {
         const uint32_t* uniform = reinterpret_cast<const uint32_t*>(SPEC_A->uniform);
@@ -429,6 +432,25 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
 #else
 #define SPEC_LEAN_OWNERS 0
 #endif
+// The tail of the lean chain (SPEC_LEAN_TAIL, a define of the generated source): two arrangements of the lean owners' loop,
+// each with a switch of its own for measurements (BSVI_SPEC_DEFINES)
+//   SPEC_DEFER_BOOK    what follows the table store — the loss division, the curve and flag stores — waits in two registers
+//                      and is done beside the NEXT iteration's bodies; the launch's last iteration does it at once
+//   SPEC_PLAIN_SGD     SGD without momentum, weight decay or maximize (launch-uniform, decided beside the bodies) is one
+//                      multiply-add on theta and the step count: its own scalar branch, not optimizer_apply's dispatch
+#if SPEC_LEAN_OWNERS && defined(SPEC_LEAN_TAIL) && !defined(SPEC_DEBUG_NO_DEFER_BOOK)
+#define SPEC_DEFER_BOOK 1
+#else
+#define SPEC_DEFER_BOOK 0
+#endif
+#if SPEC_LEAN_OWNERS && defined(SPEC_LEAN_TAIL) && !defined(SPEC_DEBUG_NO_PLAIN_SGD)
+#define SPEC_PLAIN_SGD 1
+#else
+#define SPEC_PLAIN_SGD 0
+#endif
+#if defined(SPEC_TAIL_MUST_BE_OFF) && (SPEC_DEFER_BOOK || SPEC_PLAIN_SGD)
+#error "the tail's arrangements are compiled into a kernel that keeps the previous epilogue"
+#endif
 #if SPEC_DRAW_OWNERS
     const uint32_t own_base = own_wave * 64u;
 #else
@@ -531,11 +553,13 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
     // (6: the owners' new table published — lean chain: what is left behind it is bookkeeping)
     unsigned long long rstamp[7] = {0, 0, 0, 0, 0, 0, 0};
 #define SPEC_RSTAMP(i) if (it == n_it / 2) rstamp[i] = __builtin_amdgcn_s_memtime()
-#define SPEC_RSTAMP_NEXT() if (it == n_it / 2 + 1u) rstamp[5] = __builtin_amdgcn_s_memtime()
+#define SPEC_RSTAMP_NEXT() if (it == n_it / 2 + 1u) rstamp[5] = __builtin_amdgcn_s_memtime(); else if (it == 0u) stamp_first = __builtin_amdgcn_s_memtime()
+    unsigned long long stamp_first = 0;     // (7: the launch's first barrier passed, counted from the kernel's entry)
 #define SPEC_RSTAMP_WRITE()                                                                                              \
     if (lane == 0u && SPEC_A->loss_slot && n_it > 16u + 8u * SPEC_MAX_WAVES) {                                           \
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                                 \
         for (int i = 1; i < 7; ++i) SPEC_A->loss_slot[16u + 8u * wave + i] = rstamp[i] ? (float)(rstamp[i] - rstamp[0]) : 0.0f; \
+        SPEC_A->loss_slot[16u + 8u * wave + 7] = (float)(stamp_first - stamp_entry);                                     \
         SPEC_A->loss_slot[16u + 8u * wave] = 1.0f;                                                                       \
     }
 #else
@@ -598,6 +622,9 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
         // (the lean epilogue adds the rows of all SPEC_MAX_WAVES waves: the host launches the service with a full workgroup only)
         if (W != SPEC_MAX_WAVES) __builtin_trap();
 #endif
+#if SPEC_DEFER_BOOK
+        float book_vs = 0.0f, book_finite = 0.0f;             // the last iteration's loss sum and flag, until they are written
+#endif
         for (uint32_t it = 0; it < n_it; ++it) {
             const bool more = it + 1u < n_it, last = !more;
             spec_lds_barrier();                                // (the main loop's first barrier: the sample waves read their buffers behind it)
@@ -633,6 +660,9 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
             typedef SPEC_GLOBAL_AS float* spec_gptr;
             spec_gptr e_out = nullptr, e_loss = nullptr, e_finite = nullptr, e_params = nullptr, e_state = nullptr;
             bsvi_opt_cfg e_cfg = {};
+#if SPEC_PLAIN_SGD
+            bool plain_sgd = false;
+#endif
             if (owners) {
                 SPEC_RELOAD_ARGS();
                 e_out = (spec_gptr)SPEC_A->out; e_loss = (spec_gptr)SPEC_A->loss_slot; e_finite = (spec_gptr)SPEC_A->finite_slot;
@@ -642,6 +672,18 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
                 asm volatile("" : "+s"(e_out), "+s"(e_loss), "+s"(e_finite), "+s"(e_params), "+s"(e_state));
                 asm volatile("" : "+s"(e_cfg.kind), "+s"(e_cfg.lr), "+s"(e_cfg.momentum), "+s"(e_cfg.dampening), "+s"(e_cfg.weight_decay),
                              "+s"(e_cfg.nesterov), "+s"(e_cfg.beta1), "+s"(e_cfg.beta2), "+s"(e_cfg.eps), "+s"(e_cfg.amsgrad), "+s"(e_cfg.maximize));
+#endif
+#if SPEC_PLAIN_SGD
+                plain_sgd = __builtin_amdgcn_readfirstlane((e_cfg.kind == BSVI_OPT_SGD && e_cfg.momentum == 0.0f && e_cfg.weight_decay == 0.0f
+                                                            && !e_cfg.maximize) ? 1 : 0) != 0;
+#endif
+#if SPEC_DEFER_BOOK
+                // ---- the bookkeeping of the iteration before, beside this one's bodies (the pointers have just arrived)
+                if (it > 0u && oid == 0u) {
+                    const float loss = -book_vs / (float)n_global;
+                    if (e_loss) e_loss[it - 1u] = loss;
+                    if (e_finite) e_finite[it - 1u] = book_finite;
+                }
 #endif
             }
 #endif
@@ -683,6 +725,14 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
                     gsum += own.n > 0u ? term : 0.0f;
                     grad = gsum * own_scale;
                     SPEC_RSTAMP(3);
+#if SPEC_PLAIN_SGD
+                    if (plain_sgd) {                           // (optimizer_apply's SGD branch with its options off)
+                        if (finite != 0.0f && (own.mask & mask_bit)) {
+                            own.st = own.st + 1.0f;
+                            own.theta = own.theta - e_cfg.lr * grad;
+                        }
+                    } else
+#endif
                     if (finite != 0.0f && (own.mask & mask_bit)) {
                         if (e_cfg.kind == BSVI_OPT_SGD) {
                             optimizer_apply(e_cfg, own.theta, own.s0, own.s1, own.s2, own.st, grad);
@@ -700,6 +750,10 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
                 asm volatile("" ::: "memory");                 // (the table's stores stay in front of the bookkeeping's)
                 SPEC_RSTAMP(6);
                 // ---- behind the table: the loss (a full-precision division), the curve, the launch's output block
+#if SPEC_DEFER_BOOK
+                book_vs = vs; book_finite = finite;
+                if (more) { SPEC_RSTAMP(4); continue; }        // (written beside the next bodies, above)
+#endif
                 const float loss = -vs / (float)n_global;
                 if (oid == 0u) {
                     const float vb = spec_rows_total(rb);

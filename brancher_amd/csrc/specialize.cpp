@@ -747,6 +747,11 @@ Spec* create(const bsvi_program_desc& d, std::string& why) {
     // when BSVI_SPEC_LEAN_CHAIN is set, to either value, while the program is created — nobody else pays the third pass.
     const bool want_previous = getenv("BSVI_SPEC_LEAN_CHAIN") != nullptr;
     std::string previous;
+    // The tail of the owners' chain (variant 6 only; spec_main.h SPEC_LEAN_TAIL): the loss bookkeeping beside the next bodies,
+    // plain SGD as a step of its own.  BSVI_SPEC_TAIL=0, read when the program is created, generates variant 6 as it was
+    // (comparisons).
+    const char* const tail_env = getenv("BSVI_SPEC_TAIL");
+    const bool tail = !(tail_env && tail_env[0] == '0');
     for (int gi = 0; gi < 2; ++gi) {
         const Geom& G = s->geom[gi];
         for (int v = 0; v < (gi == GEOM_ONE && want_previous ? 3 : 2); ++v) {
@@ -806,7 +811,8 @@ Spec* create(const bsvi_program_desc& d, std::string& why) {
     }
     // (a kernel of its own: the extra roles cost the plain loop 3 % when they are merely compiled in)
     s->variant[4].src = "#define SPEC_WITH_DRAW_WAVE 1\n" + s->variant[0].src;
-    s->variant[6].src = "#define SPEC_WITH_DRAW_WAVE 1\n#define SPEC_WITH_DRAW_OWNERS 1\n#define SPEC_LEAN_CHAIN 1\n" + s->variant[0].src;
+    s->variant[6].src = std::string("#define SPEC_WITH_DRAW_WAVE 1\n#define SPEC_WITH_DRAW_OWNERS 1\n#define SPEC_LEAN_CHAIN 1\n")
+                        + (tail ? "#define SPEC_LEAN_TAIL 1\n" : "") + s->variant[0].src;
     if (want_previous) s->variant[7].src = "#define SPEC_WITH_DRAW_WAVE 1\n#define SPEC_WITH_DRAW_OWNERS 1\n" + previous;
     s->exchange_ok = true;       // (owners in one wave: the wave exchanges; otherwise every thread exchanges its own parameters' entries)
     s->variant[5].src = std::string("#define SPEC_WITH_EXCHANGE 1\n") + (s->draw_wave_ok ? "#define SPEC_WITH_DRAW_WAVE 1\n" : "") + s->variant[0].src;
