@@ -71,12 +71,24 @@ __device__ __forceinline__ u32x4 philox_raw(const PhiloxKey& k, uint32_t row, ui
 // Box-Muller on the hardware transcendental units: v_sin/v_cos take revolutions, so
 // sin(2*pi*u) is one instruction and needs no range reduction
 __device__ __forceinline__ void box_muller_fast(uint32_t a, uint32_t b, float& z0, float& z1) {
-    // u01 is a normal float in (0, 1): v_log_f32 (log2) and v_sqrt_f32 need no denormal or range handling — the
+    // u01 is a normal float in (0, 1] (philox.h; log2(1) = 0, r = 0): v_log_f32 (log2) and v_sqrt_f32 need no denormal or range handling — the
     // library logf / sqrtf spend ~20 instructions per pair on exactly that
     const float r = __builtin_amdgcn_sqrtf(__builtin_amdgcn_logf(u01(a)) * -1.3862943611198906f);     // sqrt(-2 ln u)
     const float u = u01(b);
     z0 = r * __builtin_amdgcn_cosf(u);
     z1 = r * __builtin_amdgcn_sinf(u);
+}
+// Base noise of the uniform-based reparameterised draws.  u01 reaches exactly 1.0f (philox.h), where the plain formulas leave
+// their range: the Laplace noise would be 1 (log1p(-1) = -inf: an infinite draw) and the Cauchy angle pi_f32 / 2 > pi / 2 (a
+// tangent of the wrong sign).  ONE definition each, used by the draw and by the reverse sweep's replay, so the two cannot disagree.
+// Laplace: torch laplace.py:83 draws from [eps - 1, 1) — clamp to the largest float below 1.
+__device__ __forceinline__ float laplace_noise(uint32_t x) {
+    return fminf((kFloatEps - 1.0f) + (2.0f - kFloatEps) * u01(x), 1.0f - 0.5f * kFloatEps);
+}
+// Cauchy: the angle stays inside (-pi/2, pi/2) — 1.57079625f is the largest float below pi / 2
+__device__ __forceinline__ float cauchy_noise(uint32_t x) {
+    constexpr float kBelowHalfPi = 1.57079625f;
+    return tanf(fminf(fmaxf(3.14159265358979323846f * (u01(x) - 0.5f), -kBelowHalfPi), kBelowHalfPi));
 }
 __device__ __noinline__ float philox_gamma(PhiloxKey G, float alpha, uint32_t row, uint32_t stream) {
     // Marsaglia & Tsang (2000), as ATen/native/Distributions.h sample_gamma
@@ -116,13 +128,13 @@ BSVI_SWITCH_FN float2 philox_draw(PhiloxKey G, int dist, float p0, float p1, uin
     }
     case BSVI_DIST_CAUCHY: {
         const u32x4 x = philox_raw(G, row, 0);
-        noise = tanf(3.14159265358979323846f * (u01(x.x) - 0.5f));
+        noise = cauchy_noise(x.x);
         v = p0 + noise * p1;
         break;
     }
     case BSVI_DIST_LAPLACE: {
         const u32x4 x = philox_raw(G, row, 0);
-        noise = (kFloatEps - 1.0f) + (2.0f - kFloatEps) * u01(x.x);   // torch laplace.py:83
+        noise = laplace_noise(x.x);
         v = sample_from_noise_generic(dist, p0, p1, noise);
         break;
     }
@@ -158,8 +170,8 @@ BSVI_SWITCH_FN float2 philox_draw(PhiloxKey G, int dist, float p0, float p1, uin
 BSVI_SWITCH_FN float philox_noise_again(PhiloxKey G, int dist, uint32_t row) {
     const u32x4 x = philox_raw(G, row, 0);
     if (dist == BSVI_DIST_LOGNORMAL) { float n0, n1; box_muller(x.x, x.y, n0, n1); return n0; }
-    if (dist == BSVI_DIST_CAUCHY) return tanf(3.14159265358979323846f * (u01(x.x) - 0.5f));
-    if (dist == BSVI_DIST_LAPLACE) return (kFloatEps - 1.0f) + (2.0f - kFloatEps) * u01(x.x);
+    if (dist == BSVI_DIST_CAUCHY) return cauchy_noise(x.x);
+    if (dist == BSVI_DIST_LAPLACE) return laplace_noise(x.x);
     return 0.0f;
 }
 

@@ -1413,6 +1413,25 @@ __global__ void debug_math_kernel(int fn, int dist, const float* x, const float*
     case 4: { r0 = entropy_generic(dist, a, b); const float2 r = entropy_bwd_generic(dist, a, b, 1.0f); r2 = r.x; r3 = r.y; break; }
     case 5: { r0 = sample_from_noise_generic(dist, a, b, xv); const float2 r = sample_bwd_generic(dist, r0, a, b, xv, 1.0f); r2 = r.x; r3 = r.y; break; }
     case 6: r0 = lgammaf(xv); break;
+    case 7: {
+        // raw Philox words: the buffers hold BIT PATTERNS, two planes of m = n / 2 words each — x = (c0 | c1), p0 = (c2 | c3),
+        // p1 = (k0 | k1); call i < m writes its four words (as bit patterns) to out[j][i]
+        const uint32_t m = n >> 1;
+        if (i < m) {
+            const uint32_t *xw = (const uint32_t*)x, *aw = (const uint32_t*)p0, *bw = (const uint32_t*)p1;
+            const u32x4 w = philox4x32(xw[i], xw[m + i], aw[i], aw[m + i], bw[i], bw[m + i]);
+            r0 = __uint_as_float(w.x); r1 = __uint_as_float(w.y); r2 = __uint_as_float(w.z); r3 = __uint_as_float(w.w);
+        }
+        break;
+    }
+    case 8: {
+        // the transforms of raw words a = bits of x[i], b = bits of p0[i]; `dist` selects the quadruple:
+        // 0: u01(a), box_muller(a, b), cauchy_noise(a);  1: laplace_noise(a), box_muller_fast(a, b), u01(b)
+        const uint32_t wa = __float_as_uint(xv), wb = __float_as_uint(a);
+        if (dist == 0) { r0 = u01(wa); box_muller(wa, wb, r1, r2); r3 = cauchy_noise(wa); }
+        else { r0 = laplace_noise(wa); box_muller_fast(wa, wb, r1, r2); r3 = u01(wb); }
+        break;
+    }
     default: break;
     }
     out[i] = r0; out[n + i] = r1; out[2 * (size_t)n + i] = r2; out[3 * (size_t)n + i] = r3;

@@ -37,7 +37,9 @@ __device__ __forceinline__ u32x4 philox4x32(uint32_t c0, uint32_t c1, uint32_t c
     return {c0, c1, c2, c3};
 }
 
-// (0,1) open interval, 24 random bits
+// 24 random bits on (0, 1] — NOT the open interval: for x >> 8 == 2^24 - 1 the sum rounds to 2^24 in single precision and the
+// result is exactly 1.0f (probability 2^-24 per word).  log(1) = 0 is fine for Box-Muller; a transform that cannot take 1 clamps
+// its own result (bsvi_device.h: laplace_noise, cauchy_noise).  The Normal streams depend on this rounding bit for bit.
 __device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 
 __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {

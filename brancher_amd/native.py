@@ -408,6 +408,9 @@ STRUCT_KINDS = {0: UniformEntry, 1: Record, 2: ProgramDesc, 3: ElboArgs, 4: OptC
                 8: AmortDesc, 9: AmortArgs, 10: MvnInsn, 11: MvnDesc, 12: MvnArgs, 13: BnnLayer, 14: BnnDesc, 15: BnnArgs,
                 16: ReduceDesc, 17: ReduceArgs}
 
+# bsvi_debug_math: the `fn` values of the noise stream (include/bsvi.h) — raw Philox words, transforms of raw words
+DEBUG_MATH_PHILOX_WORDS, DEBUG_MATH_NOISE_TRANSFORMS = 7, 8
+
 _lib = None
 
 

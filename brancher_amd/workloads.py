@@ -557,6 +557,22 @@ def build_discrete_latent(api, n_obs=8, seed=0):
     return model
 
 
+def build_cauchy_binomial_latents(api, n_obs=6, total=13, seed=0):
+    """Drawn Cauchy and Binomial latents (every other workload here only observes these two): a Cauchy location and a Binomial
+    count — 13 trials are three full blocks of four Philox words and one trial of a fourth — under a Normal likelihood.  The
+    Binomial has no reparameterisation: BlackBox estimator, like `build_discrete_latent`."""
+    rng = np.random.RandomState(seed)
+    k = api.BinomialVariable(total, probs=0.4, name="k")
+    c = api.CauchyVariable(0., 1., "c")
+    x = api.NormalVariable(c + k * 0.5, 0.7, "x")
+    model = api.ProbabilisticModel([x])
+    x.observe(rng.normal(1.5, 0.7, size=n_obs).astype(np.float32))
+    Qk = api.BinomialVariable(total, logits=0.3, name="k", learnable=True)
+    Qc = api.CauchyVariable(0.1, 1.2, "c", learnable=True)
+    model.set_posterior_model(api.ProbabilisticModel([Qk, Qc]))
+    return model
+
+
 def build_heavy_tails(api, n_obs=12, seed=1):
     """Cauchy / Laplace coverage (`examples/logNormal_normal.py` imports both): a Laplace
     location with Cauchy likelihood and an explicit nonlinear link."""

@@ -728,7 +728,13 @@ int bsvi_debug_gemm(int mode, const float* a_dev, const float* b_dev, float* c_d
 /* Test hook, not used by the product path: evaluates one special function (fn 0 digamma,
  * 1 trigamma, 2 dirichlet_grad_one(x, alpha=p0, total=p1), 6 lgamma) or one node function of
  * distribution `dist` (fn 3 log-prob, 4 entropy, 5 reparameterised draw from noise x) elementwise;
- * out_dev is [4][n] = value, d/dx, d/dp0, d/dp1. */
+ * out_dev is [4][n] = value, d/dx, d/dp0, d/dp1.
+ * The noise stream (the buffers carry 32-bit words as BIT PATTERNS):
+ *   fn 7: raw Philox4x32 words of m = n / 2 calls; x_dev = (c0[m] | c1[m]), p0_dev = (c2[m] | c3[m]), p1_dev = (k0[m] | k1[m]);
+ *         out_dev[j][i], i < m, is word j of call i.
+ *   fn 8: transforms of the raw words a = x[i], b = p0[i].  dist 0: u01(a), Box-Muller (a, b) with the library functions
+ *         (z0, z1), Cauchy base noise of a.  dist 1: Laplace base noise of a, Box-Muller (a, b) on the hardware
+ *         transcendental units (z0, z1), u01(b). */
 int bsvi_debug_math(int fn, int dist, const float* x_dev, const float* p0_dev, const float* p1_dev,
                     float* out_dev, uint32_t n, void* stream);
 
