@@ -88,8 +88,15 @@ struct Launch {
     float* finite_slot = nullptr;
     void* workspace = nullptr;      // the spec's region of the caller's workspace
     const void* xchg = nullptr;     // loop mode on several ranks: the device-resident descriptor of the exchange (SpecExchange), or null
+    const float* const* datasets = nullptr;   // loop mode with the gather phase: the datasets of the program's minibatch sources (host array), or null
 };
 int launch(Spec* s, const bsvi_program* p, const Launch& L);
+// Minibatched observations inside the training loop (bsvi_program_set_minibatches): n x {obs_offset, batch, row_floats,
+// dataset_size, group}.  Checks the geometry against the program's observation table and the gathering wave's registers,
+// and generates the loop variants with the gather phase; refused once a launch with the geometry was prepared.
+int set_minibatches(Spec* s, uint32_t n, const uint32_t* geometry);
+const std::string& source_minibatch(const Spec* s, int variant);
+uint32_t minibatch_sources(const Spec* s);
 // geometry of that launch (tests / bench)
 void geometry(const Spec* s, uint32_t n_local, int mode, uint32_t* n_blocks, uint32_t* n_threads, uint32_t* lds_bytes);
 

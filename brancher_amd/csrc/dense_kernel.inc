@@ -122,27 +122,11 @@ __device__ __forceinline__ float uniform_value(const DParams& D, uint32_t k) {
     return e.a + e.b * utransform(e.transform, x);
 }
 
-// minibatch row b: supplied, or a keyed bijection of [0, DS) (4-round Feistel on the next power of
-// four, cycle-walked) so that the B rows are distinct — sampling without replacement like
-// np.random.choice(replace=False) in distributions.py:438
+// minibatch row b: supplied, or the keyed bijection of [0, DS) of minibatch_index.h (the one definition: the generated
+// kernels' in-loop gather draws the same rows)
 __device__ __forceinline__ uint32_t minibatch_index(const DParams& D, uint32_t b) {
     if (D.indices_in) return (uint32_t)D.indices_in[b];
-    uint32_t half_bits = 1;
-    while ((1u << (2 * half_bits)) < D.DS) ++half_bits;
-    const uint32_t mask = (1u << half_bits) - 1u;
-    uint32_t x = b;
-    for (int walk = 0; walk < 64; ++walk) {
-        uint32_t lft = (x >> half_bits) & mask, rgt = x & mask;
-        for (uint32_t round = 0; round < 4; ++round) {
-            const u32x4 h = philox4x32(rgt, round, D.offset_lo, D.offset_hi, D.seed_lo ^ 0x5bd1e995u, D.seed_hi);
-            const uint32_t t = lft ^ (h.x & mask);
-            lft = rgt;
-            rgt = t;
-        }
-        x = (lft << half_bits) | rgt;
-        if (x < D.DS) return x;
-    }
-    return b % D.DS;
+    return minibatch_index_keyed(D.DS, D.seed_lo, D.seed_hi, D.offset_lo, D.offset_hi, b);
 }
 
 // LDS stores of staged fragments are built from the components (a HIP float4 object copied through a pointer cast can

@@ -2157,6 +2157,64 @@ extern "C" int bsvi_train_persistent_exchange(const bsvi_program* p, const bsvi_
     return bsvi_spec::launch(p->spec, p, L);
 }
 
+// ---- minibatched observations INSIDE the in-kernel training loop (standard_variables.py:71-112, distributions.py:393-473,
+//      inference.py:95-108): the program is told which stretches of its observation table are minibatches of which datasets,
+//      and the generated loop rewrites them in every iteration with the rows `bsvi_minibatch_gather` would fetch for
+//      (seed ^ group constant, offset + it) — spec_main.h, SPEC_MINIBATCH.  One launch instead of 1 + sources per iteration.
+extern "C" int bsvi_program_set_minibatches(bsvi_program* p, uint32_t n_sources, const uint32_t* geometry) {
+    if (!p || !geometry) return fail(BSVI_ERR_INVALID, "null argument");
+    if (!p->spec) return fail(BSVI_ERR_UNSUPPORTED, "the program is not specialised: its minibatches are gathered launch by launch (bsvi_minibatch_gather)");
+    if (n_sources && geometry && p->d.n_obs == 0) return fail(BSVI_ERR_INVALID, "the program has no observation table");
+    return bsvi_spec::set_minibatches(p->spec, n_sources, geometry);
+}
+
+extern "C" int bsvi_train_persistent_minibatch(const bsvi_program* p, const bsvi_elbo_args* a, const bsvi_opt_cfg* cfg,
+                                               float* params_dev, float* state_dev, const uint8_t* active_mask_dev,
+                                               const uint8_t* active_mask_first_dev, uint32_t pretraining_iterations,
+                                               uint32_t n_iterations, float* loss_curve_dev, float* finite_dev,
+                                               const float* const* datasets_dev) {
+    if (!p || !a || !datasets_dev) return fail(BSVI_ERR_INVALID, "null argument");
+    BSVI_CHECK_STRUCT(a, bsvi_elbo_args);
+    int rc = check_cfg(cfg);
+    if (rc) return rc;
+    if (!a->out_dev || !params_dev || !active_mask_dev || !active_mask_first_dev || !loss_curve_dev || !finite_dev)
+        return fail(BSVI_ERR_INVALID, "null argument");
+    if (a->offset_dev) return fail(BSVI_ERR_INVALID, "the in-kernel training loop counts its own iterations: offset_dev must be null");
+    if (a->noise_dev || a->samples_out_dev || a->noise_out_dev || a->fvalue_out_dev || a->f_weight_dev || a->q_weight_dev)
+        return fail(BSVI_ERR_UNSUPPORTED, "the in-kernel minibatch gather serves Philox noise without per-sample outputs");
+    if (!p->spec || g_debug_stamps || !bsvi_spec::applies(p->spec, a->n_samples_local, bsvi_spec::MODE_LOOP))
+        return fail(BSVI_ERR_UNSUPPORTED, "this shard's training loop does not run on the program-specialised kernels: gather launch by launch");
+    if (!bsvi_spec::minibatch_sources(p->spec))
+        return fail(BSVI_ERR_UNSUPPORTED, "the program carries no minibatch geometry (bsvi_program_set_minibatches)");
+    bsvi_spec::Launch L;
+    L.a = a; L.mode = bsvi_spec::MODE_LOOP; L.cfg = cfg; L.params = params_dev; L.state = state_dev; L.mask = active_mask_dev;
+    L.mask_first = active_mask_first_dev; L.pretraining_iterations = pretraining_iterations; L.n_iterations = n_iterations;
+    L.loss_slot = loss_curve_dev; L.finite_slot = finite_dev; L.workspace = spec_workspace(p, a); L.datasets = datasets_dev;
+    return bsvi_spec::launch(p->spec, p, L);
+}
+
+// host only: the generated source of loop variant `variant` (0, 2, 4, 6; 7 when it exists) with the gather phase for this geometry
+extern "C" size_t bsvi_program_source_minibatch(const bsvi_program_desc* desc, int variant, uint32_t n_sources, const uint32_t* geometry,
+                                                char* buf, size_t capacity) {
+    if (validate(desc) != BSVI_OK) return 0;
+    if (!geometry) { fail(BSVI_ERR_INVALID, "null argument"); return 0; }
+    std::string why;
+    bsvi_spec::Spec* sp = bsvi_spec::create(*desc, why);
+    if (!sp) { fail(BSVI_ERR_UNSUPPORTED, "program not specialised: " + why); return 0; }
+    size_t need = 0;
+    if (bsvi_spec::set_minibatches(sp, n_sources, geometry) == BSVI_OK) {
+        const std::string& src = bsvi_spec::source_minibatch(sp, variant);
+        if (src.empty()) {
+            fail(BSVI_ERR_INVALID, "variant " + std::to_string(variant) + " does not run the training loop");
+        } else {
+            need = src.size() + 1;
+            if (buf && capacity >= need) memcpy(buf, src.c_str(), need);
+        }
+    }
+    bsvi_spec::destroy(sp);
+    return need;
+}
+
 // Attach the shares of a program (programs created from lowering.Program.shares[n]: identical tables, own code) for the
 // multi-workgroup launches of bsvi_elbo_fwd_bwd / bsvi_svi_step.  The shares must outlive `p`'s use.
 extern "C" int bsvi_program_set_shares(bsvi_program* p, const bsvi_program* const* shares, uint32_t n_shares) {
@@ -2375,6 +2433,7 @@ extern "C" int bsvi_debug_math(int fn, int dist, const float* x_dev, const float
     return BSVI_OK;
 }
 
+#include "minibatch_index.h"
 #include "dense_kernel.inc"
 #include "bnn_kernel.inc"
 

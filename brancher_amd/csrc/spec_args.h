@@ -9,6 +9,7 @@
 namespace bsvi {
 
 enum { SPEC_MODE_SUMS = 0, SPEC_MODE_STEP = 1, SPEC_MODE_LOOP = 2 };
+enum { SPEC_MB_MAX_SOURCES = 8 };
 
 // The one-shot exchange (collective.hip) as the in-kernel training loop sees it: a rank's region is
 //   [header: XCHG_HEADER_WORDS words][slots: 2 parities x world ranks x capacity floats]
@@ -53,6 +54,9 @@ struct SpecArgs {
     uint32_t seed_lo, seed_hi, offset_lo, offset_hi;
     uint32_t n_iterations, pretraining_iterations, n_params, reserved;
     bsvi_opt_cfg cfg;
+    // the in-loop minibatch gather (spec_main.h, SPEC_MINIBATCH): the datasets of the program's minibatch sources, in the order
+    // of its geometry (bsvi_program_set_minibatches); behind everything else, so that no other field moves
+    const float* mb_data[SPEC_MB_MAX_SOURCES];
 };
 
 }  // namespace bsvi

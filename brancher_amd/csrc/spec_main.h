@@ -11,6 +11,16 @@
 //              sample shards of other GPUs), or loss / finite flag / scaled gradients / fused SGD-Adam step
 //              (inference.py:96-108), or that whole loop n_iterations times inside this one launch.
 #pragma once
+// The gather phase of the in-kernel training loop (SPEC_MINIBATCH, a define of the generated source with the sources' geometry
+// as literals — specialize.cpp, set_minibatches): observations that are a minibatch of a dataset take other rows in every
+// iteration, drawn by the keyed bijection of minibatch_index.h from (key, offset0 + it).  SPEC_DEBUG_NO_GATHER compiles the
+// phase out (measurements: what it costs; the rows then stay those of the observation buffer).
+#if defined(SPEC_MINIBATCH) && !SPEC_DIAG && !defined(SPEC_WITH_EXCHANGE) && !defined(SPEC_DEBUG_NO_GATHER)
+#define SPEC_MB 1
+#include "minibatch_index.h"
+#else
+#define SPEC_MB 0
+#endif
 
 namespace bsvi {
 
@@ -525,6 +535,71 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
     if (const unsigned long long* const offset_dev = SPEC_A->offset_dev) off0 += *offset_dev;
     const uint32_t n_global = SPEC_A->n_global;
     const uint32_t pretraining = SPEC_A->pretraining_iterations;
+#if SPEC_MB
+    // ---- the gather phase.  Source s rewrites its stretch obs[o : o + B * r] of the LDS observation table with the rows
+    //      dataset_s[minibatch_index(key_s, offset, b)][0 .. r) — ONE wave does it, lane l the rows b = l, l + 64, ...: the row's
+    //      index once per key group (sources that share a RandomIndices variable share the walk), then r floats per source, held
+    //      in SPEC_MB_REGS registers between `mb_fetch` (index walk + global loads: issued beside the bodies where the wave has
+    //      no body of its own) and `mb_store` (the LDS stores).  The bodies read the stretch between an iteration's first and
+    //      second barrier, so the stores lie between the second barrier and the next first one — no race, by construction.
+    //      Every geometry number is a literal of the generated source (SPEC_MB_SOURCES), the offsets of the body stay literals.
+    struct SpecGather { float v[SPEC_MB_REGS]; };
+    const uint32_t mb_seed_lo = B0.seed_lo, mb_seed_hi = B0.seed_hi;
+    auto mb_fetch = [&](unsigned long long offn, SpecGather& Gv) {
+        SPEC_RELOAD_ARGS();
+        const uint32_t olo = (uint32_t)offn, ohi = (uint32_t)(offn >> 32);
+#define SPEC_MB_INDEX(s, o, B, r, DS, g, leader, base) uint32_t idx_##s[SPEC_MB_MAXQ] = {}; (void)idx_##s;
+        SPEC_MB_SOURCES(SPEC_MB_INDEX)
+#undef SPEC_MB_INDEX
+#define SPEC_MB_FETCH(s, o, B, r, DS, g, leader, base)                                                              \
+        {                                                                                                           \
+            const float* const data = SPEC_A->mb_data[s];                                                           \
+            uint32_t klo, khi;                                                                                      \
+            minibatch_group_key(mb_seed_lo, mb_seed_hi, g, klo, khi);                                               \
+            _Pragma("unroll") for (uint32_t q = 0; q < ((B) + 63u) / 64u; ++q) {                                    \
+                const uint32_t b = lane + 64u * q;                                                                  \
+                if ((leader) == (s)) idx_##s[q] = b < (B) ? minibatch_index_keyed(DS, klo, khi, olo, ohi, b) : 0u;  \
+                const float* const row = data + (size_t)idx_##leader[q] * (r);                                      \
+                _Pragma("unroll") for (uint32_t e = 0; e < (r); ++e) Gv.v[(base) + q * (r) + e] = b < (B) ? row[e] : 0.0f; \
+            }                                                                                                       \
+        }
+        SPEC_MB_SOURCES(SPEC_MB_FETCH)
+#undef SPEC_MB_FETCH
+    };
+    auto mb_store = [&](const SpecGather& Gv) {
+#define SPEC_MB_STORE(s, o, B, r, DS, g, leader, base)                                                              \
+        _Pragma("unroll") for (uint32_t q = 0; q < ((B) + 63u) / 64u; ++q) {                                        \
+            const uint32_t b = lane + 64u * q;                                                                      \
+            if (b < (B)) {                                                                                          \
+                _Pragma("unroll") for (uint32_t e = 0; e < (r); ++e) spec_lds[SPEC_N_UNIFORM + (o) + b * (r) + e] = Gv.v[(base) + q * (r) + e]; \
+            }                                                                                                       \
+        }
+        SPEC_MB_SOURCES(SPEC_MB_STORE)
+#undef SPEC_MB_STORE
+    };
+    // Who gathers (wave-uniform).  The draw service: its last draw wave that is not on the owners' SIMD (wave & 3 == 1) — beside
+    // the bodies it draws one or two sets of normals and waits.  A single draw wave: that wave, idle beside the bodies.  No draw
+    // wave (the plain loop, several workgroups): the last wave that is not the owners', behind the second barrier, beside the
+    // owners' epilogue — every workgroup of a many-workgroup launch its own copy (the rows are a function of the key alone).
+    const bool mb_loop = mode == SPEC_MODE_LOOP;
+#if SPEC_DRAW_WAVE
+    const uint32_t mb_service_wave = ((W - 1u) & 3u) != 1u ? W - 1u : W - 2u;
+    const bool mb_in_service = draw_service;
+#else
+    const uint32_t mb_service_wave = 0u;
+    const bool mb_in_service = false;
+#endif
+    const uint32_t mb_plain_wave = (W - 1u) != (own_base >> 6) ? W - 1u : (W > 1u ? W - 2u : 0u);
+    const uint32_t mb_wave = mb_in_service ? mb_service_wave : has_draw_wave ? W - 1u : mb_plain_wave;
+    const bool mb_gatherer = __builtin_amdgcn_readfirstlane((mb_loop && wave == mb_wave) ? 1 : 0) != 0;
+    const bool mb_beside_bodies = has_draw_wave;      // (the gathering wave carries no samples: it fetches in front of the second barrier)
+    // iteration 0's rows: behind the prologue's barrier (the whole observation table is in LDS), in front of the first barrier
+    if (mb_gatherer) {
+        SpecGather G0;
+        mb_fetch(off0, G0);
+        mb_store(G0);
+    }
+#endif
     // several workgroups in loop mode (the many-workgroup geometry only: the one-workgroup kernels are never launched with
     // more, and the extra live scalars cost BASELINE config 1's kernel 30 more spilled scalar registers).  The arrival ticket
     // and the generation number of the launch are ZERO when it starts (the host clears both words on the launch's stream,
@@ -630,6 +705,10 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
             spec_lds_barrier();                                // (the main loop's first barrier: the sample waves read their buffers behind it)
             SPEC_RSTAMP(0);
             SPEC_RSTAMP_NEXT();
+#if SPEC_MB
+            SpecGather Gn;
+            if (mb_gatherer && more) mb_fetch(off0 + it + 1u, Gn);      // (the loads fly while the sets are drawn)
+#endif
             SpecNoise Za, Zb;
             float fac[2] = {0.0f, 0.0f};
             AdamBias bias = {1.0, 1.0, 0.0f, 0.0f};
@@ -690,6 +769,9 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
             SPEC_RSTAMP(1);
             spec_lds_barrier();                                // (the second: every wave's sums are in WS / RED, the buffers are free)
             SPEC_RSTAMP(2);
+#if SPEC_MB
+            if (mb_gatherer && more) mb_store(Gn);
+#endif
 #if SPEC_LEAN_OWNERS
             if (owners) {
                 // ---- the owners' epilogue, lean: every LDS word it needs requested in one batch — the waves' loss rows and
@@ -865,11 +947,18 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
             spec_lds_barrier();                                // (the main loop's first barrier: the sample waves read their buffers behind it)
             SPEC_RSTAMP(0);
             SPEC_RSTAMP_NEXT();
+#if SPEC_MB
+            SpecGather Gn;
+            if (mb_gatherer && more) mb_fetch(off0 + it + 1u, Gn);      // (the loads fly while the set is drawn)
+#endif
             SpecNoise Za;
             if (more && has_first) draw_for(first, off0 + it + 1u, Za);     // beside the bodies, in registers
             SPEC_RSTAMP(1);
             spec_lds_barrier();                                // (the second: the buffers are free)
             SPEC_RSTAMP(2);
+#if SPEC_MB
+            if (mb_gatherer && more) mb_store(Gn);
+#endif
             if (more) {
                 if (has_first) {
 #pragma unroll
@@ -986,10 +1075,24 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
             noise_ready = true;
         }
 #endif
+#if SPEC_MB && !SPEC_DRAW_OWNERS
+        // the gather: a single draw wave fetches the next rows here, beside the bodies; without one the wave fetches behind the
+        // barrier, beside the owners' epilogue (several workgroups: while thread 0 waits for the grid, below)
+        SpecGather Gn;
+        const bool mb_more = mb_gatherer && it + 1u < n_it;
+        if (mb_more && mb_beside_bodies) mb_fetch(off0 + it + 1u, Gn);
+#endif
         SPEC_RSTAMP(1);
         spec_lds_barrier();                                    // every wave's sums are in WS / RED
         SPEC_STAMP(5);
         SPEC_RSTAMP(2);
+#if SPEC_MB && !SPEC_DRAW_OWNERS
+        const bool mb_with_grid = SPEC_LOOP_MANY && G > 1 && mode == SPEC_MODE_LOOP;
+        if (mb_more && !mb_with_grid) {
+            if (!mb_beside_bodies) mb_fetch(off0 + it + 1u, Gn);
+            mb_store(Gn);
+        }
+#endif
 #if SPEC_DRAW_OWNERS
         SPEC_RSTAMP(4);
         continue;                                              // (the epilogue runs on the owners' draw wave)
@@ -1038,6 +1141,10 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
                 // are bounded (a launch whose workgroups are not all resident must not hang: it ends with a NaN loss).
                 unsigned int* const gen = ticket + 64;
                 const unsigned int target = gen0 + it + 1u;
+#if SPEC_MB && !SPEC_DRAW_OWNERS
+                // every workgroup rebuilds its own copy of the minibatch stretches, while its thread 0 waits for the grid
+                if (mb_more) { mb_fetch(off0 + it + 1u, Gn); mb_store(Gn); }
+#endif
                 if (blockIdx.x != 0) {
                     if (tid == 0) {
                         __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);

@@ -673,6 +673,12 @@ struct Spec {
     const uint32_t* pu_idx = nullptr;
     uint32_t n_cus = 256;
     bool draw_wave_ok = false;                            // the in-kernel loop may be given a wave that draws for the owners' wave
+    // minibatched observations inside the training loop (set_minibatches): the sources' geometry, the defines it becomes, and
+    // the loop variants with the gather phase compiled in — variant v's source behind the defines (0, 2, 4, 6, 7 only)
+    std::vector<uint32_t> mb_geometry;                    // n x {obs_offset, batch, row_floats, dataset_size, group}
+    std::string mb_defines;
+    Variant mb_variant[8];
+    bool mb_launch_prepared = false;
     uint32_t launch_seq = 0;
     std::mutex mu;
 };
@@ -819,9 +825,67 @@ Spec* create(const bsvi_program_desc& d, std::string& why) {
     return s;
 }
 
+// ---- minibatch sources of the in-kernel loop (spec_main.h, SPEC_MINIBATCH) ----------------------------------------------
+// The gathering wave keeps a row's floats of every source in registers between the loads (beside the bodies) and the LDS
+// stores (behind the second barrier): sum over the sources of ceil(batch / 64) * row_floats registers per lane.  The cap:
+// a 512-thread workgroup leaves a lane 256 registers; a draw wave of the service holds up to two sets of normals beside the
+// rows (2 x up to 68) and the loop's frame takes 77 to 96 (the compiled loop variants of the minibatch fixtures, the index
+// walk included): 256 - 136 - 96 = 24 are certain, and the fixtures' programs have far fewer noise rows than 68 — 32.
+constexpr uint32_t kMinibatchMaxRegs = 32;
+static int minibatch_defines(uint32_t n_obs, uint32_t n, const uint32_t* g, std::string& out) {
+    if (!n || !g) return bsvi_fail(BSVI_ERR_INVALID, "minibatch geometry: no sources");
+    if (n > bsvi::SPEC_MB_MAX_SOURCES) return bsvi_fail(BSVI_ERR_UNSUPPORTED, fmt("minibatch geometry: %u sources, the in-kernel gather serves up to %u", n, (uint32_t)bsvi::SPEC_MB_MAX_SOURCES));
+    uint32_t regs = 0, maxq = 1;
+    std::string list;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t o = g[5 * i], B = g[5 * i + 1], r = g[5 * i + 2], DS = g[5 * i + 3], grp = g[5 * i + 4];
+        if (!B || !r || !DS) return bsvi_fail(BSVI_ERR_INVALID, fmt("minibatch source %u: batch, row_floats and dataset_size must be positive", i));
+        if (B > DS) return bsvi_fail(BSVI_ERR_INVALID, fmt("minibatch source %u: batch %u exceeds dataset_size %u", i, B, DS));
+        if (DS >= (1u << 30)) return bsvi_fail(BSVI_ERR_UNSUPPORTED, fmt("minibatch source %u: dataset_size %u is beyond the index walk's domain", i, DS));
+        if ((uint64_t)o + (uint64_t)B * r > (uint64_t)n_obs)
+            return bsvi_fail(BSVI_ERR_INVALID, fmt("minibatch source %u: the stretch [%u, %llu) leaves the observation table [0, %u)", i, o,
+                                               (unsigned long long)o + (unsigned long long)B * r, n_obs));
+        const uint32_t q = (B + 63u) / 64u;
+        if ((uint64_t)q * r > kMinibatchMaxRegs || regs + q * r > kMinibatchMaxRegs)
+            return bsvi_fail(BSVI_ERR_UNSUPPORTED, fmt("minibatch geometry: the gathering wave would hold more than %u registers of rows (source %u: batch %u x %u floats)",
+                                                   kMinibatchMaxRegs, i, B, r));
+        // (sources of one key group with the same batch and dataset draw the same rows: the first of them walks the index)
+        uint32_t leader = i;
+        for (uint32_t j = 0; j < i; ++j)
+            if (g[5 * j + 4] == grp && g[5 * j + 1] == B && g[5 * j + 3] == DS) { leader = j; break; }
+        list += fmt(" F(%u, %uu, %uu, %uu, %uu, %uu, %u, %u)", i, o, B, r, DS, grp, leader, regs);
+        regs += q * r;
+        maxq = std::max(maxq, q);
+    }
+    out = fmt("#define SPEC_MINIBATCH %u\n#define SPEC_MB_REGS %u\n#define SPEC_MB_MAXQ %u\n", n, regs, maxq);
+    out += "// per source: F(index, obs_offset, batch, row_floats, dataset_size, key group, source whose row indices it shares, first register)\n";
+    out += "#define SPEC_MB_SOURCES(F)" + list + "\n";
+    return BSVI_OK;
+}
+static bool mb_loop_variant(int v) { return v == 0 || v == 2 || v == 4 || v == 6 || v == 7; }
+
+int set_minibatches(Spec* s, uint32_t n, const uint32_t* geometry) {
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (s->mb_launch_prepared) return bsvi_fail(BSVI_ERR_INVALID, "bsvi_program_set_minibatches: a training launch with this program's minibatch geometry was already prepared");
+    std::string defines;
+    const int rc = minibatch_defines(s->n_obs, n, geometry, defines);
+    if (rc) return rc;
+    s->mb_geometry.assign(geometry, geometry + 5 * (size_t)n);
+    s->mb_defines = defines;
+    for (int v = 0; v < 8; ++v) s->mb_variant[v].src = (mb_loop_variant(v) && !s->variant[v].src.empty()) ? defines + s->variant[v].src : std::string();
+    return BSVI_OK;
+}
+// the generated translation unit of loop variant v with the gather phase (empty: the variant does not run the loop)
+const std::string& source_minibatch(const Spec* s, int variant) {
+    static const std::string none;
+    return (variant >= 0 && variant < 8) ? s->mb_variant[variant].src : none;
+}
+uint32_t minibatch_sources(const Spec* s) { return (uint32_t)(s->mb_geometry.size() / 5); }
+
 void destroy(Spec* s) {
     if (!s) return;
     for (Variant& v : s->variant) if (v.module) (void)hipModuleUnload(v.module);
+    for (Variant& v : s->mb_variant) if (v.module) (void)hipModuleUnload(v.module);
     if (s->dev) (void)hipFree(s->dev);
     delete s;
 }
@@ -1088,8 +1152,9 @@ int last_variant() { return t_last_variant; }
 std::string cache_directory() { return disk_cache::enabled() ? disk_cache::directory() : std::string(); }
 std::string compiler_identity() { return disk_cache::compiler_identity(); }
 
-static int ensure_compiled(Spec* s, int v) {
-    Variant& V = s->variant[v];
+static int ensure_compiled(Variant& V);
+static int ensure_compiled(Spec* s, int v) { return ensure_compiled(s->variant[v]); }
+static int ensure_compiled(Variant& V) {
     if (V.fn) return BSVI_OK;
     if (V.failed) return BSVI_ERR_UNSUPPORTED;
     std::vector<char> code;
@@ -1201,9 +1266,20 @@ int launch(Spec* s, const bsvi_program* p, const Launch& L) {
     int v = 2 * g.geom + ((a->noise_dev || a->samples_out_dev || a->noise_out_dev || a->fvalue_out_dev || a->f_weight_dev || a->q_weight_dev) ? 1 : 0);
     if (L.xchg && !(L.mode == MODE_LOOP && g.blocks == 1 && v == 0 && s->exchange_ok))
         return bsvi_fail(BSVI_ERR_UNSUPPORTED, "the in-loop exchange serves the one-workgroup training loop with Philox noise and no per-sample outputs");
+    const bool gather = L.datasets != nullptr;
+    if (gather) {
+        // the loop with the gather phase: Philox noise, no per-sample outputs, one rank — everything else trains launch by launch
+        if (L.mode != MODE_LOOP || v != 2 * g.geom || L.xchg)
+            return bsvi_fail(BSVI_ERR_UNSUPPORTED, "the in-kernel minibatch gather serves the training loop with Philox noise, no per-sample outputs and one rank");
+        if (s->mb_geometry.empty()) return bsvi_fail(BSVI_ERR_UNSUPPORTED, "the program carries no minibatch geometry (bsvi_program_set_minibatches)");
+        for (size_t i = 0; i < s->mb_geometry.size() / 5; ++i)
+            if (!L.datasets[i]) return bsvi_fail(BSVI_ERR_INVALID, "a dataset pointer is null");
+    }
+    Variant* const table = gather ? s->mb_variant : s->variant;
     uint32_t seq;
     {
         std::lock_guard<std::mutex> lock(s->mu);
+        if (gather) s->mb_launch_prepared = true;
         if (L.xchg) {
             const int rc5 = ensure_compiled(s, 5);
             if (rc5) return rc5;
@@ -1211,14 +1287,14 @@ int launch(Spec* s, const bsvi_program* p, const Launch& L) {
         }
         else if (g.draw_owners && v == 0 && owner_wave()) {
             v = lean_chain() ? 6 : 7;
-            if (v == 7 && s->variant[7].src.empty())
+            if (v == 7 && table[7].src.empty())
                 return bsvi_fail(BSVI_ERR_UNSUPPORTED, "BSVI_SPEC_LEAN_CHAIN=0 needs the variable set when the program is created (the previous source is generated then)");
-            const int rc6 = ensure_compiled(s, v);
+            const int rc6 = ensure_compiled(table[v]);
             if (rc6) return rc6;
         }
-        else if (g.draw_wave && v == 0 && ensure_compiled(s, 4) == BSVI_OK) v = 4;
+        else if (g.draw_wave && v == 0 && ensure_compiled(table[4]) == BSVI_OK) v = 4;
         else if (g.draw_wave) { g.threads -= 64 * g.extra_waves; g.draw_wave = false; }        // (diagnostic kernel, or the variant did not compile)
-        const int rc = ensure_compiled(s, v);
+        const int rc = ensure_compiled(table[v]);
         if (rc) return rc;
         seq = s->launch_seq++;
     }
@@ -1244,16 +1320,18 @@ int launch(Spec* s, const bsvi_program* p, const Launch& L) {
     A.xchg = (const bsvi::SpecExchange*)L.xchg;
     A.n_iterations = L.n_iterations; A.pretraining_iterations = L.pretraining_iterations; A.n_params = s->n_params;
     if (L.cfg) A.cfg = *L.cfg;
+    if (gather)
+        for (size_t i = 0; i < s->mb_geometry.size() / 5; ++i) A.mb_data[i] = L.datasets[i];
     if (g.blocks > 1) {
         // every workgroup of the in-kernel loop over several workgroups must be resident (workgroup 0 waits for the others in every
         // iteration): never more than the occupancy of THIS code object allows — fewer workgroups walk more chunks each
-        int per_cu = s->variant[v].per_cu;
+        int per_cu = table[v].per_cu;
         if (!per_cu) {
-            if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, s->variant[v].fn, (int)g.threads, 0) != hipSuccess || per_cu <= 0) {
+            if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, table[v].fn, (int)g.threads, 0) != hipSuccess || per_cu <= 0) {
                 (void)hipGetLastError();
                 per_cu = -1;                 // (no answer: geo()'s register / LDS estimate stands)
             }
-            s->variant[v].per_cu = per_cu;
+            table[v].per_cu = per_cu;
         }
         if (per_cu > 0 && g.blocks > (uint32_t)per_cu * s->n_cus) g.blocks = (uint32_t)per_cu * s->n_cus;
         if (L.mode == MODE_LOOP) {
@@ -1266,7 +1344,7 @@ int launch(Spec* s, const bsvi_program* p, const Launch& L) {
     }
     size_t size = sizeof A;
     void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &A, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-    const hipError_t e = hipModuleLaunchKernel(s->variant[v].fn, g.blocks, 1, 1, g.threads, 1, 1, 0, (hipStream_t)a->stream, nullptr, config);
+    const hipError_t e = hipModuleLaunchKernel(table[v].fn, g.blocks, 1, 1, g.threads, 1, 1, 0, (hipStream_t)a->stream, nullptr, config);
     if (e != hipSuccess) return bsvi_fail(BSVI_ERR_HIP, std::string("hipModuleLaunchKernel (specialised kernel): ") + hipGetErrorString(e));
     t_last_variant = v;
     return BSVI_OK;

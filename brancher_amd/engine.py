@@ -430,6 +430,7 @@ class CompiledELBO:
         self._workspaces = {}
         self._train_plans = {}
         self._fast_train = {}
+        self.last_error = None      # why the last call that asked for something was served another way (e.g. the minibatch loop)
         self._plain_args = {}
         self._shares_for = None
         self._noise_cache = None
@@ -836,9 +837,15 @@ class CompiledELBO:
 
     def train(self, number_iterations, number_samples, optimizer="Adam", noise_seq=None, seed=None,
               pretraining_iterations=0, allow_persistent=True, minibatch_seq=None, _force_sharded_path=False,
-              **opt_params):
+              minibatch_loop=False, **opt_params):
         """`brancher/inference.py:95-108` on the device.  Returns (loss_curve, finite_flags) as
-        device tensors of length number_iterations; nothing synchronises with the host."""
+        device tensors of length number_iterations; nothing synchronises with the host.
+
+        `minibatch_loop=True`: a model that observes minibatches of a dataset (EmpiricalVariable) keeps the whole loop in ONE
+        launch too — the generated kernel draws and gathers every iteration's rows itself (`bsvi_train_persistent_minibatch`),
+        the same rows the launch-by-launch path gathers.  Served on one rank, with Philox noise and drawn rows, by the
+        program-specialised kernels; everything else (`BSVI_JIT=0`, `noise_seq`, `minibatch_seq`, several ranks, external nodes,
+        more rows than the gathering wave holds, `BSVI_MINIBATCH_LOOP=0`) trains launch by launch as without the keyword."""
         # The short call (the driver times 20 iterations: ~100 us on the device): everything a repeat of the same call needs
         # — optimizer block, argument block, ctypes pointers, the launch plan — is kept from the first one, and the call is
         # a buffer, five stores into the argument block and ONE library call.
@@ -870,21 +877,32 @@ class CompiledELBO:
         # (_force_sharded_path: run the multi-GPU step sequence on one GPU — tests)
         # which launch path serves this shard: decided once per (shard size, switches) — four library queries that a
         # short training call (the driver times 20 iterations) would otherwise repeat
-        plan_key = (n_local, bool(allow_persistent), world, bool(_force_sharded_path), os.environ.get("BSVI_JIT"))
+        in_loop_gather = bool(minibatch_loop and self._minibatches and noise_seq is None and minibatch_seq is None
+                              and os.environ.get("BSVI_MINIBATCH_LOOP", "1") != "0")
+        plan_key = (n_local, bool(allow_persistent), world, bool(_force_sharded_path), os.environ.get("BSVI_JIT"), in_loop_gather)
         plan = self._train_plans.get(plan_key)
         if plan is None or self._shares_for != n_local:
             self.native.ensure_shares(n_local)          # (the share set attached to the program follows the last shard size)
             self._shares_for = n_local
         if plan is None:
-            # (observations that are a minibatch change in every iteration: the loop cannot stay in one launch)
+            # (observations that are a minibatch change in every iteration: the plain loop cannot serve them — `gathers` below)
             persistent = (allow_persistent and world == 1 and not _force_sharded_path and not self._externals
                           and not self._minibatches and self.native.persistent_supported(n_local))
             shares = self.native.split_shares(n_local) if persistent else None
             # the specialised in-kernel loop starts a fresh optimizer itself and nobody reads its final state: no state
             # buffer, and with it no fill launch in front of the training launch
             fresh = persistent and shares is None and self.native.engine(n_local, 2)["engine"] == "specialised"
-            plan = self._train_plans[plan_key] = (persistent, shares, fresh)
-        persistent, shares, fresh_in_kernel = plan
+            gathers = False
+            if (in_loop_gather and allow_persistent and world == 1 and not _force_sharded_path and not self._externals
+                    and self.native.engine(n_local, 2)["engine"] == "specialised"):
+                # minibatched observations inside the in-kernel loop: the program took its sources' geometry when it was created
+                if self.native.minibatch_loop:
+                    gathers, fresh = True, True
+                else:
+                    self.last_error = "minibatch loop declined: " + str(self.native.minibatch_loop_refusal)
+                    warnings.warn(self.last_error + "; training launch by launch")
+            plan = self._train_plans[plan_key] = (persistent, shares, fresh, gathers)
+        persistent, shares, fresh_in_kernel, gathers = plan
         loss_curve, finite, state = training_buffers(K, p.n_params, dev, with_state=not (fresh_in_kernel and K > 0))
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         noise_t = None
@@ -899,6 +917,22 @@ class CompiledELBO:
         self.grads_valid = True
         if K == 0:
             return loss_curve[:0], finite[:0]
+
+        if gathers:
+            # ONE launch: every iteration's rows are drawn and gathered by the kernel (spec_main.h, the gather phase)
+            args = self._elbo_args(n_local, number_samples, base, None, seed, offset0)
+            datasets = (C.c_void_p * len(self._minibatches))(*[mb["data"].data_ptr() for mb in self._minibatches])
+            rc = self.lib.bsvi_train_persistent_minibatch(
+                self.native.handle, C.byref(args), C.byref(cfg), ptr(self.params), ptr(state), ptr(self.mask_all),
+                ptr(self.mask_first), int(pretraining_iterations), K, ptr(loss_curve), ptr(finite), datasets)
+            if rc == 0:
+                self.last_mode = "persistent"
+                return loss_curve, finite
+            # not served after all (the variant did not compile, the engine was switched since): launch by launch, from now on
+            self.last_error = "minibatch loop declined: " + self.lib.bsvi_last_error().decode()
+            warnings.warn(self.last_error + "; training launch by launch")
+            self._train_plans[plan_key] = (persistent, shares, False, False)
+            loss_curve, finite, state = training_buffers(K, p.n_params, dev, with_state=True)
 
         if persistent:
             args = self._elbo_args(n_local, number_samples, base, noise_t, seed, offset0)
@@ -920,7 +954,7 @@ class CompiledELBO:
                     # the plan said "specialised in-kernel loop" before the lazy hiprtc compile; if that compile then
                     # fails the library leaves the program to the interpreter's trainer, which needs a state buffer:
                     # forget the plan and run this call (and every later one) with one
-                    self._train_plans[plan_key] = (persistent, shares, False)
+                    self._train_plans[plan_key] = (persistent, shares, False, False)
                     loss_curve, finite, state = training_buffers(K, p.n_params, dev, with_state=True)
                     rc = call(state)
                 native.check(rc)

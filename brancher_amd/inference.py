@@ -133,6 +133,11 @@ class ReverseKL(InferenceMethod):
         extra = {}
         if getattr(compiled, "prefers_stepwise", None) and compiled.prefers_stepwise(number_samples):
             extra["allow_persistent"] = False
+        if getattr(compiled, "_minibatches", None):
+            # observations that are minibatches of a dataset: the rows are drawn and gathered inside the training launch
+            # (CompiledELBO.train, minibatch_loop; BSVI_MINIBATCH_LOOP=0 switches it off)
+            extra["minibatch_loop"] = True
+        self.last_compiled = compiled       # (what served the last run: its `last_mode` says how)
         return compiled.train(number_iterations, number_samples, optimizer,
                               pretraining_iterations=pretraining_iterations, **extra, **opt_params)
 

@@ -245,6 +245,11 @@ EXPORTS.update({
     "bsvi_exchange_selftest_tagged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "bsvi_minibatch_gather": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bsvi_exchange_destroy": (None, [C.c_void_p]),
+    # minibatched observations inside the in-kernel training loop
+    "bsvi_program_set_minibatches": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "bsvi_train_persistent_minibatch": (C.c_int, [C.c_void_p, C.POINTER(ElboArgs), C.POINTER(OptCfg), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "bsvi_program_source_minibatch": (C.c_size_t, [C.POINTER(ProgramDesc), C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
 })
 
 class MvnInsn(C.Structure):
@@ -484,6 +489,39 @@ def specialised_source(program, variant=0):
     return buf.value.decode()
 
 
+def minibatch_geometry(program):
+    """the minibatch sources of a lowered program as bsvi_program_set_minibatches takes them: a ctypes array of
+    n x {obs_offset, batch, row_floats, dataset_size, group} words (and n), or (None, 0)"""
+    mbs = getattr(program, "minibatches", None) or []
+    if not mbs:
+        return None, 0
+    words = []
+    for mb in mbs:
+        words += [int(mb["offset"]), int(mb["batch"]), int(mb["row"]), int(mb["dataset_size"]), int(mb["group"])]
+    return (C.c_uint32 * len(words))(*words), len(mbs)
+
+
+def specialised_source_minibatch(program, variant=0, geometry=None):
+    """The generated translation unit of a LOOP variant with the gather phase (bsvi_program_source_minibatch): host only.
+    `geometry`: a list of (obs_offset, batch, row_floats, dataset_size, group), default the program's own sources.  None when
+    the library refuses (bsvi_last_error says why) or the variant does not run the loop."""
+    lib = load()
+    d, keep = program_desc(program)
+    if geometry is None:
+        geo, n = minibatch_geometry(program)
+    else:
+        words = [int(w) for row in geometry for w in row]
+        geo, n = (C.c_uint32 * max(len(words), 1))(*words), len(geometry)
+    if geo is None:
+        return None
+    need = lib.bsvi_program_source_minibatch(C.byref(d), variant, n, geo, None, 0)
+    if need == 0:
+        return None
+    buf = C.create_string_buffer(need)
+    lib.bsvi_program_source_minibatch(C.byref(d), variant, n, geo, buf, need)
+    return buf.value.decode()
+
+
 def jit_compile(source):
     """hiprtc-compile a generated translation unit for gfx950 (no device needed); returns the code-object size."""
     n = C.c_size_t()
@@ -535,6 +573,16 @@ class NativeProgram:
         self._elbo_shares_set = 0
         self._shares_wanted = 0
         self.ensure_shares(1)
+        # minibatch sources: their geometry goes into the generated training loop (bsvi_program_set_minibatches); a refusal —
+        # a program the generator declined, more rows than the gathering wave holds — leaves the launch-by-launch gather
+        self.minibatch_loop_refusal = None
+        geo, n = minibatch_geometry(program)
+        self.minibatch_loop = False
+        if n:
+            if lib.bsvi_program_set_minibatches(handle, n, geo) == 0:
+                self.minibatch_loop = True
+            else:
+                self.minibatch_loop_refusal = lib.bsvi_last_error().decode()
 
     def workspace_bytes(self, n_local):
         return int(self.lib.bsvi_workspace_bytes(self.handle, n_local))

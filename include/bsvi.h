@@ -908,6 +908,35 @@ int bsvi_minibatch_gather(const float* dataset_dev, uint32_t dataset_size, uint3
                           const int32_t* indices_dev, uint64_t seed, uint64_t offset, float* dst_dev, int32_t* indices_out_dev,
                           void* stream);
 
+/* (ABI 11, entry points added without a change to any struct) Minibatched observations INSIDE the in-kernel training loop: replaces
+ * standard_variables.py:71-112 + distributions.py:393-473 (the draw of the rows and the gather) as they run inside inference.py:95-108
+ * (the loop) — K iterations of draw rows / gather / ELBO / gradients / optimizer step in ONE launch, where the stepwise path is one
+ * gather launch per source plus one step launch per iteration with the host between them.
+ *
+ * bsvi_program_set_minibatches tells a program which stretches of its observation table are minibatches: n_sources rows of
+ *   {obs_offset, batch, row_floats, dataset_size, group} — the stretch obs[obs_offset : obs_offset + batch * row_floats] takes `batch`
+ *   rows of a dataset [dataset_size][row_floats]; sources with the same group, batch and dataset_size take the SAME rows (they share a
+ *   RandomIndices variable).  The geometry becomes literals of the generated kernels (and so part of the code-object cache key).
+ *   Call it once after bsvi_program_create, before the first launch that uses it: it is refused (BSVI_ERR_INVALID) once such a launch
+ *   was prepared, when a stretch leaves [0, n_obs) or when batch > dataset_size, and with BSVI_ERR_UNSUPPORTED when the program is not
+ *   specialised, has more than 8 sources or more rows than the gathering wave holds in registers (sum of ceil(batch / 64) * row_floats
+ *   above 32).  A refused program trains launch by launch as before.
+ * bsvi_train_persistent_minibatch is bsvi_train_persistent2 with the gather phase: datasets_dev is a HOST array of n_sources device
+ *   pointers, in the order of the geometry.  In iteration it, source s reads dataset row
+ *   index(key_s, a->offset + it, b) for b < batch, key_s = (a->seed ^ 0x9E3779B97F4A7C15 * group_s) & (2^63 - 1) — exactly the rows
+ *   bsvi_minibatch_gather fetches when called with (key_s, a->offset + it).  state_dev may be NULL (a fresh optimizer, nothing written
+ *   back).  BSVI_ERR_UNSUPPORTED with a bsvi_last_error text when the shard or the arguments are not served (the interpreter engine,
+ *   caller noise, per-sample outputs, no geometry): the host then gathers and steps launch by launch.
+ * bsvi_program_source_minibatch is bsvi_program_source for the loop variants with the gather phase (host only, no device): variants
+ *   0 and 2 (one / many workgroups), 4 (draw waves), 6 (owners on a draw wave); returns 0 for other variants or a refused geometry. */
+int bsvi_program_set_minibatches(bsvi_program* p, uint32_t n_sources, const uint32_t* geometry);
+int bsvi_train_persistent_minibatch(const bsvi_program* p, const bsvi_elbo_args* a, const bsvi_opt_cfg* cfg, float* params_dev,
+                                    float* state_dev, const uint8_t* active_mask_dev, const uint8_t* active_mask_first_dev,
+                                    uint32_t pretraining_iterations, uint32_t n_iterations, float* loss_curve_dev, float* finite_dev,
+                                    const float* const* datasets_dev);
+size_t bsvi_program_source_minibatch(const bsvi_program_desc* desc, int variant, uint32_t n_sources, const uint32_t* geometry,
+                                     char* buf, size_t capacity);
+
 const char* bsvi_last_error(void);
 int bsvi_abi_version(void);
 /* number of gfx950 devices visible to the HIP runtime (0 if none) */
