@@ -1044,7 +1044,12 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
             if (!draw_wave) {
                 spec_body(B, T, Z, WSw);
 #if SPEC_TILE
-                spec_du_flush(spec_lds + SPEC_OFF_TR + wave * SPEC_TR_FLOATS, WSw, lane);
+                {
+                    // the lanes of this wave with a sample of this chunk (the samples fill the lanes in order)
+                    const uint32_t first = T.n - lane;
+                    const uint32_t live = __builtin_amdgcn_readfirstlane(first < B.n_local ? (B.n_local - first < 64u ? B.n_local - first : 64u) : 0u);
+                    spec_du_flush(spec_lds + SPEC_OFF_TR + wave * SPEC_TR_FLOATS, WSw, lane, live);
+                }
 #endif
             }
 #endif

@@ -165,6 +165,31 @@ __shared__ __attribute__((aligned(16))) float spec_lds[SPEC_LDS_FLOATS];
 #define SPEC_UR(k) spec_lds[SPEC_OFF_UR + (k) + T.vz]
 #define SPEC_UL(k) spec_lds[SPEC_OFF_UL + (k) + T.vz]
 
+
+// ---- the trimmed kernels (specialize.cpp, BSVI_SPEC_TRIM): work the result does not need, off the sample waves.  Each item has
+//      a switch of its own for measurements (BSVI_SPEC_DEFINES); without SPEC_TRIM the source compiles as it did before them.
+//  SPEC_SAME(k, k0)  entry k of the uniform table publishes the same constant as the earlier entry k0 (same value bits, transform,
+//      a and b): the body reads k0, once, where it read twenty copies (the likelihood terms' measure_noise at config 1).
+//  SPEC_ENT_NOISE    the scale gradient of a sampled node with an entropy term only: fma(zb, eps, w / S).  It was
+//      (0 + w / S) + zb * eps, one rounding as well, with the 0 + x an instruction of its own.
+//  SPEC_FLUSH_MASK   SPEC_TILE: SPEC_DU stores a lane's contribution as it is and spec_du_flush leaves the idle lanes' columns out,
+//      instead of a select in front of every store in every wave (only a shard's last wave has idle lanes).
+#if defined(SPEC_TRIM) && !defined(SPEC_DEBUG_NO_SHARED_CONST)
+#define SPEC_SAME(k, k0) k0
+#else
+#define SPEC_SAME(k, k0) k
+#endif
+#if defined(SPEC_TRIM) && !defined(SPEC_DEBUG_NO_ENT_NOISE)
+#define SPEC_ENT_NOISE(gs, ws, zb, eps) gs = __builtin_fmaf(zb, eps, ws)
+#else
+#define SPEC_ENT_NOISE(gs, ws, zb, eps) gs += ws; gs += (zb) * (eps)
+#endif
+#if defined(SPEC_TRIM) && !defined(SPEC_DEBUG_NO_FLUSH_MASK) && SPEC_TILE
+#define SPEC_FLUSH_MASK 1
+#else
+#define SPEC_FLUSH_MASK 0
+#endif
+
 typedef float spec_f4 __attribute__((ext_vector_type(4)));
 
 // Contribution of this lane to position `pos` (a literal).  Two schemes, chosen per program by the generator:
@@ -188,14 +213,47 @@ __device__ __forceinline__ float spec_row_sum(float x) {
     return x;
 }
 #if SPEC_TILE
+#if SPEC_FLUSH_MASK
+#define SPEC_DU(pos, val) spec_lds[SPEC_OFF_TR + T.tile + (pos) * SPEC_TR_STRIDE] = (val)
+#else
 #define SPEC_DU(pos, val) spec_lds[SPEC_OFF_TR + T.tile + (pos) * SPEC_TR_STRIDE] = T.active ? (val) : 0.0f
-__device__ __forceinline__ void spec_du_flush(const float* TRw, float* WSw, uint32_t lane) {
+#endif
+// `live`: the wave's lanes that carry a sample of this chunk — the first `live` of them; wave-uniform, in a scalar register
+// (SPEC_FLUSH_MASK; unused otherwise: the idle lanes stored zeros)
+__device__ __forceinline__ void spec_du_flush(const float* TRw, float* WSw, uint32_t lane, uint32_t live) {
+    (void)live;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the wave's tile stores have landed (LDS is in order)
     if (lane < SPEC_N_POS) {
         const spec_f4* row = reinterpret_cast<const spec_f4*>(TRw + lane * SPEC_TR_STRIDE);
+#if SPEC_FLUSH_MASK
+        // The idle lanes' columns hold whatever those lanes computed, not necessarily finite: they never enter a sum.  The pieces
+        // are added in the same order, two reads in flight, as before; a wave-uniform branch in front of each pair leaves the chain
+        // where the whole pieces end — never, in a full wave — for an odd whole piece and the piece that `live` cuts, its idle
+        // components selected to zero as they were stored before.  A piece wholly past `live` was + 0.0f and is skipped.  The sum
+        // starts from -0.0f: -0 + x is x bit for bit, so the first piece starts it as before.  A wave without a sample leaves
+        // -0.0f where it left 0.0f; every reader of the waves' totals adds them to a sum that starts from 0.0f (spec_pos_total
+        // here, spec_rows_total of the lean owners' epilogue in spec_main.h, the `+=` of the chunk-walking kernels).
+        const uint32_t whole = live >> 2, cut = live & 3u;
+        spec_f4 s = spec_f4{-0.0f, -0.0f, -0.0f, -0.0f};
+#pragma unroll
+        for (uint32_t q = 0; q < 16u; q += 2u) {
+            if (q + 2u > whole) break;
+            s += row[q];
+            s += row[q + 1u];
+        }
+        if (whole & 1u) s += row[whole & ~1u];
+        if (cut) {                                              // lane 4 * whole is live, lane 4 * whole + 3 is not
+            const spec_f4 c = row[whole];
+            s.x += c.x;
+            s.y += cut > 1u ? c.y : 0.0f;
+            s.z += cut > 2u ? c.z : 0.0f;
+            s.w += 0.0f;
+        }
+#else
         spec_f4 s = row[0];
 #pragma unroll
         for (uint32_t q = 1; q < 16u; ++q) s += row[q];
+#endif
         const float t = (s.x + s.y) + (s.z + s.w);
 #if SPEC_ACCUMULATE_CHUNKS
         WSw[lane] += t;

@@ -76,8 +76,23 @@ std::string flit(uint32_t bits) {       // a float literal that round-trips
 
 class Emitter {
 public:
-    Emitter(const bsvi_program_desc& d, bool diag, bool fold = true) : d_(d), diag_(diag), fold_(fold) {
+    Emitter(const bsvi_program_desc& d, bool diag, bool fold = true, bool trim = false) : d_(d), diag_(diag), fold_(fold), trim_(trim) {
         keep_eps_ = d.n_noise <= kKeepEpsRows;
+        // (trim_) constant entries that repeat an earlier one — same value bits, transform, a and b: the table publishes the same
+        // three numbers for both, every iteration — are read at the earlier one's index (SPEC_SAME, spec_prelude.h)
+        same_as_.resize(d.n_uniform);
+        for (uint32_t k = 0; k < d.n_uniform; ++k) {
+            same_as_[k] = k;
+            const bsvi_uniform_entry& u = d.uniform[k];
+            if (!trim_ || !d.consts || u.is_param || u.src >= d.n_consts) continue;
+            for (uint32_t k0 = 0; k0 < k; ++k0) {
+                const bsvi_uniform_entry& u0 = d.uniform[k0];
+                if (u0.is_param || u0.src >= d.n_consts || u0.transform != u.transform) continue;
+                if (memcmp(&u0.a, &u.a, 4) || memcmp(&u0.b, &u.b, 4) || memcmp(d.consts + u0.src, d.consts + u.src, 4)) continue;
+                same_as_[k] = k0;
+                break;
+            }
+        }
         // long programs: a gradient contribution leaves through its own position of the transpose tile instead of
         // waiting in an accumulator register for the entry's last contribution
         direct_du_ = d.n_uniform_grad > kAccumulateEntries;
@@ -148,7 +163,8 @@ public:
 
 private:
     const bsvi_program_desc& d_;
-    bool diag_, fold_;
+    bool diag_, fold_, trim_;
+    std::vector<uint32_t> same_as_;       // uniform entry -> the first entry that publishes the same constant (itself otherwise)
     bool keep_eps_ = true, counting_ = true, direct_du_ = false, reschedule_ = true, two_pass_ = false;
     int sink_mode_ = 0;         // two_pass_: 1 = a sink's value only (forward sweep), 2 = its adjoints only (reverse sweep); 0 = both
     size_t visits_ = 0;
@@ -174,7 +190,11 @@ private:
     }
     std::string val(uint32_t o, uint32_t e) const {
         const Opnd p = resolve(o, e);
-        return p.lane ? fmt("v_%u", p.idx) : fmt("SPEC_U(%u)", p.idx);
+        return p.lane ? fmt("v_%u", p.idx) : fmt("SPEC_U(%s)", entry(p.idx).c_str());
+    }
+    // the index a table read is emitted with (observations, parameters and first occurrences: their own)
+    std::string entry(uint32_t k) const {
+        return (k < same_as_.size() && same_as_[k] != k) ? fmt("SPEC_SAME(%u, %u)", k, same_as_[k]) : fmt("%u", k);
     }
     // Literal constants of the model.  "An absent factor / addend is encoded as the constant 1.0 / 0.0 of the uniform table"
     // (include/bsvi.h): an entry sourced from the program's constants with the identity transform, a = 0, b = 1 and a value
@@ -238,11 +258,11 @@ private:
     // 1/S and log S of a Normal node's scale: companions of the uniform table when S is lane-uniform
     std::string rcp_of(uint32_t o, uint32_t e) const {
         const Opnd p = resolve(o, e);
-        return p.lane ? fmt("spec_rcp(v_%u)", p.idx) : fmt("SPEC_UR(%u)", p.idx);
+        return p.lane ? fmt("spec_rcp(v_%u)", p.idx) : fmt("SPEC_UR(%s)", entry(p.idx).c_str());
     }
     std::string log_of(uint32_t o, uint32_t e) const {
         const Opnd p = resolve(o, e);
-        return p.lane ? fmt("spec_log(v_%u)", p.idx) : fmt("SPEC_UL(%u)", p.idx);
+        return p.lane ? fmt("spec_log(v_%u)", p.idx) : fmt("SPEC_UL(%s)", entry(p.idx).c_str());
     }
 
     // ---- noise of a Normal draw.  Programs that keep their noise (keep_eps_) take it from spec_draw's SpecNoise,
@@ -399,8 +419,12 @@ private:
                     const std::string gw = (flags & BSVI_F_WF) ? fmt("(%s + fweight)", wg(I.imm0).c_str()) : wg(I.imm0);
                     line(fmt("  spec_naff_lp_bwd(%s, %s, loc, rS, gv, gl, gs);", gw.c_str(), v.c_str()));
                 }
-                if (flags & BSVI_F_ENT) line(fmt("  gs += %s * rS;", wg(I.imm1).c_str()));
             }
+            // (trim_) a sampled node with an entropy term and no log-prob term: gs is 0 + w / S + zb * eps, and the sum with the literal
+            // zero survives as an instruction (0 + x is not x for x = -0).  SPEC_ENT_NOISE (spec_prelude.h) is the same fused
+            // multiply-add with w / S itself for its addend: one rounding, as before.
+            const bool ent_noise = trim_ && (flags & BSVI_F_ENT) && (flags & BSVI_F_SAMPLE) && !(flags & (BSVI_F_LOGP | BSVI_F_WF));
+            if ((flags & BSVI_F_ENT) && !ent_noise) line(fmt("  gs += %s * rS;", wg(I.imm1).c_str()));
             if (flags & BSVI_F_SAMPLE) {
                 // a sampled latent's own adjoint is its incoming gradient: folded into loc / scale, left unchanged
                 if (!counting_) {
@@ -408,7 +432,8 @@ private:
                     const std::string eps = eps_reverse(dst.idx);
                     line(fmt("  const float zb = a_%u + gv;", dst.idx));
                     line("  gl += zb;");
-                    line(fmt("  gs += zb * %s;", eps.c_str()));
+                    if (ent_noise) line(fmt("  SPEC_ENT_NOISE(gs, %s * rS, zb, %s);", wg(I.imm1).c_str(), eps.c_str()));
+                    else line(fmt("  gs += zb * %s;", eps.c_str()));
                 }
             } else {
                 add_adj(I.dst, e, "gv");
@@ -758,16 +783,22 @@ Spec* create(const bsvi_program_desc& d, std::string& why) {
     // (comparisons).
     const char* const tail_env = getenv("BSVI_SPEC_TAIL");
     const bool tail = !(tail_env && tail_env[0] == '0');
+    // The trimmed kernels (every variant; spec_prelude.h SPEC_TRIM): repeated constant entries read once, no zero-add in the
+    // reverse step of an entropy-only node, idle lanes masked in the tile's flush instead of in every store.  BSVI_SPEC_TRIM=0,
+    // read when the program is created, generates the sources as they were (comparisons).
+    const char* const trim_env = getenv("BSVI_SPEC_TRIM");
+    const bool trim = !(trim_env && trim_env[0] == '0');
     for (int gi = 0; gi < 2; ++gi) {
         const Geom& G = s->geom[gi];
         for (int v = 0; v < (gi == GEOM_ONE && want_previous ? 3 : 2); ++v) {
             const bool old = v == 2;       // (v == 2: variant 0 once more, in its previous form)
             const bool lean = lean_body && !old;
-            Emitter E(d, v == 1, lean);
+            Emitter E(d, v == 1, lean, trim);
             if (!E.run(why)) { delete s; return nullptr; }
             std::string src;
             src += "// generated by libbsvi (specialize.cpp) from a model program: do not edit\n";
             src += "#define BSVI_SPECIALIZED 1\n";
+            if (trim) src += "#define SPEC_TRIM 1\n";
             // long BlackBox programs: no SLP vectorizer.  gfx950 has packed f32 arithmetic, so the vectorizer pairs the
             // isomorphic terms of DISTANT records of the unrolled stream into <2 x float> operations placed at the later one
             // — every such pair holds the earlier record's operands across the records in between (T = 200: 2 158 spilled
