@@ -60,7 +60,7 @@ Spec* create(const bsvi_program_desc& desc, std::string& why);
 void destroy(Spec* s);
 // device-side tables of the spec (needs a device; called from bsvi_program_create)
 int upload(Spec* s);
-// the generated translation unit of a variant (0 lean, 1 diagnostic) — tests and bsvi_program_source
+// the generated translation unit of a variant (VariantId, spec_select.h) — tests and bsvi_program_source
 const std::string& source(const Spec* s, int variant);
 // compile a generated translation unit for gfx950 with hiprtc; `code` receives the code object
 int compile(const std::string& src, std::vector<char>& code, std::string& log);

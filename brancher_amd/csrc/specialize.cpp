@@ -35,6 +35,7 @@
 #include "bsvi.h"
 #include "bsvi_internal.h"
 #include "spec_args.h"
+#include "spec_select.h"
 #include "jit_headers.inc"      // kJitHeaderNames / kJitHeaderTexts: the device headers, embedded by the Makefile
 
 namespace bsvi_spec {
@@ -57,13 +58,22 @@ constexpr uint32_t kFenceEvery = 4;           // ... every this many records
 constexpr uint32_t kBasicRegallocAboveCode = 700;   // programs longer than this are compiled with LLVM's basic register allocator
 constexpr uint32_t kAccumulateEntries = 1u << 30;   // up to this many gradient-carrying uniform entries accumulate in registers
 
-std::string fmt(const char* f, ...) {
-    char buf[512];
-    va_list ap;
+std::string fmt(const char* f, ...) {     // (sized first: a generated line is never cut short)
+    va_list ap, again;
     va_start(ap, f);
-    vsnprintf(buf, sizeof buf, f, ap);
+    va_copy(again, ap);
+    const int n = vsnprintf(nullptr, 0, f, ap);
     va_end(ap);
-    return buf;
+    std::string s(n > 0 ? (size_t)n : 0, '\0');
+    if (n > 0) vsnprintf(&s[0], (size_t)n + 1, f, again);
+    va_end(again);
+    return s;
+}
+
+// an environment switch: on unless the variable's value starts with '0'
+bool switch_on(const char* name) {
+    const char* e = getenv(name);
+    return !(e && e[0] == '0');
 }
 
 std::string flit(uint32_t bits) {       // a float literal that round-trips
@@ -74,9 +84,16 @@ std::string flit(uint32_t bits) {       // a float literal that round-trips
     return fmt("%.9gf", (double)x);
 }
 
+struct EmitOptions {
+    bool diag = false;          // the diagnostic kernel: noise in / samples, noise and per-sample values out
+    bool fold = true;           // literal constants folded (the lean body)
+    bool trim = false;          // SPEC_TRIM (spec_prelude.h)
+    bool two_pass = true;       // long BlackBox programs run their sinks twice (BSVI_SPEC_TWO_PASS)
+};
+
 class Emitter {
 public:
-    Emitter(const bsvi_program_desc& d, bool diag, bool fold = true, bool trim = false) : d_(d), diag_(diag), fold_(fold), trim_(trim) {
+    Emitter(const bsvi_program_desc& d, const EmitOptions& o) : d_(d), diag_(o.diag), fold_(o.fold), trim_(o.trim) {
         keep_eps_ = d.n_noise <= kKeepEpsRows;
         // (trim_) constant entries that repeat an earlier one — same value bits, transform, a and b: the table publishes the same
         // three numbers for both, every iteration — are read at the earlier one's index (SPEC_SAME, spec_prelude.h)
@@ -109,7 +126,7 @@ public:
         // adjoints only — same schedule as above — in the reverse sweep.  With every sink finished in the forward sweep the
         // adjoint of every latent is live across the turn: T = 200 is 2 x 201 long-lived registers of 512, and the register
         // allocator's eviction search alone took 23 s of a 29 s compile (-ftime-report).
-        two_pass_ = reschedule_ && d.estimator == BSVI_EST_BLACKBOX && !(getenv("BSVI_SPEC_TWO_PASS") && getenv("BSVI_SPEC_TWO_PASS")[0] == '0');
+        two_pass_ = reschedule_ && d.estimator == BSVI_EST_BLACKBOX && o.two_pass;
         if (d.estimator == BSVI_EST_BLACKBOX && !two_pass_) reschedule_ = false;
         du_total_.assign(d.n_uniform_grad, 0);
         du_seen_.assign(d.n_uniform_grad, 0);
@@ -678,18 +695,37 @@ struct Variant {
 //   ONE  a shard of up to max_threads / 64 waves runs as ONE workgroup — no grid reduction, the training loop can stay
 //        in the kernel;
 //   MANY larger shards: 256-thread workgroups, sized so that two fit a CU's LDS, each walking several sample chunks.
-enum { GEOM_ONE = 0, GEOM_MANY = 1 };
+// (GEOM_ONE, GEOM_MANY: spec_select.h)
 struct Geom { uint32_t max_threads = 0, lds_bytes = 0; };
+
+// The variant table: how each kernel variant (VariantId, spec_select.h) is built from a generated base source — the defines put in
+// front of it, one of them under a condition — and whether it runs the training loop, and so gets a twin with the minibatch gather
+// phase.  (Kernels of their own: the extra roles cost the plain loop 3 % when they are merely compiled in.)
+enum Form { FORM_LEAN, FORM_DIAGNOSTIC, FORM_PREVIOUS };     // of a generated body; previous: lean, as it was before the lean chain
+enum Base { BASE_ONE = 0, BASE_ONE_DIAG, BASE_MANY, BASE_MANY_DIAG, BASE_ONE_PREVIOUS, BASE_COUNT };
+constexpr struct { int geometry; Form form; } kBases[BASE_COUNT] = {
+    {GEOM_ONE, FORM_LEAN}, {GEOM_ONE, FORM_DIAGNOSTIC}, {GEOM_MANY, FORM_LEAN}, {GEOM_MANY, FORM_DIAGNOSTIC}, {GEOM_ONE, FORM_PREVIOUS}};
+enum When { ALWAYS, WHEN_TAIL, WHEN_DRAW_WAVE_OK };     // BSVI_SPEC_TAIL at creation; Spec::draw_wave_ok
+struct VariantRow { const char* name; Base base; const char* defines; When when; const char* define_when; bool loop; };
+constexpr VariantRow kVariants[V_COUNT] = {
+    /* V_ONE             */ {"one", BASE_ONE, "", ALWAYS, "", true},
+    /* V_ONE_DIAG        */ {"one-diag", BASE_ONE_DIAG, "", ALWAYS, "", false},
+    /* V_MANY            */ {"many", BASE_MANY, "", ALWAYS, "", true},
+    /* V_MANY_DIAG       */ {"many-diag", BASE_MANY_DIAG, "", ALWAYS, "", false},
+    /* V_DRAW_WAVE       */ {"draw-wave", BASE_ONE, "#define SPEC_WITH_DRAW_WAVE 1\n", ALWAYS, "", true},
+    // (owners in one wave: the wave exchanges; otherwise every thread exchanges its own parameters' entries)
+    /* V_EXCHANGE        */ {"exchange", BASE_ONE, "#define SPEC_WITH_EXCHANGE 1\n", WHEN_DRAW_WAVE_OK, "#define SPEC_WITH_DRAW_WAVE 1\n", false},
+    /* V_OWNERS          */ {"owners", BASE_ONE, "#define SPEC_WITH_DRAW_WAVE 1\n#define SPEC_WITH_DRAW_OWNERS 1\n#define SPEC_LEAN_CHAIN 1\n",
+                             WHEN_TAIL, "#define SPEC_LEAN_TAIL 1\n", true},
+    /* V_OWNERS_PREVIOUS */ {"owners-previous", BASE_ONE_PREVIOUS, "#define SPEC_WITH_DRAW_WAVE 1\n#define SPEC_WITH_DRAW_OWNERS 1\n", ALWAYS, "", true},
+};
 
 struct Spec {
     uint32_t n_params = 0, n_uniform = 0, n_ugrad = 0, n_obs = 0, n_noise = 0;
     uint32_t n_pos = 0;                                   // positions of the transpose tile (>= n_ugrad)
     Geom geom[2];
     std::vector<uint32_t> pu_ptr_host, pu_pos_host, pu_idx_host;   // CSR theta -> (position, uniform entry)
-    Variant variant[8];                                   // [geometry][0 lean, 1 diagnostic]; 4: lean one-workgroup kernel with the draw wave;
-                                                          // 5: the same with the cross-rank exchange inside the training loop (spec_main.h);
-                                                          // 6: 4 with the owners' epilogue on a draw wave of the draw service;
-                                                          // 7: 6 as it was before the lean chain (BSVI_SPEC_LEAN_CHAIN=0: comparisons)
+    Variant variant[V_COUNT];                             // by VariantId (spec_select.h), built from kVariants
     bool exchange_ok = false;                             // every parameter has its owner in one wave: the in-loop exchange serves
     void* dev = nullptr;                                  // [tickets: 256 B][pu_ptr][pu_pos][pu_idx]
     unsigned int* tickets = nullptr;
@@ -699,10 +735,10 @@ struct Spec {
     uint32_t n_cus = 256;
     bool draw_wave_ok = false;                            // the in-kernel loop may be given a wave that draws for the owners' wave
     // minibatched observations inside the training loop (set_minibatches): the sources' geometry, the defines it becomes, and
-    // the loop variants with the gather phase compiled in — variant v's source behind the defines (0, 2, 4, 6, 7 only)
+    // the loop variants with the gather phase compiled in — variant v's source behind the defines (kVariants[v].loop only)
     std::vector<uint32_t> mb_geometry;                    // n x {obs_offset, batch, row_floats, dataset_size, group}
     std::string mb_defines;
-    Variant mb_variant[8];
+    Variant mb_variant[V_COUNT];
     bool mb_launch_prepared = false;
     uint32_t launch_seq = 0;
     std::mutex mu;
@@ -716,8 +752,8 @@ static uint32_t many_waves() {
     return w;
 }
 static bool tiled(uint32_t n_pos, int geom) {     // SPEC_TILE (spec_prelude.h, SPEC_DU)
-    static const bool many_tile = [] { const char* e = getenv("BSVI_SPEC_MANY_TILE"); return !(e && e[0] == '0'); }();
-    if (geom == 1 /* GEOM_MANY */ && (!many_tile || many_waves() > 2)) return false;
+    static const bool many_tile = switch_on("BSVI_SPEC_MANY_TILE");
+    if (geom == GEOM_MANY && (!many_tile || many_waves() > 2)) return false;
     return n_pos <= 64;
 }
 static uint32_t lds_floats(uint32_t n_params, uint32_t n_uniform, uint32_t n_obs, uint32_t n_pos, uint32_t max_threads, int geom) {
@@ -730,13 +766,29 @@ static uint32_t lds_floats(uint32_t n_params, uint32_t n_uniform, uint32_t n_obs
     return u_pad + 2 * nu_pad + W * ws_pad + (2 * W + 8) + 5 * np_pad + tab + own + scr + (tiled(n_pos, geom) ? W * 64 * 68 : 0);
 }
 
+// the switches read when a program is created (comparisons and measurements: each generates the sources as they were)
+struct CreateSwitches {
+    bool lean_body = switch_on("BSVI_SPEC_LEAN_BODY");              // literal constants folded: what every variant gets
+    bool want_previous = getenv("BSVI_SPEC_LEAN_CHAIN") != nullptr; // set, to either value: V_OWNERS_PREVIOUS exists — nobody else pays the third pass
+    bool tail = switch_on("BSVI_SPEC_TAIL");                        // the tail of the owners' chain (V_OWNERS only; spec_main.h SPEC_LEAN_TAIL):
+                                                                    // the loss bookkeeping beside the next bodies, plain SGD as a step of its own
+    bool trim = switch_on("BSVI_SPEC_TRIM");                        // the trimmed kernels (every variant; spec_prelude.h SPEC_TRIM): repeated constant entries
+                                                                    // read once, no zero-add in the reverse step of an entropy-only node, idle lanes masked in the flush
+    bool two_pass = switch_on("BSVI_SPEC_TWO_PASS");                // long BlackBox programs run their sinks twice (Emitter)
+    const char* slp = getenv("BSVI_JIT_SLP");                       // 1 / 0 forces the SLP vectorizer on / off for every program
+    const char* regalloc = getenv("BSVI_JIT_REGALLOC");             // greedy / basic forces one register allocator for every program
+};
+
 Spec* create(const bsvi_program_desc& d, std::string& why) {
     if (!d.n_code) { why = "empty program"; return nullptr; }
+    const CreateSwitches sw;
+    EmitOptions plain;
+    plain.two_pass = sw.two_pass;
     Spec* s = new Spec();
     s->n_params = d.n_params; s->n_uniform = d.n_uniform; s->n_ugrad = d.n_uniform_grad; s->n_obs = d.n_obs; s->n_noise = d.n_noise;
     {
         // the positions (and with them the CSR map theta -> positions) do not depend on the geometry
-        Emitter E(d, false);
+        Emitter E(d, plain);
         if (!E.run(why)) { delete s; return nullptr; }
         const std::vector<uint32_t>& order = E.order();
         s->n_pos = (uint32_t)order.size();
@@ -770,89 +822,70 @@ Spec* create(const bsvi_program_desc& d, std::string& why) {
     // the most table entries any parameter owns: the owners' code is compiled for that many (spec_main.h, SPEC_OWN_ENTRIES)
     uint32_t own_entries = 1;
     for (uint32_t i = 0; i < d.n_params; ++i) own_entries = std::max(own_entries, std::min(2u, s->pu_ptr_host[i + 1] - s->pu_ptr_host[i]));
-    // The lean body (literal constants folded) is what every variant gets; BSVI_SPEC_LEAN_BODY=0, read when the program is
-    // created, generates the body as it was (measurements).
-    const char* const lean_env = getenv("BSVI_SPEC_LEAN_BODY");
-    const bool lean_body = !(lean_env && lean_env[0] == '0');
-    // The lean one-workgroup source as it was before the lean chain (variant 7) exists for comparisons only: it is generated
-    // when BSVI_SPEC_LEAN_CHAIN is set, to either value, while the program is created — nobody else pays the third pass.
-    const bool want_previous = getenv("BSVI_SPEC_LEAN_CHAIN") != nullptr;
-    std::string previous;
-    // The tail of the owners' chain (variant 6 only; spec_main.h SPEC_LEAN_TAIL): the loss bookkeeping beside the next bodies,
-    // plain SGD as a step of its own.  BSVI_SPEC_TAIL=0, read when the program is created, generates variant 6 as it was
-    // (comparisons).
-    const char* const tail_env = getenv("BSVI_SPEC_TAIL");
-    const bool tail = !(tail_env && tail_env[0] == '0');
-    // The trimmed kernels (every variant; spec_prelude.h SPEC_TRIM): repeated constant entries read once, no zero-add in the
-    // reverse step of an entropy-only node, idle lanes masked in the tile's flush instead of in every store.  BSVI_SPEC_TRIM=0,
-    // read when the program is created, generates the sources as they were (comparisons).
-    const char* const trim_env = getenv("BSVI_SPEC_TRIM");
-    const bool trim = !(trim_env && trim_env[0] == '0');
-    for (int gi = 0; gi < 2; ++gi) {
+    // a base source: the generated body of one geometry in one form, in the frame of spec_prelude.h / spec_main.h
+    auto generate = [&](int gi, Form form, std::string& src) {
         const Geom& G = s->geom[gi];
-        for (int v = 0; v < (gi == GEOM_ONE && want_previous ? 3 : 2); ++v) {
-            const bool old = v == 2;       // (v == 2: variant 0 once more, in its previous form)
-            const bool lean = lean_body && !old;
-            Emitter E(d, v == 1, lean, trim);
-            if (!E.run(why)) { delete s; return nullptr; }
-            std::string src;
-            src += "// generated by libbsvi (specialize.cpp) from a model program: do not edit\n";
-            src += "#define BSVI_SPECIALIZED 1\n";
-            if (trim) src += "#define SPEC_TRIM 1\n";
-            // long BlackBox programs: no SLP vectorizer.  gfx950 has packed f32 arithmetic, so the vectorizer pairs the
-            // isomorphic terms of DISTANT records of the unrolled stream into <2 x float> operations placed at the later one
-            // — every such pair holds the earlier record's operands across the records in between (T = 200: 2 158 spilled
-            // registers and 52 s of compile time with it, 231 and 29 s without; the rest went with the two-pass sinks: 12
-            // and 9 s; 199 -> 90 us per iteration at 1 024 samples).  Long Pathwise programs keep it: their deferred sinks
-            // leave it nothing distant to pair (7 spills with, 0 without, and 69.7 against 70.9 us).
-            // (BSVI_JIT_SLP=1 / 0 forces it on / off for every program: measurements)
-            const char* const slp = getenv("BSVI_JIT_SLP");
-            if (slp ? slp[0] == '0' : (d.n_code > kFenceAboveCode && d.estimator == BSVI_EST_BLACKBOX))
-                src += std::string(kJitOptionMark) + "-fno-slp-vectorize\n";
-            // very long programs: the greedy allocator's time grows much faster than the unrolled stream once the register file is
-            // full (a Gaussian process over 100 inputs, 414 instructions: 15 s, of which 9 s are "Greedy Register Allocator"; over 200
-            // inputs, 814 instructions: 150 s and 690 spilled registers).  The basic allocator takes 16 s there (1 875 spills —
-            // beside the term's batched factorisation the program is a small part of such an iteration); same arithmetic.
-            // (BSVI_JIT_REGALLOC=greedy / basic forces one for every program)
-            const char* const ra = getenv("BSVI_JIT_REGALLOC");
-            if (ra ? ra[0] == 'b' : d.n_code > kBasicRegallocAboveCode)
-                src += std::string(kJitOptionMark) + "-mllvm\n" + kJitOptionMark + "-vgpr-regalloc=basic\n";
-            src += fmt("#define SPEC_N_PARAMS %u\n#define SPEC_N_UNIFORM %u\n#define SPEC_N_UGRAD %u\n#define SPEC_N_OBS %u\n#define SPEC_N_NOISE %u\n",
-                       d.n_params, d.n_uniform, d.n_uniform_grad, d.n_obs, d.n_noise);
-            src += fmt("#define SPEC_N_POS %u\n", s->n_pos);
-            src += fmt("#define SPEC_ESTIMATOR %u\n#define SPEC_MAX_THREADS %u\n#define SPEC_DIAG %d\n", d.estimator, G.max_threads, v == 1 ? 1 : 0);
-            src += fmt("#define SPEC_ACCUMULATE_CHUNKS %d\n#define SPEC_TILE %d\n", gi == GEOM_MANY ? 1 : 0, tiled(s->n_pos, gi) ? 1 : 0);
-            if (gi == GEOM_MANY && many_waves() > 2) src += fmt("#define SPEC_BOUND_THREADS %u\n", 256u * many_waves());
-            src += fmt("#define SPEC_KEEP_NOISE %u\n", E.keeps_noise() ? d.n_noise : 0u);
-            // (all parameters "fast": the epilogue's generic loop over the LDS working copy is compiled out)
-            src += fmt("#define SPEC_GENERIC_OWNERS %d\n", all_fast ? 0 : 1);
-            // (the out-of-line transforms — exp, log, tanh, sqrt, square — are calls: programs without them compile none)
-            src += fmt("#define SPEC_RARE_TRANSFORMS %d\n#define SPEC_UT_MASK 0x%xu\n", rare_transforms ? 1 : 0, ut_mask);
-            if (!old) src += fmt("#define SPEC_OWN_ENTRIES %u\n", own_entries);
-            src += "#include \"spec_prelude.h\"\n";
-            src += "namespace bsvi {\n";
-            src += "__device__ __forceinline__ void spec_draw(const SpecBody& A, const SpecLane& T, SpecNoise& Z) {\n";
-            src += "    (void)A; (void)T; (void)Z;\n";
-            src += E.draw();
-            src += "}\n";
-            src += "__device__ __forceinline__ void spec_body(const SpecBody& A, SpecLane& T, const SpecNoise& Z, float* WSw) {\n";
-            src += "    (void)Z;\n";
-            if (v == 1) src += "    const float* const noise = A.noise;\n";
-            if (old) { previous = std::move(src); previous += E.declarations() + E.body() + "}\n}  // namespace bsvi\n#include \"spec_main.h\"\n"; continue; }
-            src += E.declarations();
-            src += E.body();
-            src += "}\n}  // namespace bsvi\n";
-            src += "#include \"spec_main.h\"\n";
-            s->variant[2 * gi + v].src = std::move(src);
-        }
+        const bool diag = form == FORM_DIAGNOSTIC, old = form == FORM_PREVIOUS;
+        EmitOptions o = plain;
+        o.diag = diag; o.fold = sw.lean_body && !old; o.trim = sw.trim;
+        Emitter E(d, o);
+        if (!E.run(why)) return false;
+        src += "// generated by libbsvi (specialize.cpp) from a model program: do not edit\n";
+        src += "#define BSVI_SPECIALIZED 1\n";
+        if (sw.trim) src += "#define SPEC_TRIM 1\n";
+        // long BlackBox programs: no SLP vectorizer.  gfx950 has packed f32 arithmetic, so the vectorizer pairs the
+        // isomorphic terms of DISTANT records of the unrolled stream into <2 x float> operations placed at the later one
+        // — every such pair holds the earlier record's operands across the records in between (T = 200: 2 158 spilled
+        // registers and 52 s of compile time with it, 231 and 29 s without; the rest went with the two-pass sinks: 12
+        // and 9 s; 199 -> 90 us per iteration at 1 024 samples).  Long Pathwise programs keep it: their deferred sinks
+        // leave it nothing distant to pair (7 spills with, 0 without, and 69.7 against 70.9 us).
+        if (sw.slp ? sw.slp[0] == '0' : (d.n_code > kFenceAboveCode && d.estimator == BSVI_EST_BLACKBOX))
+            src += std::string(kJitOptionMark) + "-fno-slp-vectorize\n";
+        // very long programs: the greedy allocator's time grows much faster than the unrolled stream once the register file is
+        // full (a Gaussian process over 100 inputs, 414 instructions: 15 s, of which 9 s are "Greedy Register Allocator"; over 200
+        // inputs, 814 instructions: 150 s and 690 spilled registers).  The basic allocator takes 16 s there (1 875 spills —
+        // beside the term's batched factorisation the program is a small part of such an iteration); same arithmetic.
+        if (sw.regalloc ? sw.regalloc[0] == 'b' : d.n_code > kBasicRegallocAboveCode)
+            src += std::string(kJitOptionMark) + "-mllvm\n" + kJitOptionMark + "-vgpr-regalloc=basic\n";
+        src += fmt("#define SPEC_N_PARAMS %u\n#define SPEC_N_UNIFORM %u\n#define SPEC_N_UGRAD %u\n#define SPEC_N_OBS %u\n#define SPEC_N_NOISE %u\n",
+                   d.n_params, d.n_uniform, d.n_uniform_grad, d.n_obs, d.n_noise);
+        src += fmt("#define SPEC_N_POS %u\n", s->n_pos);
+        src += fmt("#define SPEC_ESTIMATOR %u\n#define SPEC_MAX_THREADS %u\n#define SPEC_DIAG %d\n", d.estimator, G.max_threads, diag ? 1 : 0);
+        src += fmt("#define SPEC_ACCUMULATE_CHUNKS %d\n#define SPEC_TILE %d\n", gi == GEOM_MANY ? 1 : 0, tiled(s->n_pos, gi) ? 1 : 0);
+        if (gi == GEOM_MANY && many_waves() > 2) src += fmt("#define SPEC_BOUND_THREADS %u\n", 256u * many_waves());
+        src += fmt("#define SPEC_KEEP_NOISE %u\n", E.keeps_noise() ? d.n_noise : 0u);
+        // (all parameters "fast": the epilogue's generic loop over the LDS working copy is compiled out)
+        src += fmt("#define SPEC_GENERIC_OWNERS %d\n", all_fast ? 0 : 1);
+        // (the out-of-line transforms — exp, log, tanh, sqrt, square — are calls: programs without them compile none)
+        src += fmt("#define SPEC_RARE_TRANSFORMS %d\n#define SPEC_UT_MASK 0x%xu\n", rare_transforms ? 1 : 0, ut_mask);
+        if (!old) src += fmt("#define SPEC_OWN_ENTRIES %u\n", own_entries);
+        src += "#include \"spec_prelude.h\"\n";
+        src += "namespace bsvi {\n";
+        src += "__device__ __forceinline__ void spec_draw(const SpecBody& A, const SpecLane& T, SpecNoise& Z) {\n";
+        src += "    (void)A; (void)T; (void)Z;\n";
+        src += E.draw();
+        src += "}\n";
+        src += "__device__ __forceinline__ void spec_body(const SpecBody& A, SpecLane& T, const SpecNoise& Z, float* WSw) {\n";
+        src += "    (void)Z;\n";
+        if (diag) src += "    const float* const noise = A.noise;\n";
+        src += E.declarations();
+        src += E.body();
+        src += "}\n}  // namespace bsvi\n";
+        src += "#include \"spec_main.h\"\n";
+        return true;
+    };
+    std::string base[BASE_COUNT];
+    for (int b = 0; b < BASE_COUNT; ++b) {
+        if (kBases[b].form == FORM_PREVIOUS && !sw.want_previous) continue;
+        if (!generate(kBases[b].geometry, kBases[b].form, base[b])) { delete s; return nullptr; }
     }
-    // (a kernel of its own: the extra roles cost the plain loop 3 % when they are merely compiled in)
-    s->variant[4].src = "#define SPEC_WITH_DRAW_WAVE 1\n" + s->variant[0].src;
-    s->variant[6].src = std::string("#define SPEC_WITH_DRAW_WAVE 1\n#define SPEC_WITH_DRAW_OWNERS 1\n#define SPEC_LEAN_CHAIN 1\n")
-                        + (tail ? "#define SPEC_LEAN_TAIL 1\n" : "") + s->variant[0].src;
-    if (want_previous) s->variant[7].src = "#define SPEC_WITH_DRAW_WAVE 1\n#define SPEC_WITH_DRAW_OWNERS 1\n" + previous;
-    s->exchange_ok = true;       // (owners in one wave: the wave exchanges; otherwise every thread exchanges its own parameters' entries)
-    s->variant[5].src = std::string("#define SPEC_WITH_EXCHANGE 1\n") + (s->draw_wave_ok ? "#define SPEC_WITH_DRAW_WAVE 1\n" : "") + s->variant[0].src;
+    s->exchange_ok = true;
+    for (int v = 0; v < V_COUNT; ++v) {
+        const VariantRow& row = kVariants[v];
+        if (base[row.base].empty()) continue;
+        const bool when = row.when == ALWAYS || (row.when == WHEN_TAIL ? sw.tail : s->draw_wave_ok);
+        s->variant[v].src = std::string(row.defines) + (when ? row.define_when : "") + base[row.base];
+    }
     return s;
 }
 
@@ -893,7 +926,6 @@ static int minibatch_defines(uint32_t n_obs, uint32_t n, const uint32_t* g, std:
     out += "#define SPEC_MB_SOURCES(F)" + list + "\n";
     return BSVI_OK;
 }
-static bool mb_loop_variant(int v) { return v == 0 || v == 2 || v == 4 || v == 6 || v == 7; }
 
 int set_minibatches(Spec* s, uint32_t n, const uint32_t* geometry) {
     std::lock_guard<std::mutex> lock(s->mu);
@@ -903,13 +935,13 @@ int set_minibatches(Spec* s, uint32_t n, const uint32_t* geometry) {
     if (rc) return rc;
     s->mb_geometry.assign(geometry, geometry + 5 * (size_t)n);
     s->mb_defines = defines;
-    for (int v = 0; v < 8; ++v) s->mb_variant[v].src = (mb_loop_variant(v) && !s->variant[v].src.empty()) ? defines + s->variant[v].src : std::string();
+    for (int v = 0; v < V_COUNT; ++v) s->mb_variant[v].src = (kVariants[v].loop && !s->variant[v].src.empty()) ? defines + s->variant[v].src : std::string();
     return BSVI_OK;
 }
 // the generated translation unit of loop variant v with the gather phase (empty: the variant does not run the loop)
 const std::string& source_minibatch(const Spec* s, int variant) {
     static const std::string none;
-    return (variant >= 0 && variant < 8) ? s->mb_variant[variant].src : none;
+    return (variant >= 0 && variant < V_COUNT) ? s->mb_variant[variant].src : none;
 }
 uint32_t minibatch_sources(const Spec* s) { return (uint32_t)(s->mb_geometry.size() / 5); }
 
@@ -943,8 +975,8 @@ int upload(Spec* s) {
     return BSVI_OK;
 }
 
-// variant: 0 training kernel, 1 diagnostic kernel of the one-workgroup geometry; 2, 3 the same of the many-workgroup one
-const std::string& source(const Spec* s, int variant) { return s->variant[(variant >= 4 && variant <= 7) ? variant : (variant & 3)].src; }
+// variant: a VariantId; anything else is taken by its two low bits — one of the four base kernels
+const std::string& source(const Spec* s, int variant) { return s->variant[(variant >= V_DRAW_WAVE && variant < V_COUNT) ? variant : (variant & 3)].src; }
 
 // ---------------------------------------------------------------------------------------------------------------
 //  hiprtc
@@ -1014,10 +1046,7 @@ static void feed(Hash128& h, const void* data, size_t n) {
 }
 static void feed(Hash128& h, const std::string& s) { const uint64_t n = s.size(); feed(h, &n, 8); feed(h, s.data(), s.size()); }
 
-static bool enabled() {
-    const char* e = getenv("BSVI_JIT_CACHE");
-    return !(e && e[0] == '0');
-}
+static bool enabled() { return switch_on("BSVI_JIT_CACHE"); }
 
 static std::string directory() {
     if (const char* d = getenv("BSVI_CACHE_DIR")) if (d[0]) return d;
@@ -1183,8 +1212,6 @@ int last_variant() { return t_last_variant; }
 std::string cache_directory() { return disk_cache::enabled() ? disk_cache::directory() : std::string(); }
 std::string compiler_identity() { return disk_cache::compiler_identity(); }
 
-static int ensure_compiled(Variant& V);
-static int ensure_compiled(Spec* s, int v) { return ensure_compiled(s->variant[v]); }
 static int ensure_compiled(Variant& V) {
     if (V.fn) return BSVI_OK;
     if (V.failed) return BSVI_ERR_UNSUPPORTED;
@@ -1208,84 +1235,41 @@ static int ensure_compiled(Variant& V) {
 // ---------------------------------------------------------------------------------------------------------------
 //  launch
 // ---------------------------------------------------------------------------------------------------------------
-struct Geo { uint32_t blocks, threads; int geom; bool draw_wave = false; uint32_t extra_waves = 0; bool draw_owners = false; };
-// The in-kernel loop is given one wave more than the samples need: it carries no samples and draws the next iteration's
-// normals of the owners' wave, whose chain — draw, body, sums, epilogue — is what an iteration takes (spec_main.h).
-static bool draw_wave() {
-    const char* e = getenv("BSVI_SPEC_DRAW_WAVE");        // (read per call: the tests switch it within a process)
-    return !(e && e[0] == '0');
-}
-static bool draw_service() {
-    const char* e = getenv("BSVI_SPEC_DRAW_SERVICE");     // (read per call: the tests switch it within a process)
-    return !(e && e[0] == '0');
-}
-// The draw service's owners' epilogue on a draw wave (spec_main.h, SPEC_DRAW_OWNERS; BSVI_SPEC_OWNER_WAVE=0: on sample wave 1 as before)
-static bool owner_wave() {
-    const char* e = getenv("BSVI_SPEC_OWNER_WAVE");       // (read per call: the tests switch it within a process)
-    return !(e && e[0] == '0');
-}
-// The owners' wave with the lean chain (spec_main.h, SPEC_LEAN_CHAIN) and the lean body; BSVI_SPEC_LEAN_CHAIN=0: the kernel as it
-// was before both — same draws, same arithmetic, same bits (its source exists when the variable was set at the program's creation)
-static bool lean_chain() {
-    const char* e = getenv("BSVI_SPEC_LEAN_CHAIN");       // (read per call: the tests switch it within a process)
-    return !(e && e[0] == '0');
-}
-static Geo geo(const Spec* s, uint32_t n_local, int mode = MODE_SUMS, bool exchange = false) {
-    const uint32_t waves = (n_local + 63) / 64;
-    if (waves <= s->geom[GEOM_ONE].max_threads / 64) {
-        // (up to four sample waves — one per SIMD: beyond that two of them share a SIMD and their draws set the pace, not the owners' chain)
-        const bool extra = mode == MODE_LOOP && s->draw_wave_ok && draw_wave() && waves <= 4 && waves + 1 <= s->geom[GEOM_ONE].max_threads / 64
-                           && !s->variant[exchange ? 5 : 4].failed;
-        // four or five sample waves: four / three draw waves draw for ALL of them (spec_main.h, the draw service; BSVI_SPEC_DRAW_SERVICE=0:
-        // the single draw wave up to four sample waves, none at five); the sets are handed over in the draw waves' transpose tiles.
-        // (Three sample waves: 3.89 us with the single draw wave, 3.94 with the service; one and two: the single draw wave.)
-        const uint32_t n_service = waves == 4 ? 4u : 3u;
-        const bool service = mode == MODE_LOOP && s->draw_wave_ok && draw_wave() && draw_service() && waves >= 4 && waves <= 5
-                             && waves + n_service <= s->geom[GEOM_ONE].max_threads / 64 && (size_t)s->n_noise * 64u * waves <= (size_t)n_service * 64u * 68u
-                             && !s->variant[exchange ? 5 : 4].failed;
-        const uint32_t more = service ? n_service : extra ? 1u : 0u;
-        // (the owners on a draw wave: one more buffer, for the set the owners' wave draws — spec_main.h, SPEC_DRAW_OWNERS)
-        // (and a full workgroup: the lean epilogue adds the rows of all waves the kernel is compiled for)
-        const bool owners = service && (size_t)s->n_noise * 64u * (waves + 1u) <= (size_t)n_service * 64u * 68u
-                            && waves + n_service == s->geom[GEOM_ONE].max_threads / 64;
-        return Geo{1, (waves + more) * 64, GEOM_ONE, more != 0u, more, owners};
-    }
-    // many samples: 256-thread workgroups (one wave per SIMD), two per CU at most; beyond that every workgroup walks
-    // several chunks of 256 samples
-    const uint32_t threads = s->geom[GEOM_MANY].max_threads;
-    uint32_t blocks = (n_local + threads - 1) / threads;
-    uint32_t per_cu = many_waves();                                                            // (registers: see many_waves)
-    while (per_cu > 1u && s->geom[GEOM_MANY].lds_bytes * per_cu > 160u * 1024u) --per_cu;
-    if (blocks > per_cu * s->n_cus) blocks = per_cu * s->n_cus;
-    return Geo{blocks, threads, GEOM_MANY};
+static_assert(SELECT_MODE_LOOP == MODE_LOOP, "spec_select.h");
+// The selection (spec_select.h) of a launch, or of a query that knows only the sample count and the mode.  The switches are read
+// at every call: the tests flip them within a process.
+static Selection choose(const Spec* s, uint32_t n_local, int mode, bool diagnostic = false, bool exchange = false, bool gather = false) {
+    SelectInput in;
+    in.max_waves_one = s->geom[GEOM_ONE].max_threads / 64;
+    in.many_threads = s->geom[GEOM_MANY].max_threads;
+    in.many_per_cu = many_waves();                                                              // (registers: see many_waves)
+    while (in.many_per_cu > 1u && s->geom[GEOM_MANY].lds_bytes * in.many_per_cu > 160u * 1024u) --in.many_per_cu;
+    in.n_cus = s->n_cus;
+    in.draw_wave_ok = s->draw_wave_ok; in.n_noise = s->n_noise; in.exchange_ok = s->exchange_ok;
+    in.has_previous = !s->variant[V_OWNERS_PREVIOUS].src.empty();
+    for (int v = 0; v < V_COUNT; ++v) in.failed[v] = s->variant[v].failed;
+    in.n_local = n_local; in.mode = mode; in.diagnostic = diagnostic; in.exchange = exchange; in.gather = gather;
+    in.jit = switch_on("BSVI_JIT");
+    in.loop_many = switch_on("BSVI_SPEC_LOOP_MANY");
+    in.draw_wave = switch_on("BSVI_SPEC_DRAW_WAVE");
+    in.draw_service = switch_on("BSVI_SPEC_DRAW_SERVICE");
+    in.owner_wave = switch_on("BSVI_SPEC_OWNER_WAVE");
+    in.lean_chain = switch_on("BSVI_SPEC_LEAN_CHAIN");
+    return select(in);
 }
 
 void geometry(const Spec* s, uint32_t n_local, int mode, uint32_t* n_blocks, uint32_t* n_threads, uint32_t* lds_bytes) {
-    const Geo g = geo(s, n_local, mode);
+    const Selection g = choose(s, n_local, mode);
     if (n_blocks) *n_blocks = g.blocks;
     if (n_threads) *n_threads = g.threads;
-    if (lds_bytes) *lds_bytes = s->geom[g.geom].lds_bytes;
+    if (lds_bytes) *lds_bytes = s->geom[g.geometry].lds_bytes;
 }
 
 size_t workspace_bytes(const Spec* s, uint32_t n_local) {
-    const Geo g = geo(s, n_local);
-    return ((size_t)g.blocks * (2 + s->n_pos) * 4 + 255) / 256 * 256 + 256;
+    return ((size_t)choose(s, n_local, MODE_SUMS).blocks * (2 + s->n_pos) * 4 + 255) / 256 * 256 + 256;
 }
 
-bool applies(const Spec* s, uint32_t n_local, int mode) {
-    if (!s || !n_local) return false;
-    const char* e = getenv("BSVI_JIT");
-    if (e && e[0] == '0') return false;
-    const Geo g = geo(s, n_local);
-    if (s->variant[2 * g.geom].failed || s->variant[2 * g.geom + 1].failed) return false;
-    // several workgroups in loop mode: workgroup 0 owns the iteration, the others wait on its generation number (spec_main.h);
-    // every workgroup must be resident — geo() never asks for more than fit the chip (BSVI_SPEC_LOOP_MANY=0: launch per iteration)
-    if (mode == MODE_LOOP && g.blocks != 1) {
-        const char* m = getenv("BSVI_SPEC_LOOP_MANY");
-        return !(m && m[0] == '0');
-    }
-    return true;
-}
+bool applies(const Spec* s, uint32_t n_local, int mode) { return s && choose(s, n_local, mode).applies; }
 
 int launch(Spec* s, const bsvi_program* p, const Launch& L) {
     const bsvi_elbo_args* a = L.a;
@@ -1293,43 +1277,30 @@ int launch(Spec* s, const bsvi_program* p, const Launch& L) {
     if (!a->obs_dev && s->n_obs) return bsvi_fail(BSVI_ERR_INVALID, "obs_dev is null");
     if (!a->out_dev) return bsvi_fail(BSVI_ERR_INVALID, "out_dev is null");
     if (!a->n_samples_local || !a->n_samples_global) return bsvi_fail(BSVI_ERR_INVALID, "zero samples");
-    Geo g = geo(s, a->n_samples_local, L.mode, L.xchg != nullptr);
-    int v = 2 * g.geom + ((a->noise_dev || a->samples_out_dev || a->noise_out_dev || a->fvalue_out_dev || a->f_weight_dev || a->q_weight_dev) ? 1 : 0);
-    if (L.xchg && !(L.mode == MODE_LOOP && g.blocks == 1 && v == 0 && s->exchange_ok))
-        return bsvi_fail(BSVI_ERR_UNSUPPORTED, "the in-loop exchange serves the one-workgroup training loop with Philox noise and no per-sample outputs");
+    const bool diagnostic = a->noise_dev || a->samples_out_dev || a->noise_out_dev || a->fvalue_out_dev || a->f_weight_dev || a->q_weight_dev;
     const bool gather = L.datasets != nullptr;
+    const Selection g = choose(s, a->n_samples_local, L.mode, diagnostic, L.xchg != nullptr, gather);
+    if (g.status == SELECT_NO_EXCHANGE || g.status == SELECT_NO_GATHER) return bsvi_fail(BSVI_ERR_UNSUPPORTED, g.reason);
     if (gather) {
-        // the loop with the gather phase: Philox noise, no per-sample outputs, one rank — everything else trains launch by launch
-        if (L.mode != MODE_LOOP || v != 2 * g.geom || L.xchg)
-            return bsvi_fail(BSVI_ERR_UNSUPPORTED, "the in-kernel minibatch gather serves the training loop with Philox noise, no per-sample outputs and one rank");
         if (s->mb_geometry.empty()) return bsvi_fail(BSVI_ERR_UNSUPPORTED, "the program carries no minibatch geometry (bsvi_program_set_minibatches)");
         for (size_t i = 0; i < s->mb_geometry.size() / 5; ++i)
             if (!L.datasets[i]) return bsvi_fail(BSVI_ERR_INVALID, "a dataset pointer is null");
     }
     Variant* const table = gather ? s->mb_variant : s->variant;
+    int v = g.variant;
+    uint32_t blocks = g.blocks, threads = g.threads;
     uint32_t seq;
     {
         std::lock_guard<std::mutex> lock(s->mu);
         if (gather) s->mb_launch_prepared = true;
-        if (L.xchg) {
-            const int rc5 = ensure_compiled(s, 5);
-            if (rc5) return rc5;
-            v = 5;
-        }
-        else if (g.draw_owners && v == 0 && owner_wave()) {
-            v = lean_chain() ? 6 : 7;
-            if (v == 7 && table[7].src.empty())
-                return bsvi_fail(BSVI_ERR_UNSUPPORTED, "BSVI_SPEC_LEAN_CHAIN=0 needs the variable set when the program is created (the previous source is generated then)");
-            const int rc6 = ensure_compiled(table[v]);
-            if (rc6) return rc6;
-        }
-        else if (g.draw_wave && v == 0 && ensure_compiled(table[4]) == BSVI_OK) v = 4;
-        else if (g.draw_wave) { g.threads -= 64 * g.extra_waves; g.draw_wave = false; }        // (diagnostic kernel, or the variant did not compile)
+        if (g.status != SELECT_OK) return bsvi_fail(BSVI_ERR_UNSUPPORTED, g.reason);
+        // (the single fallback: a draw-wave kernel that does not compile becomes the base kernel without the extra waves)
+        if (g.fallback_variant >= 0 && ensure_compiled(table[v]) != BSVI_OK) { v = g.fallback_variant; threads = g.fallback_threads; }
         const int rc = ensure_compiled(table[v]);
         if (rc) return rc;
         seq = s->launch_seq++;
     }
-    if (g.blocks > 1 && !L.workspace) return bsvi_fail(BSVI_ERR_INVALID, "workspace_dev is null");
+    if (blocks > 1 && !L.workspace) return bsvi_fail(BSVI_ERR_INVALID, "workspace_dev is null");
     SpecArgs A;
     memset(&A, 0, sizeof A);
     A.uniform = p->uniform; A.consts = p->consts;
@@ -1353,18 +1324,18 @@ int launch(Spec* s, const bsvi_program* p, const Launch& L) {
     if (L.cfg) A.cfg = *L.cfg;
     if (gather)
         for (size_t i = 0; i < s->mb_geometry.size() / 5; ++i) A.mb_data[i] = L.datasets[i];
-    if (g.blocks > 1) {
+    if (blocks > 1) {
         // every workgroup of the in-kernel loop over several workgroups must be resident (workgroup 0 waits for the others in every
         // iteration): never more than the occupancy of THIS code object allows — fewer workgroups walk more chunks each
         int per_cu = table[v].per_cu;
         if (!per_cu) {
-            if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, table[v].fn, (int)g.threads, 0) != hipSuccess || per_cu <= 0) {
+            if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, table[v].fn, (int)threads, 0) != hipSuccess || per_cu <= 0) {
                 (void)hipGetLastError();
-                per_cu = -1;                 // (no answer: geo()'s register / LDS estimate stands)
+                per_cu = -1;                 // (no answer: the selection's register / LDS estimate stands)
             }
             table[v].per_cu = per_cu;
         }
-        if (per_cu > 0 && g.blocks > (uint32_t)per_cu * s->n_cus) g.blocks = (uint32_t)per_cu * s->n_cus;
+        if (per_cu > 0 && blocks > (uint32_t)per_cu * s->n_cus) blocks = (uint32_t)per_cu * s->n_cus;
         if (L.mode == MODE_LOOP) {
             // the launch's arrival ticket and generation number start from zero (spec_main.h): a launch that gave up on a workgroup
             // leaves the generation at "over", and a straggler may have touched the ticket after workgroup 0 cleared it
@@ -1375,7 +1346,7 @@ int launch(Spec* s, const bsvi_program* p, const Launch& L) {
     }
     size_t size = sizeof A;
     void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &A, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-    const hipError_t e = hipModuleLaunchKernel(table[v].fn, g.blocks, 1, 1, g.threads, 1, 1, 0, (hipStream_t)a->stream, nullptr, config);
+    const hipError_t e = hipModuleLaunchKernel(table[v].fn, blocks, 1, 1, threads, 1, 1, 0, (hipStream_t)a->stream, nullptr, config);
     if (e != hipSuccess) return bsvi_fail(BSVI_ERR_HIP, std::string("hipModuleLaunchKernel (specialised kernel): ") + hipGetErrorString(e));
     t_last_variant = v;
     return BSVI_OK;
