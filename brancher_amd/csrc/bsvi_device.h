@@ -177,12 +177,109 @@ BSVI_SWITCH_FN float philox_noise_again(PhiloxKey G, int dist, uint32_t row) {
 
 // ---------------------------------------------------------------------------------------
 // optimizer arithmetic shared by reduce_kernel / optimizer_kernel / persistent trainer
-//   torch.optim.SGD / torch.optim.Adam single-tensor paths, per element.
-// state layout: [4][n_params] = (momentum_buffer | exp_avg, exp_avg_sq, max_exp_avg_sq, step)
+//   torch.optim.{SGD, Adam, AdamW, RMSprop, Adagrad, Adamax} single-tensor paths, per element, in f32 with the scalar
+//   factors in double.
+// state layout: [4][n_params] = (s0, s1, s2, step), per kind (include/bsvi.h, bsvi_opt_cfg):
+//   SGD      momentum_buffer, -, -              Adam, AdamW  exp_avg, exp_avg_sq, max_exp_avg_sq
+//   RMSprop  momentum_buffer, square_avg, grad_avg          Adagrad -, sum, -          Adamax  exp_avg, exp_inf, -
 // ---------------------------------------------------------------------------------------
+// The scalar factors of a step, a function of the configuration, the step count and beta^st alone — never of the gradient:
+//   Adam, AdamW  step_size = lr / (1 - beta1^step), bc2_sqrt = sqrt(1 - beta2^step)
+//   Adamax       step_size = lr / (1 - beta1^step)
+//   Adagrad      step_size = lr / (1 + (step - 1) * lr_decay)
+//   RMSprop      none (step_size = lr)
+// p1 / p2 are beta1^step / beta2^step for the kinds that have them (optimizer_has_p1 / _p2), carried unchanged otherwise.
+struct AdamBias { double p1, p2; float step_size, bc2_sqrt; };
+__device__ __forceinline__ bool optimizer_has_p1(uint32_t kind) {
+    return kind == BSVI_OPT_ADAM || kind == BSVI_OPT_ADAMW || kind == BSVI_OPT_ADAMAX;
+}
+__device__ __forceinline__ bool optimizer_has_p2(uint32_t kind) { return kind == BSVI_OPT_ADAM || kind == BSVI_OPT_ADAMW; }
+// Adam's (and AdamW's) factors of the NEXT step from the running products beta1^st, beta2^st
+__device__ __forceinline__ AdamBias optimizer_adam_bias(const bsvi_opt_cfg& cfg, double p1, double p2) {
+    AdamBias b;
+    b.p1 = p1 * (double)cfg.beta1;
+    b.p2 = p2 * (double)cfg.beta2;
+    b.step_size = (float)((double)cfg.lr / (1.0 - b.p1));
+    b.bc2_sqrt = (float)sqrt(1.0 - b.p2);
+    return b;
+}
+// the factors of the next step of the kinds beyond SGD and Adam; `st` is the step count BEFORE the step
+__device__ __forceinline__ AdamBias optimizer_more_bias(const bsvi_opt_cfg& cfg, double p1, double p2, float st) {
+    if (cfg.kind == BSVI_OPT_ADAMW) return optimizer_adam_bias(cfg, p1, p2);
+    AdamBias b = {p1, p2, cfg.lr, 1.0f};
+    if (cfg.kind == BSVI_OPT_ADAMAX) {
+        b.p1 = p1 * (double)cfg.beta1;
+        b.step_size = (float)((double)cfg.lr / (1.0 - b.p1));
+    } else if (cfg.kind == BSVI_OPT_ADAGRAD) {
+        b.step_size = (float)((double)cfg.lr / (1.0 + (double)st * (double)cfg.dampening));     // dampening = lr_decay
+    }
+    return b;
+}
+// The step of the kinds beyond SGD and Adam on those factors.  Callers reach it through a branch on the (launch-uniform)
+// kind of its own: the SGD and Adam steps execute none of it.
+__device__ __forceinline__ void optimizer_apply_more(const bsvi_opt_cfg& cfg, float& p, float& s0, float& s1, float& s2, float& st,
+                                                     float grad, const AdamBias& b) {
+    if (cfg.maximize) grad = -grad;
+    const bool first = st == 0.0f;
+    st = st + 1.0f;
+    if (cfg.kind == BSVI_OPT_ADAMW) {
+        p = p * (float)(1.0 - (double)cfg.lr * (double)cfg.weight_decay);     // decoupled: the gradient carries no decay term
+        const float m = s0 + (grad - s0) * (1.0f - cfg.beta1);
+        const float v = cfg.beta2 * s1 + (1.0f - cfg.beta2) * grad * grad;
+        s0 = m;
+        s1 = v;
+        float vhat = v;
+        if (cfg.amsgrad) {
+            vhat = fmaxf(s2, v);
+            s2 = vhat;
+        }
+        const float denom = sqrtf(vhat) / b.bc2_sqrt + cfg.eps;
+        p = p - b.step_size * (m / denom);
+        return;
+    }
+    if (cfg.weight_decay != 0.0f) grad += cfg.weight_decay * p;
+    if (cfg.kind == BSVI_OPT_RMSPROP) {                       // beta2 = alpha, amsgrad = centered
+        const float sq = cfg.beta2 * s1 + (1.0f - cfg.beta2) * grad * grad;
+        s1 = sq;
+        float avg;
+        if (cfg.amsgrad) {
+            const float ga = s2 + (grad - s2) * (1.0f - cfg.beta2);
+            s2 = ga;
+            avg = sqrtf(sq - ga * ga);                        // (a radicand below zero by rounding is NaN in torch too)
+        } else {
+            avg = sqrtf(sq);
+        }
+        avg += cfg.eps;
+        if (cfg.momentum > 0.0f) {
+            const float buf = cfg.momentum * s0 + grad / avg;
+            s0 = buf;
+            p = p - cfg.lr * buf;
+        } else {
+            p = p - cfg.lr * (grad / avg);
+        }
+    } else if (cfg.kind == BSVI_OPT_ADAGRAD) {                // dampening = lr_decay, beta1 = initial_accumulator_value
+        // torch creates the sum when the parameter is first stepped: the state arrives all zero, and a parameter held
+        // back by pretraining_iterations starts its sum at its own first step
+        const float sum = (first ? cfg.beta1 : s1) + grad * grad;
+        s1 = sum;
+        p = p - b.step_size * (grad / (sqrtf(sum) + cfg.eps));
+    } else {                                                  // BSVI_OPT_ADAMAX
+        const float m = s0 + (grad - s0) * (1.0f - cfg.beta1);
+        const float u = fmaxf(cfg.beta2 * s1, fabsf(grad) + cfg.eps);
+        s0 = m;
+        s1 = u;
+        p = p - b.step_size * (m / u);
+    }
+}
 // on values (registers): p = parameter, (s0, s1, s2, st) = its four state words
 __device__ __forceinline__ void optimizer_apply(const bsvi_opt_cfg& cfg, float& p, float& s0, float& s1, float& s2, float& st,
                                                 float grad) {
+    if (cfg.kind > BSVI_OPT_ADAM) {                           // AdamW, RMSprop, Adagrad, Adamax
+        const double p1 = optimizer_has_p1(cfg.kind) ? pow((double)cfg.beta1, (double)st) : 1.0;
+        const double p2 = optimizer_has_p2(cfg.kind) ? pow((double)cfg.beta2, (double)st) : 1.0;
+        optimizer_apply_more(cfg, p, s0, s1, s2, st, grad, optimizer_more_bias(cfg, p1, p2, st));
+        return;
+    }
     if (cfg.maximize) grad = -grad;
     const float step = st + 1.0f;
     st = step;
@@ -219,17 +316,9 @@ __device__ __forceinline__ void optimizer_apply(const bsvi_opt_cfg& cfg, float& 
 // state — the in-kernel training loop: one multiply per step instead of a double-precision pow (two of them were a fifth
 // of an iteration of BASELINE config 1 under Adam).  The products differ from pow() by the rounding of at most `st`
 // multiplies (~st * 1e-16 relative): far below the single-precision rounding of the step size they end up in.
-// Adam's factors of the NEXT step, a function of the running products alone: the in-kernel loop may evaluate them before the
-// gradient exists (spec_main.h, SPEC_DRAW_OWNERS) and keep them only when the step is taken.
-struct AdamBias { double p1, p2; float step_size, bc2_sqrt; };
-__device__ __forceinline__ AdamBias optimizer_adam_bias(const bsvi_opt_cfg& cfg, double p1, double p2) {
-    AdamBias b;
-    b.p1 = p1 * (double)cfg.beta1;
-    b.p2 = p2 * (double)cfg.beta2;
-    b.step_size = (float)((double)cfg.lr / (1.0 - b.p1));
-    b.bc2_sqrt = (float)sqrt(1.0 - b.p2);
-    return b;
-}
+// The factors of the NEXT step (optimizer_adam_bias / optimizer_more_bias above) are a function of the running products and
+// the step count alone: the in-kernel loop may evaluate them before the gradient exists (spec_main.h, SPEC_DRAW_OWNERS) and
+// keep them only when the step is taken.
 // the Adam step on those factors (the caller stores b.p1 / b.p2 as its new running products)
 __device__ __forceinline__ void optimizer_apply_adam_biased(const bsvi_opt_cfg& cfg, float& p, float& s0, float& s1, float& s2, float& st,
                                                             float grad, const AdamBias& b) {
@@ -251,10 +340,17 @@ __device__ __forceinline__ void optimizer_apply_adam_biased(const bsvi_opt_cfg& 
 __device__ __forceinline__ void optimizer_apply_running(const bsvi_opt_cfg& cfg, float& p, float& s0, float& s1, float& s2, float& st,
                                                         float grad, double& p1, double& p2) {
     if (cfg.kind == BSVI_OPT_SGD) { optimizer_apply(cfg, p, s0, s1, s2, st, grad); return; }
-    const AdamBias b = optimizer_adam_bias(cfg, p1, p2);
-    optimizer_apply_adam_biased(cfg, p, s0, s1, s2, st, grad, b);
-    p1 = b.p1;
-    p2 = b.p2;
+    if (cfg.kind == BSVI_OPT_ADAM) {
+        const AdamBias b = optimizer_adam_bias(cfg, p1, p2);
+        optimizer_apply_adam_biased(cfg, p, s0, s1, s2, st, grad, b);
+        p1 = b.p1;
+        p2 = b.p2;
+    } else {
+        const AdamBias b = optimizer_more_bias(cfg, p1, p2, st);
+        optimizer_apply_more(cfg, p, s0, s1, s2, st, grad, b);
+        p1 = b.p1;
+        p2 = b.p2;
+    }
 }
 // on memory: state planes `n_params` words apart
 __device__ __forceinline__ void optimizer_update(const bsvi_opt_cfg& cfg, float* params, float* state,

@@ -1999,7 +1999,7 @@ extern "C" int bsvi_finalize(const bsvi_program* p, float* out_dev, uint32_t n_g
 
 static int check_cfg(const bsvi_opt_cfg* cfg) {
     if (!cfg) return fail(BSVI_ERR_INVALID, "null optimizer config");
-    if (cfg->kind > BSVI_OPT_ADAM) return fail(BSVI_ERR_UNSUPPORTED, "unknown optimizer kind");
+    if (cfg->kind > BSVI_OPT_ADAMAX) return fail(BSVI_ERR_UNSUPPORTED, "unknown optimizer kind");
     return BSVI_OK;
 }
 

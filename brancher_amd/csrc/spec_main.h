@@ -114,7 +114,7 @@ struct SpecOwn {
     float a[2], b[2];                // its uniform entries: U = a + b * g(theta)
     uint32_t pos[2], k[2], tr[2];
     uint32_t n, mask;                // entries (0..2); mask bits (SPEC_TAB_MASK)
-    double p1, p2;                   // Adam: beta1^st, beta2^st as running products (optimizer_apply_running)
+    double p1, p2;                   // Adam, AdamW, Adamax: beta1^st, beta2^st as running products (optimizer_apply_running)
 };
 __device__ __forceinline__ void spec_own_store_products(spec_f4* row, const SpecOwn& o) {
     const unsigned long long a = __double_as_longlong(o.p1), b = __double_as_longlong(o.p2);
@@ -491,9 +491,9 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
                 own.s2 = PS[3 * SPEC_NP_PAD + oid]; own.st = PS[4 * SPEC_NP_PAD + oid];
                 own.mask = TAB[SPEC_TAB_MASK + oid];
                 const bsvi_opt_cfg cfg0 = SPEC_A->cfg;       // once per launch: the running products start at beta^st
-                if (cfg0.kind != BSVI_OPT_SGD && own.st != 0.0f) {
-                    own.p1 = pow((double)cfg0.beta1, (double)own.st);
-                    own.p2 = pow((double)cfg0.beta2, (double)own.st);
+                if (own.st != 0.0f) {                        // (the kinds with a beta^step factor: Adam, AdamW; Adamax beta1 only)
+                    if (optimizer_has_p1(cfg0.kind)) own.p1 = pow((double)cfg0.beta1, (double)own.st);
+                    if (optimizer_has_p2(cfg0.kind)) own.p2 = pow((double)cfg0.beta2, (double)own.st);
                 }
             }
 #pragma unroll
@@ -718,7 +718,8 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
                 const bsvi_opt_cfg cfg = SPEC_A->cfg;
 #pragma unroll
                 for (uint32_t e = 0; e < SPEC_OWN_ENTRIES; ++e) fac[e] = own.b[e] * spec_utransform_grad(own.tr[e], own.theta);
-                if (cfg.kind != BSVI_OPT_SGD) bias = optimizer_adam_bias(cfg, own.p1, own.p2);     // (kept when the step is taken)
+                if (cfg.kind == BSVI_OPT_ADAM) bias = optimizer_adam_bias(cfg, own.p1, own.p2);     // (kept when the step is taken)
+                else if (cfg.kind > BSVI_OPT_ADAM) bias = optimizer_more_bias(cfg, own.p1, own.p2, own.st);
                 if (more) {
                     draw_for(0u, off0 + it + 1u, Za);
                     float* const buf = NZB + (((it + 1u) & 1u) ? WSN * (SPEC_KEEP_NOISE * 64u) : 0u);
@@ -818,8 +819,12 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
                     if (finite != 0.0f && (own.mask & mask_bit)) {
                         if (e_cfg.kind == BSVI_OPT_SGD) {
                             optimizer_apply(e_cfg, own.theta, own.s0, own.s1, own.s2, own.st, grad);
-                        } else {
+                        } else if (e_cfg.kind == BSVI_OPT_ADAM) {
                             optimizer_apply_adam_biased(e_cfg, own.theta, own.s0, own.s1, own.s2, own.st, grad, bias);
+                            own.p1 = bias.p1;
+                            own.p2 = bias.p2;
+                        } else {                               // AdamW, RMSprop, Adagrad, Adamax: a scalar branch of their own
+                            optimizer_apply_more(e_cfg, own.theta, own.s0, own.s1, own.s2, own.st, grad, bias);
                             own.p1 = bias.p1;
                             own.p2 = bias.p2;
                         }
@@ -902,8 +907,12 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
                     if (finite != 0.0f && (own.mask & mask_bit)) {
                         if (cfg.kind == BSVI_OPT_SGD) {
                             optimizer_apply(cfg, own.theta, own.s0, own.s1, own.s2, own.st, grad);
-                        } else {
+                        } else if (cfg.kind == BSVI_OPT_ADAM) {
                             optimizer_apply_adam_biased(cfg, own.theta, own.s0, own.s1, own.s2, own.st, grad, bias);
+                            own.p1 = bias.p1;
+                            own.p2 = bias.p2;
+                        } else {                               // AdamW, RMSprop, Adagrad, Adamax: a scalar branch of their own
+                            optimizer_apply_more(cfg, own.theta, own.s0, own.s1, own.s2, own.st, grad, bias);
                             own.p1 = bias.p1;
                             own.p2 = bias.p2;
                         }
@@ -1394,7 +1403,7 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
                         if (e < own.n) spec_store_uniform(own.k[e], own.a[e] + own.b[e] * utransform_common(own.tr[e], own.theta));
                     OWN[5 * oid] = spec_f4{own.theta, own.s0, own.s1, own.s2};
                     spec_lds[SPEC_OFF_OWN + SPEC_OWN_WORDS * oid + 4] = own.st;
-                    if (cfg.kind != BSVI_OPT_SGD) spec_own_store_products(OWN + 5 * oid, own);
+                    if (optimizer_has_p1(cfg.kind)) spec_own_store_products(OWN + 5 * oid, own);     // (Adam, AdamW, Adamax)
                 }
             }
         }

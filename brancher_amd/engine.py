@@ -841,6 +841,9 @@ class CompiledELBO:
         """`brancher/inference.py:95-108` on the device.  Returns (loss_curve, finite_flags) as
         device tensors of length number_iterations; nothing synchronises with the host.
 
+        `optimizer`: "SGD", "Adam", "AdamW", "RMSprop", "Adagrad" or "Adamax" with torch.optim's keyword arguments
+        (`native.make_opt_cfg`); every launch path takes the same configuration.
+
         `minibatch_loop=True`: a model that observes minibatches of a dataset (EmpiricalVariable) keeps the whole loop in ONE
         launch too — the generated kernel draws and gathers every iteration's rows itself (`bsvi_train_persistent_minibatch`),
         the same rows the launch-by-launch path gathers.  Served on one rank, with Philox noise and drawn rows, by the

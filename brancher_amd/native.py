@@ -661,10 +661,38 @@ class NativeProgram:
             pass
 
 
+# bsvi_optimizer_kind (include/bsvi.h)
+OPT_SGD, OPT_ADAM, OPT_ADAMW, OPT_RMSPROP, OPT_ADAGRAD, OPT_ADAMAX = range(6)
+OPTIMIZER_NAMES = ("SGD", "Adam", "AdamW", "RMSprop", "Adagrad", "Adamax")
+
+
+def _opt_options(name, kw, allowed):
+    extra = set(kw) - allowed
+    if extra:
+        raise NotImplementedError("{} options {} are not supported by the fused optimizer".format(name, sorted(extra)))
+
+
+def _opt_nonnegative(name, **values):
+    for key, value in values.items():
+        if not 0.0 <= value:
+            raise ValueError("{}: invalid {}: {}".format(name, key, value))
+
+
+def _opt_betas(name, betas):
+    b1, b2 = betas
+    for i, b in enumerate((b1, b2)):
+        if not 0.0 <= b < 1.0:
+            raise ValueError("{}: invalid beta parameter at index {}: {}".format(name, i, b))
+    return b1, b2
+
+
 def make_opt_cfg(optimizer, **kw):
     """torch.optim keyword arguments -> bsvi_opt_cfg (`brancher/optimizers.py:53-67` forwards
-    ``**opt_params`` verbatim to ``getattr(torch.optim, name)``)."""
+    ``**opt_params`` verbatim to ``getattr(torch.optim, name)``).  SGD, Adam, AdamW, RMSprop, Adagrad and Adamax, with
+    torch's keyword names, defaults and range checks; how the kinds share the words of the struct is the table at
+    `bsvi_opt_cfg` in include/bsvi.h."""
     name = optimizer if isinstance(optimizer, str) else getattr(optimizer, "__name__", str(optimizer))
+    maximize = int(bool(kw.get("maximize", False)))
     if name == "SGD":
         allowed = {"lr", "momentum", "dampening", "weight_decay", "nesterov", "maximize"}
         extra = set(kw) - allowed
@@ -684,5 +712,31 @@ def make_opt_cfg(optimizer, **kw):
         return OptCfg(kind=1, lr=kw.get("lr", 1e-3), beta1=b1, beta2=b2, eps=kw.get("eps", 1e-8),
                       weight_decay=kw.get("weight_decay", 0.0), amsgrad=int(bool(kw.get("amsgrad", False))),
                       maximize=int(bool(kw.get("maximize", False))))
-    raise NotImplementedError("optimizer {!r}: the fused device optimizer implements torch.optim.SGD and "
-                              "torch.optim.Adam".format(name))
+    if name == "AdamW":
+        _opt_options(name, kw, {"lr", "betas", "eps", "weight_decay", "amsgrad", "maximize"})
+        lr, eps, wd = kw.get("lr", 1e-3), kw.get("eps", 1e-8), kw.get("weight_decay", 1e-2)
+        _opt_nonnegative(name, lr=lr, eps=eps, weight_decay=wd)
+        b1, b2 = _opt_betas(name, kw.get("betas", (0.9, 0.999)))
+        return OptCfg(kind=OPT_ADAMW, lr=lr, beta1=b1, beta2=b2, eps=eps, weight_decay=wd,
+                      amsgrad=int(bool(kw.get("amsgrad", False))), maximize=maximize)
+    if name == "RMSprop":
+        _opt_options(name, kw, {"lr", "alpha", "eps", "weight_decay", "momentum", "centered", "maximize"})
+        lr, alpha, eps = kw.get("lr", 1e-2), kw.get("alpha", 0.99), kw.get("eps", 1e-8)
+        wd, momentum = kw.get("weight_decay", 0.0), kw.get("momentum", 0.0)
+        _opt_nonnegative(name, lr=lr, eps=eps, momentum=momentum, weight_decay=wd, alpha=alpha)
+        return OptCfg(kind=OPT_RMSPROP, lr=lr, beta2=alpha, eps=eps, weight_decay=wd, momentum=momentum,
+                      amsgrad=int(bool(kw.get("centered", False))), maximize=maximize)
+    if name == "Adagrad":
+        _opt_options(name, kw, {"lr", "lr_decay", "weight_decay", "initial_accumulator_value", "eps", "maximize"})
+        lr, lr_decay, eps = kw.get("lr", 1e-2), kw.get("lr_decay", 0.0), kw.get("eps", 1e-10)
+        wd, init = kw.get("weight_decay", 0.0), kw.get("initial_accumulator_value", 0.0)
+        _opt_nonnegative(name, lr=lr, lr_decay=lr_decay, weight_decay=wd, initial_accumulator_value=init, eps=eps)
+        return OptCfg(kind=OPT_ADAGRAD, lr=lr, dampening=lr_decay, beta1=init, eps=eps, weight_decay=wd, maximize=maximize)
+    if name == "Adamax":
+        _opt_options(name, kw, {"lr", "betas", "eps", "weight_decay", "maximize"})
+        lr, eps, wd = kw.get("lr", 2e-3), kw.get("eps", 1e-8), kw.get("weight_decay", 0.0)
+        _opt_nonnegative(name, lr=lr, eps=eps, weight_decay=wd)
+        b1, b2 = _opt_betas(name, kw.get("betas", (0.9, 0.999)))
+        return OptCfg(kind=OPT_ADAMAX, lr=lr, beta1=b1, beta2=b2, eps=eps, weight_decay=wd, maximize=maximize)
+    raise NotImplementedError("optimizer {!r}: the fused device optimizer implements torch.optim.{}".format(
+        name, ", ".join(OPTIMIZER_NAMES)))

@@ -5,7 +5,8 @@ The reference walks a model's variables, gathers their ``ParameterModule`` / ``L
 ``EmptyModule`` and hands ``module.parameters()`` to ``getattr(torch.optim, name)(..., **kwargs)``.  Here a
 ``ProbabilisticOptimizer`` only *records* which ``Parameter`` objects it owns and the validated ``torch.optim``
 configuration: the update itself is the fused device optimizer (``bsvi_finalize_step`` / the step fused into the
-reduction kernels), element for element torch.optim.SGD / torch.optim.Adam.  `inference.perform_inference` builds one
+reduction kernels), element for element torch.optim's SGD, Adam, AdamW, RMSprop, Adagrad or Adamax
+(`native.make_opt_cfg`; any other name raises NotImplementedError).  `inference.perform_inference` builds one
 per model exactly like the reference (`inference.py:77-88`) and uses ``.optimizer`` (None when the model has nothing to
 learn) to decide which groups exist.
 """
@@ -65,7 +66,7 @@ class ProbabilisticOptimizer:
     def update(self):
         """One optimizer step of the parameters this optimizer owns, on the device (`bsvi_optimizer_step`), from the
         gradients of the most recent ``compute_loss`` / ``estimate_log_model_evidence(for_gradient=True)`` of the
-        compiled program(s) they live in.  Optimizer state (momentum, Adam moments, step counts) is kept per optimizer,
+        compiled program(s) they live in.  Optimizer state (three planes per kind — momentum, Adam moments, RMSprop / Adagrad sums — and step counts) is kept per optimizer,
         as `torch.optim` keeps it per instance."""
         import numpy as np
         import torch

@@ -274,22 +274,35 @@ int bsvi_elbo_fwd_bwd(const bsvi_program* prog, const bsvi_elbo_args* args);
  * (the .mean() of gradient_estimators.py:36,44 and the sign of inference.py:141). */
 int bsvi_finalize(const bsvi_program* prog, float* out_dev, uint32_t n_samples_global, void* stream);
 
-/* ---- optimizer: torch.optim.{SGD,Adam} reached through brancher/optimizers.py:53-70 ---- */
-typedef enum bsvi_optimizer_kind { BSVI_OPT_SGD = 0, BSVI_OPT_ADAM = 1 } bsvi_optimizer_kind;
+/* ---- optimizer: torch.optim.{SGD,Adam,AdamW,RMSprop,Adagrad,Adamax} reached through brancher/optimizers.py:53-70 ---- */
+typedef enum bsvi_optimizer_kind {
+    BSVI_OPT_SGD = 0, BSVI_OPT_ADAM = 1, BSVI_OPT_ADAMW = 2, BSVI_OPT_RMSPROP = 3, BSVI_OPT_ADAGRAD = 4, BSVI_OPT_ADAMAX = 5
+} bsvi_optimizer_kind;
 
+/* One layout for every kind; the kinds added after SGD and Adam reuse the words:
+ *   kind     words it reads                                                        state planes (s0, s1, s2, st)
+ *   SGD      lr, momentum, dampening, weight_decay, nesterov, maximize             momentum_buffer, -, -, step
+ *   Adam     lr, beta1, beta2, eps, weight_decay, amsgrad, maximize                exp_avg, exp_avg_sq, max_exp_avg_sq, step
+ *   AdamW    as Adam; weight_decay is decoupled (p *= 1 - lr * weight_decay)       exp_avg, exp_avg_sq, max_exp_avg_sq, step
+ *   RMSprop  lr, beta2 = alpha, eps, weight_decay, momentum, amsgrad = centered,   momentum_buffer, square_avg, grad_avg, step
+ *            maximize
+ *   Adagrad  lr, dampening = lr_decay, beta1 = initial_accumulator_value, eps,     -, sum, -, step
+ *            weight_decay, maximize   (the sum starts from beta1 at a parameter's
+ *            own first step, st == 0: the state arrives all zero)
+ *   Adamax   lr, beta1, beta2, eps, weight_decay, maximize                         exp_avg, exp_inf, -, step */
 typedef struct bsvi_opt_cfg {
     uint32_t kind;            /* bsvi_optimizer_kind */
     float lr;
-    float momentum, dampening, weight_decay;   /* SGD */
+    float momentum, dampening, weight_decay;   /* SGD; RMSprop: momentum; Adagrad: dampening = lr_decay */
     uint32_t nesterov;
-    float beta1, beta2, eps;                    /* Adam */
-    uint32_t amsgrad;
+    float beta1, beta2, eps;                    /* Adam, AdamW, Adamax; RMSprop: beta2 = alpha; Adagrad: beta1 = initial_accumulator_value */
+    uint32_t amsgrad;                           /* Adam, AdamW; RMSprop: centered */
     uint32_t maximize;
 } bsvi_opt_cfg;
 
 /* Apply one optimizer step to params[i] for every i with active_mask[i] != 0, unless
  * out_dev[3] (finite flag) is 0 — `inference.py:98-107`.  `state_dev` is
- * [4][n_params] floats (momentum_buffer | exp_avg, exp_avg_sq, max_exp_avg_sq, step count —
+ * [4][n_params] floats (three planes per kind as listed at bsvi_opt_cfg, then the step count —
  * torch keeps one step counter per parameter); zero-initialised by the caller. */
 int bsvi_optimizer_step(const bsvi_opt_cfg* cfg, float* params_dev, const float* out_dev,
                         float* state_dev, const uint8_t* active_mask_dev, uint32_t n_params,
