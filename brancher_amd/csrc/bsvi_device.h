@@ -386,7 +386,7 @@ __device__ __noinline__ float unop_rare_grad(uint32_t sub, float x, float y, flo
     case BSVI_U_LOG1P: return 1.0f / (1.0f + x);
     case BSVI_U_EXPM1: return y + 1.0f;
     case BSVI_U_P2L: return (x >= kFloatEps && x <= 1.0f - kFloatEps) ? (1.0f / x + 1.0f / (1.0f - x)) : 0.0f;
-    case BSVI_U_POWI: return imm * powf(x, imm - 1.0f);
+    case BSVI_U_POWI: return imm == 0.0f ? 0.0f : imm * powf(x, imm - 1.0f);      // torch: d/dx x ** 0 is 0, also at x == 0
     default: return 1.0f;
     }
 }

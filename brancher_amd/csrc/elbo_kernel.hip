@@ -590,7 +590,11 @@ __device__ __forceinline__ void exec_backward(const KParams& K, const Lay& L, La
         case BSVI_B_MUL: ga = g * b; gb = g * a; break;
         case BSVI_B_DIV: ga = g / b; gb = -ga * ld_slot<SM>(K, T, d); break;
         case BSVI_B_POW:
-            if (GEN) { ga = g * b * pow_ff(a, b - 1.0f); gb = (g == 0.0f) ? 0.0f : g * ld_slot<SM>(K, T, d) * logf(a); }
+            // torch's convention: d/da is 0 where b == 0, d/db is 0 where a == 0 and b >= 0 (elsewhere 0 * inf would be NaN)
+            if (GEN) {
+                ga = (b == 0.0f) ? 0.0f : g * b * pow_ff(a, b - 1.0f);
+                gb = (g == 0.0f || (a == 0.0f && b >= 0.0f)) ? 0.0f : g * ld_slot<SM>(K, T, d) * logf(a);
+            }
             break;
         default: break;
         }
@@ -928,8 +932,12 @@ __device__ __forceinline__ void elbo_block(const KParams& K, const Lay& L, uint3
         const uint32_t row_bytes = L.row_words * 4u, cell0 = L.rows * 4u + L.uacc;
         for (uint32_t i = tid; i < K.n_uniform_grad * L.n_waves; i += nthreads) {
             const uint32_t k = i / L.n_waves, wv = i - k * L.n_waves;
+            // only the rows of lanes that carry a sample: the others ran along on the last sample's values with the weight 0, and
+            // where that sample's adjoint is inf their 0 * inf must not turn the sum into NaN (torch returns inf there)
+            const uint32_t first = block_first_sample + wv * L.lpw;
+            const uint32_t live = first < K.n_local ? min(L.lpw, K.n_local - first) : 0u;
             float s = 0.0f;
-            for (uint32_t l = wv * L.rpw; l < wv * L.rpw + L.lpw; ++l) s += lds_ld(cell0 + 4u * k + l * row_bytes);
+            for (uint32_t l = wv * L.rpw; l < wv * L.rpw + live; ++l) s += lds_ld(cell0 + 4u * k + l * row_bytes);
             g_lds[L.uadj + i] = s;
         }
         __syncthreads();

@@ -476,8 +476,9 @@ private:
                 break;
             case BSVI_B_POW:
                 line(fmt("{ const float g = %s, pa = %s, pb = %s;", g.c_str(), a.c_str(), b.c_str()));
-                add_adj(I.a, e, "g * pb * pow_ff(pa, pb - 1.0f)");
-                add_adj(I.b, e, "((g == 0.0f) ? 0.0f : g * " + y + " * logf(pa))");
+                // torch's convention (elbo_kernel.hip exec_backward): d/da is 0 where b == 0, d/db is 0 where a == 0 and b >= 0
+                add_adj(I.a, e, "((pb == 0.0f) ? 0.0f : g * pb * pow_ff(pa, pb - 1.0f))");
+                add_adj(I.b, e, "((g == 0.0f || (pa == 0.0f && pb >= 0.0f)) ? 0.0f : g * " + y + " * logf(pa))");
                 line("}");
                 break;
             default: break;
