@@ -8,7 +8,12 @@ Bayesian neural networks on the dense-link path: lowering and engine for graphs 
     q:       NormalVariable(loc, scale, <same name>, learnable=True) for weights1, b1, weights2, b2
 
 — the reference's `tests/test_MNIST_bayesian_neural_network.py:20-60` (any depth, any of tanh / relu / sigmoid / softplus
-between the layers, biases optional).  `dense.lower_dense` serves ONE latent matrix without a bias; this module serves the
+between the layers, biases optional) — and the regression model of the same family, the chain as the loc of an observed Normal,
+
+    y = NormalVariable(BF.matmul(weights2, hidden) + b2, sigma, name="y");  y.observe(targets)        # targets [DS, C, 1]
+
+with sigma a constant of the model (one value, or [C, 1]), from one layer (minibatched Bayesian linear regression) to eight:
+`bsvi_bnn_create_normal`.  `dense.lower_dense` serves ONE latent matrix without a bias; this module serves the
 rest of the family through `bsvi_bnn_*` (include/bsvi.h, csrc/bnn_kernel.inc).  The reference's semantics are kept as on the
 dense path: priors and posteriors are matched by NAME, auto-created roots `<var>_<arg>` collide by name, no
 minibatch rescaling of the likelihood (`variables.py:849` TODO).
@@ -24,7 +29,7 @@ from brancher_amd.lowering import LoweringError, _Lowering
 from brancher_amd.native import OUT_HEADER, BnnArgs, BnnDesc, BnnLayer
 from brancher_amd.variables import RandomVariable, RootVariable
 
-LIK_CATEGORICAL, LIK_BERNOULLI = 0, 1
+LIK_CATEGORICAL, LIK_BERNOULLI, LIK_NORMAL = 0, 1, 2
 ACTIVATIONS = dict(tanh=1, relu=2, sigmoid=3, softplus=4)
 NO_BIAS = 0xFFFFFFFF
 
@@ -36,7 +41,7 @@ class BnnProgram:
     def summary(self):
         return dict(kind="bnn", layers=[(l["rows"], l["cols"], l["activation"]) for l in self.layers], n_rows=self.n_rows,
                     dataset_size=self.dataset_size, batch_size=self.batch_size, n_params=self.n_params,
-                    likelihood=("categorical", "bernoulli")[self.likelihood], latents=[t["name"] for t in self.tensors])
+                    likelihood=("categorical", "bernoulli", "normal")[self.likelihood], latents=[t["name"] for t in self.tensors])
 
 
 def _is_random(v):
@@ -73,6 +78,36 @@ def _chain(e):
     raise LoweringError("bnn path: between two layers stands one of BF.%s" % " / BF.".join(ACTIVATIONS))
 
 
+def _depends_on_latent(e):
+    """does a link expression read a random variable (through deterministic nodes too)?"""
+    if e.op == "var":
+        v = e.attr
+        if getattr(v, "_type", None) == "Deterministic node":
+            return any(_depends_on_latent(x.expr) for x in v.link.expressions().values())
+        return isinstance(v, RandomVariable)
+    return any(_depends_on_latent(a) for a in e.args if hasattr(a, "op"))
+
+
+def _normal_scale(L, k, links, n_outputs):
+    """the scale of the Normal likelihood -> (first entry among the uniform table's constants, stride): one for every output
+    (stride 0) or one per output (stride 1).  (A learnable scale needs a reduction over (sample, row) of its own through every middle
+    kernel: DESIGN.md §9.)"""
+    e = links["scale"].expr
+    m = L.match_uniform(L.from_expr(e, L.p_value))
+    if m is None:
+        raise LoweringError("bnn path: the scale of the Normal likelihood %r must be a constant or a transform of one" % k.name)
+    leaf, g, a, b = m
+    if leaf.op == "root" and leaf.attr.learnable:
+        raise LoweringError("bnn path: the scale of the Normal likelihood %r is learnable (it must be a constant of the model)" % k.name)
+    size = int(np.prod(leaf.shape))
+    shape = tuple(int(d) for d in leaf.shape)
+    if size != 1 and (size != n_outputs or shape[-1] != 1):
+        raise LoweringError("bnn path: the scale of the Normal likelihood %r has shape %r: neither one value nor one per output [%d, 1]"
+                            % (k.name, shape[1:], n_outputs))
+    _, k0 = L.uniform_entries(leaf, g, a, b)
+    return k0, (1 if size > 1 else 0)
+
+
 def lower_bnn(joint, posterior, estimator="pathwise"):
     # "taylor1" (gradient_estimators.py:47-56): f at the posterior's analytic means — every latent of the network is a mean-field Normal,
     # whose mean is its loc (distributions.py:137 through torch), so the program is the Pathwise one evaluated on the draw eps = 0
@@ -91,19 +126,34 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
         if v.learnable:
             L.param_offset(v.parameter, 1)
     q_random = [v for v in q_flat if _is_random(v)]
+    # (a regression model whose noise scale is a latent is named as such, before the posterior of that latent is looked at)
+    for v in joint._flatten():
+        if _is_random(v) and v.distribution.kind == D.DIST_NORMAL and v.is_observed and getattr(v, "has_random_dataset", False) \
+                and _depends_on_latent(v.link.expressions()["scale"].expr):
+            raise LoweringError("bnn path: the scale of the Normal likelihood %r is a latent variable or computed from one "
+                                "(it must be a constant of the model)" % v.name)
     if not q_random or any(v.distribution.kind != D.DIST_NORMAL for v in q_random):
         raise LoweringError("bnn path: the posterior must be mean-field Normal variables")
     p_random = [v for v in joint._flatten() if _is_random(v)]
-    liks = [v for v in p_random if v.distribution.kind in (D.DIST_CATEGORICAL, D.DIST_BINOMIAL, D.DIST_BERNOULLI)]
+    # the likelihood: a Categorical / Binomial(1) over logits, or — regression — an OBSERVED Normal whose loc is the chain
+    liks = [v for v in p_random if v.distribution.kind in (D.DIST_CATEGORICAL, D.DIST_BINOMIAL, D.DIST_BERNOULLI)
+            or (v.distribution.kind == D.DIST_NORMAL and v.is_observed)]
     if len(liks) != 1:
         raise LoweringError("bnn path: expected one matmul likelihood")
     k = liks[0]
+    normal = k.distribution.kind == D.DIST_NORMAL
     if not k.is_observed or not k.has_random_dataset:
         raise LoweringError("bnn path: the likelihood must be observed through an EmpiricalVariable of labels")
     links = k.link.expressions()
-    if "logits" not in links:
-        raise LoweringError("bnn path: the likelihood must be parameterised by logits")
-    chain, x_var = _chain(links["logits"].expr)
+    if normal:
+        try:
+            chain, x_var = _chain(links["loc"].expr)
+        except LoweringError as err:
+            raise LoweringError("bnn path: the loc of the Normal likelihood %r is not a chain of matmul layers (%s)" % (k.name, err)) from None
+    else:
+        if "logits" not in links:
+            raise LoweringError("bnn path: the likelihood must be parameterised by logits")
+        chain, x_var = _chain(links["logits"].expr)
     latents = []
     for W, b, _ in chain:
         latents.append(W)
@@ -138,7 +188,10 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     if ind_x is not ind_y:
         raise LoweringError("bnn path: x and labels must share one RandomIndices variable")
     DS = X.shape[1]
-    Xm, Ym = X.reshape(DS, -1), Y.reshape(-1)
+    # labels: one per row; targets of the Normal likelihood: one per row and output, [DS][C] row-major
+    if normal and (Y.ndim < 2 or Y.shape[1] != DS):
+        raise LoweringError("bnn path: dataset sizes of x and labels differ")
+    Xm, Ym = X.reshape(DS, -1), (Y.reshape(DS, -1) if normal else Y.reshape(-1))
     if Ym.shape[0] != DS:
         raise LoweringError("bnn path: dataset sizes of x and labels differ")
     P = Xm.shape[1]
@@ -191,7 +244,12 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
         layers.append(dict(rows=t["rows"], cols=t["cols"], weight_row0=t["row0"], bias_row0=bias0,
                            activation=ACTIVATIONS[act] if act else 0, weights=W.name, bias=b.name if b is not None else None))
         width = t["rows"]
-    lik = LIK_CATEGORICAL if k.distribution.kind == D.DIST_CATEGORICAL else LIK_BERNOULLI
+    lik = LIK_NORMAL if normal else LIK_CATEGORICAL if k.distribution.kind == D.DIST_CATEGORICAL else LIK_BERNOULLI
+    scale_entries = None
+    if normal:
+        if Ym.shape[1] != width:
+            raise LoweringError("bnn path: the targets have %d columns but the last layer has %d rows" % (Ym.shape[1], width))
+        scale_entries = _normal_scale(L, k, links, width)
     if lik == LIK_BERNOULLI:
         if width != 1:
             raise LoweringError("bnn path: a Bernoulli/Binomial likelihood needs a single output")
@@ -215,6 +273,9 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     prog.layers, prog.tensors, prog.n_rows = layers, tensors, R
     prog.n_features, prog.n_classes, prog.dataset_size, prog.batch_size = P, width, DS, int(ind_x.batch_size)
     prog.likelihood = lik
+    if normal:
+        # (constants stand behind the entries with a gradient in the uniform table)
+        prog.scale_uniform, prog.scale_stride = n_up + scale_entries[0], scale_entries[1]
     prog.dataset = np.ascontiguousarray(Xm, dtype=np.float32)
     prog.labels = np.ascontiguousarray(Ym, dtype=np.float32)
     prog.indices_name = ind_x.name
@@ -222,6 +283,25 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     prog.n_noise = R
     prog.bmax = 1
     return prog
+
+
+def make_desc(p):
+    """bsvi_bnn_desc of a lowered program -> (desc, the arrays it points into: keep them alive as long as the desc)"""
+    layers = (BnnLayer * len(p.layers))(*[BnnLayer(rows=l["rows"], cols=l["cols"], weight_row0=l["weight_row0"],
+                                                    bias_row0=l["bias_row0"], activation=l["activation"]) for l in p.layers])
+    k = dict(uniform=np.ascontiguousarray(p.uniform), consts=np.ascontiguousarray(p.consts, dtype=np.float32),
+             ptr=np.ascontiguousarray(p.param_uniform_ptr, dtype=np.uint32),
+             idx=np.ascontiguousarray(p.param_uniform_idx, dtype=np.uint32),
+             rows=np.ascontiguousarray(p.row_uniform, dtype=np.uint32), dataset=p.dataset, labels=p.labels, layers=layers)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+    d = BnnDesc(abi_version=native.ABI_VERSION, n_params=p.n_params, n_consts=k["consts"].size, n_uniform=len(k["uniform"]),
+                n_uniform_grad=p.n_uniform_grad, n_layers=len(p.layers), n_rows=p.n_rows, n_features=p.n_features,
+                dataset_size=p.dataset_size, batch_size=p.batch_size, likelihood=p.likelihood,
+                estimator=lowering.EST[getattr(p, "estimator", "pathwise")], lik_weight=p.lik_weight,
+                prior_weight=p.prior_weight, entropy_weight=p.entropy_weight, layers=C.cast(layers, C.c_void_p),
+                row_uniform=ptr(k["rows"]), uniform=ptr(k["uniform"]), consts=ptr(k["consts"]),
+                param_uniform_ptr=ptr(k["ptr"]), param_uniform_idx=ptr(k["idx"]), dataset=ptr(k["dataset"]), labels=ptr(k["labels"]))
+    return d, k
 
 
 class CompiledBnn:
@@ -241,23 +321,12 @@ class CompiledBnn:
         if lib.bsvi_device_count() < 1:
             raise native.NativeError("no MI355X / HIP device visible: the engine cannot run (no CPU fallback)")
         self.lib = lib
-        layers = (BnnLayer * len(p.layers))(*[BnnLayer(rows=l["rows"], cols=l["cols"], weight_row0=l["weight_row0"],
-                                                        bias_row0=l["bias_row0"], activation=l["activation"]) for l in p.layers])
-        self._keep = dict(uniform=np.ascontiguousarray(p.uniform), consts=np.ascontiguousarray(p.consts, dtype=np.float32),
-                          ptr=np.ascontiguousarray(p.param_uniform_ptr, dtype=np.uint32),
-                          idx=np.ascontiguousarray(p.param_uniform_idx, dtype=np.uint32),
-                          rows=np.ascontiguousarray(p.row_uniform, dtype=np.uint32), dataset=p.dataset, labels=p.labels, layers=layers)
-        k = self._keep
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
-        d = BnnDesc(abi_version=native.ABI_VERSION, n_params=p.n_params, n_consts=k["consts"].size, n_uniform=len(k["uniform"]),
-                    n_uniform_grad=p.n_uniform_grad, n_layers=len(p.layers), n_rows=p.n_rows, n_features=p.n_features,
-                    dataset_size=p.dataset_size, batch_size=p.batch_size, likelihood=p.likelihood,
-                    estimator=lowering.EST[getattr(p, "estimator", "pathwise")], lik_weight=p.lik_weight,
-                    prior_weight=p.prior_weight, entropy_weight=p.entropy_weight, layers=C.cast(layers, C.c_void_p),
-                    row_uniform=ptr(k["rows"]), uniform=ptr(k["uniform"]), consts=ptr(k["consts"]),
-                    param_uniform_ptr=ptr(k["ptr"]), param_uniform_idx=ptr(k["idx"]), dataset=ptr(k["dataset"]), labels=ptr(k["labels"]))
+        d, self._keep = make_desc(p)
         handle = C.c_void_p()
-        native.check(lib.bsvi_bnn_create(C.byref(d), C.byref(handle)))
+        if p.likelihood == LIK_NORMAL:
+            native.check(lib.bsvi_bnn_create_normal(C.byref(d), p.scale_uniform, p.scale_stride, C.byref(handle)))
+        else:
+            native.check(lib.bsvi_bnn_create(C.byref(d), C.byref(handle)))
         self.handle = handle
         self._exact_data = bool(lib.bsvi_bnn_exact_data(handle))
         dev = self.device

@@ -3,7 +3,13 @@
 // The reference's model family (tests/test_MNIST_bayesian_neural_network.py:20-60): a chain
 //     logits = W_L act( ... act(W_1 x + b_1) ... ) + b_L
 // in which EVERY weight matrix and every bias is a latent with a mean-field Normal posterior, the likelihood an observed
-// Categorical (or Binomial(1)) over a random minibatch.  All latent scalars form ONE vector of R rows (weights1 first: H_1 x P
+// Categorical (or Binomial(1)) over a random minibatch — or, for regression, an observed Normal whose loc is the chain and whose
+// scale sigma is a constant of the model (BSVI_LIK_NORMAL, bsvi_bnn_create_normal): one real target per output and minibatch row,
+// lab [B_pad][C], where the classifiers keep one label per row.  Per (row b, sample n):
+//     lik = wgt sum_c (-1/2 u_c^2 - log sigma_c - 1/2 log 2 pi),  u_c = (y[b][c] - z_c) / sigma_c;   delta_c = wgt u_c / sigma_c
+// at the three sites that hold a likelihood (bnn_upper, bnn_upper_gen, bnn_mid_gen); everything behind the deltas is unchanged.
+// A learnable sigma would need a reduction over (sample, row) of its own through each of them: not built (DESIGN.md 9).
+// All latent scalars form ONE vector of R rows (weights1 first: H_1 x P
 // rows r = h * P + p, then the other tensors); row r draws eps from the dense path's Philox counters (sample, r >> 2), so the
 // noise of a model is one [R][N] matrix as on the dense path, and reads its four parameters (q loc, q scale, prior loc, prior
 // scale) from the uniform table through a per-row index — any mixture of per-element arrays and shared scalars.
@@ -14,7 +20,8 @@
 //                   pieces when the data is exactly bf16, else f32), the small tensors per sample; per-sample prior / log q sums
 //   product 1       a1[b][(h, n)] = sum_p x[b][p] W1[n][h][p]              bf16 matrix cores on exact pieces | f32-input MFMA
 //   bnn_upper       one thread per (sample, minibatch row): bias + activation, the upper layers (per-sample H_l x H_l-1 products),
-//                   log-softmax cross-entropy, the reverse sweep down to d f / d a1 (as the operand of the second product)
+//                   the likelihood (log-softmax cross-entropy | Bernoulli logits | Normal), the reverse sweep down to d f / d a1 (as
+//                   the operand of the second product)
 //   bnn_small / bnn_lik   per sample: gradients of the small tensors (sums over the minibatch), the sample's likelihood
 //   product 2       GT[(h, n)][p] = sum_b d a1[(h, n)][b] x[b][p]
 //   bnn_row_sums    per row: sum_n eps G, sum_n G, sum_n eps, sum_n eps^2 (fixed order)
@@ -33,6 +40,7 @@ struct BParams {
     BnnLayerDev layer[BNN_MAX_LAYERS];
     uint32_t n_layers, R, R1, Rs, P, C, H1, DS, B, B_pad, Kp, P_ld, n_local, n_pad, n_global, sample_base, NC;
     uint32_t n_uniform_grad, likelihood, estimator, exact, act_width;
+    uint32_t LC, scale_u, scale_stride;       // targets per minibatch row (1 label; C for the Normal likelihood) and sigma's uniform entries
     float lik_weight, prior_weight, entropy_weight;
     uint32_t seed_lo, seed_hi, offset_lo, offset_hi;
     const float* noise_in; float* noise_out; const int32_t* indices_in; int32_t* indices_out; float* fvalue_out; float* logq_out;
@@ -44,7 +52,8 @@ struct BParams {
     const float* q_weight;      // [n_local] or null (BlackBox: b_n = f_n)
     // workspace
     float* rowp;            // [4][R]
-    int32_t* idx; float* lab;
+    int32_t* idx;
+    float* lab;             // [B_pad][LC]; Normal likelihood: then sigma [C] and -log sigma - 1/2 log 2 pi [C] (bnn_head_body)
     float* Xb; uint16_t* Xb_bf; uint16_t* XbT_bf;
     float* W1f; uint16_t* Wp; float* Wsm;
     float* a1T;             // [B_pad][NC]
@@ -130,7 +139,13 @@ __device__ __forceinline__ void bnn_head_body(const BParams& Q, const uint32_t i
         const int32_t row = bnn_minibatch_row(Q, i);
         if (i < Q.B && Q.indices_out) Q.indices_out[i] = row;
         Q.idx[i] = row;
-        Q.lab[i] = row >= 0 ? Q.labels[row] : 0.0f;
+        for (uint32_t c = 0; c < Q.LC; ++c) Q.lab[(size_t)i * Q.LC + c] = row >= 0 ? Q.labels[(size_t)row * Q.LC + c] : 0.0f;
+    }
+    if (Q.likelihood == BSVI_LIK_NORMAL && i < Q.C) {      // (R >= C: the last layer alone has C rows of weights)
+        const float sigma = bnn_uniform_value(Q, Q.scale_u + i * Q.scale_stride);
+        float* const sg = Q.lab + (size_t)Q.B_pad * Q.LC;
+        sg[i] = sigma;
+        sg[Q.C + i] = -logf(sigma) - 0.91893853320467274178f;
     }
     for (uint32_t k = i; k < 2u + Q.n_uniform_grad; k += n_threads) Q.partial[k] = 0.0f;
 }
@@ -280,9 +295,21 @@ __global__ void __launch_bounds__(256) bnn_upper(const BParams Q) {
             }
         }
         // ---- likelihood and d f / d logits (distributions.py:294-311 / 561-592 through torch: log_softmax, BCE with logits)
-        const float wgt = live ? Q.lik_weight * (Q.f_weight ? Q.f_weight[n] : 1.0f) : 0.0f, label = Q.lab[b];
+        const float wgt = live ? Q.lik_weight * (Q.f_weight ? Q.f_weight[n] : 1.0f) : 0.0f, label = Q.lab[(size_t)b * Q.LC];
         float lik = 0.0f;
-        if (Q.likelihood == BSVI_LIK_CATEGORICAL) {
+        if (Q.likelihood == BSVI_LIK_NORMAL) {
+            // y_c ~ Normal(z_c, sigma_c), sigma a constant of the model (distributions.py:137 through torch): the targets of row b,
+            // then sigma and -log sigma - 1/2 log 2 pi per output behind the targets (bnn_head_body)
+            const float* const yb = Q.lab + (size_t)b * Q.LC;
+            const float* const sg = Q.lab + (size_t)Q.B_pad * Q.LC;
+            float s = 0.0f;
+            for (uint32_t c = 0; c < LL.rows; ++c) {
+                const float sigma = sg[c], u = (yb[c] - Y(LL, c)) / sigma;
+                s += -0.5f * u * u + sg[LL.rows + c];
+                Dl(LL, c) = wgt * u / sigma;
+            }
+            lik = wgt * s;
+        } else if (Q.likelihood == BSVI_LIK_CATEGORICAL) {
             float m = -INFINITY;
             for (uint32_t c = 0; c < LL.rows; ++c) m = fmaxf(m, Y(LL, c));
             float se = 0.0f, zl = 0.0f;
@@ -551,6 +578,8 @@ struct bsvi_bnn {
     const uint32_t* ur_ptr = nullptr; const uint32_t* ur_item = nullptr;
     const float* dataset = nullptr; const float* labels = nullptr;
     uint32_t R = 0, R1 = 0, Rs = 0, P = 0, C = 0, H1 = 0, B_pad = 0, Kp = 0, P_ld = 0;
+    uint32_t LC = 1;             // targets per dataset row: one label, or C for the Normal likelihood
+    uint32_t scale_u = 0, scale_stride = 0;      // Normal likelihood: sigma of output c is uniform entry scale_u + c * scale_stride (constants)
     uint64_t act_floats = 0, delta_floats = 0;      // per (sample, minibatch row)
     uint32_t act_off[BNN_MAX_LAYERS] = {};
     bool exact = false;
@@ -573,6 +602,26 @@ struct BnnUpperArgs {
     float lik_weight;
     const float* f_weight;      // a_n per sample, or null
 };
+
+// the Normal likelihood of the two generated kernels (the text bnn_upper runs with loop bounds): targets [B_pad][C] in A.lab, then
+// sigma [C] and -log sigma - 1/2 log 2 pi [C] as bnn_head_body leaves them — the values of the uniform table, never a host copy
+static std::string bnn_normal_source(uint32_t C, uint32_t yl) {
+    char buf[1024];
+    snprintf(buf, sizeof buf,
+             "        {\n"
+             "            const float* const yb = A.lab + (size_t)b * %uu;\n"
+             "            const float* const sg = A.lab + (size_t)A.B_pad * %uu;\n"
+             "            float sn = 0.0f;\n"
+             "#pragma unroll\n"
+             "            for (uint32_t c = 0; c < %uu; ++c) {\n"
+             "                const float sigma = sg[c], u = (yb[c] - y[%uu + c]) / sigma;\n"
+             "                sn += -0.5f * u * u + sg[%uu + c];\n"
+             "                d[%uu + c] = wgt * u / sigma;\n"
+             "            }\n"
+             "            lik = wgt * sn;\n"
+             "        }\n", C, C, C, yl, C, yl);
+    return std::string(buf);
+}
 
 // ---- bnn_upper as generated source.  The generic kernel above walks the network with run-time loop bounds: every weight of the
 // sample's small tensors and every activation is an LDS read in front of the FMA that needs it (~2 200 of them per (sample, row) of
@@ -642,8 +691,11 @@ static std::string bnn_upper_source(const bsvi_bnn* p) {
     // likelihood
     const bsvi_bnn_layer& LL = p->layers[NL - 1];
     const uint32_t yl = p->act_off[NL - 1];
-    s += "        const float wgt = live ? A.lik_weight * (A.f_weight ? A.f_weight[n] : 1.0f) : 0.0f, label = A.lab[b];\n        float lik = 0.0f;\n";
-    if (p->d.likelihood == BSVI_LIK_CATEGORICAL) {
+    s += std::string("        const float wgt = live ? A.lik_weight * (A.f_weight ? A.f_weight[n] : 1.0f) : 0.0f") +
+         (p->d.likelihood == BSVI_LIK_NORMAL ? ";\n" : ", label = A.lab[b];\n") + "        float lik = 0.0f;\n";
+    if (p->d.likelihood == BSVI_LIK_NORMAL) {
+        s += bnn_normal_source(LL.rows, yl);
+    } else if (p->d.likelihood == BSVI_LIK_CATEGORICAL) {
         s += "        {\n            float m = -INFINITY;\n#pragma unroll\n";
         s += fmt("            for (uint32_t c = 0; c < %uu; ++c) m = fmaxf(m, y[%uu + c]);\n", LL.rows, yl);
         s += "            float se = 0.0f, zl = 0.0f;\n#pragma unroll\n";
@@ -792,8 +844,11 @@ static std::string bnn_mid_source(const bsvi_bnn* p) {
     }
     const bsvi_bnn_layer& LL = p->layers[NL - 1];
     const uint32_t yl = p->act_off[NL - 1];
-    s += "        const float wgt = live ? A.lik_weight * (A.f_weight ? A.f_weight[n] : 1.0f) : 0.0f, label = A.lab[b];\n        float lik = 0.0f;\n";
-    if (p->d.likelihood == BSVI_LIK_CATEGORICAL) {
+    s += std::string("        const float wgt = live ? A.lik_weight * (A.f_weight ? A.f_weight[n] : 1.0f) : 0.0f") +
+         (p->d.likelihood == BSVI_LIK_NORMAL ? ";\n" : ", label = A.lab[b];\n") + "        float lik = 0.0f;\n";
+    if (p->d.likelihood == BSVI_LIK_NORMAL) {
+        s += bnn_normal_source(LL.rows, yl);
+    } else if (p->d.likelihood == BSVI_LIK_CATEGORICAL) {
         s += "        {\n            float m = -INFINITY;\n#pragma unroll\n";
         s += fmt("            for (uint32_t c = 0; c < %uu; ++c) m = fmaxf(m, y[%uu + c]);\n", LL.rows, yl);
         s += "            float se = 0.0f, zl = 0.0f;\n#pragma unroll\n";
@@ -927,7 +982,8 @@ static bool bnn_upper_ready(const bsvi_bnn* p) {
 }
 
 
-extern "C" int bsvi_bnn_create(const bsvi_bnn_desc* desc, bsvi_bnn** out) {
+// the two entry points' common body; normal: bsvi_bnn_create_normal (the scale entries are its plain arguments)
+static int bnn_create(const bsvi_bnn_desc* desc, const bool normal, const uint32_t scale_uniform, const uint32_t scale_stride, bsvi_bnn** out) {
     if (!desc || !out) return fail(BSVI_ERR_INVALID, "null argument");
     *out = nullptr;
     BSVI_CHECK_STRUCT(desc, bsvi_bnn_desc);
@@ -935,7 +991,10 @@ extern "C" int bsvi_bnn_create(const bsvi_bnn_desc* desc, bsvi_bnn** out) {
     if (!desc->layers || !desc->n_layers || desc->n_layers > BNN_MAX_LAYERS) return fail(BSVI_ERR_INVALID, "1 .. 8 layers");
     if (!desc->n_features || !desc->batch_size || desc->batch_size > desc->dataset_size || !desc->n_rows) return fail(BSVI_ERR_INVALID, "bad shape");
     if (desc->n_features % 4) return fail(BSVI_ERR_UNSUPPORTED, "the number of features must be a multiple of 4 (the noise is drawn in quads of rows)");
-    if (desc->likelihood > BSVI_LIK_BERNOULLI) return fail(BSVI_ERR_UNSUPPORTED, "unknown likelihood");
+    if (!normal && desc->likelihood == BSVI_LIK_NORMAL)
+        return fail(BSVI_ERR_UNSUPPORTED, "the Normal likelihood needs its scale entries: create the model with bsvi_bnn_create_normal");
+    if (normal && desc->likelihood != BSVI_LIK_NORMAL) return fail(BSVI_ERR_INVALID, "bsvi_bnn_create_normal takes likelihood BSVI_LIK_NORMAL");
+    if (desc->likelihood > BSVI_LIK_NORMAL) return fail(BSVI_ERR_UNSUPPORTED, "unknown likelihood");
     if (desc->estimator > BSVI_EST_BLACKBOX) return fail(BSVI_ERR_INVALID, "unknown estimator");
     for (uint32_t k = 0; k < desc->n_uniform; ++k) {
         const bsvi_uniform_entry& e = desc->uniform[k];
@@ -959,6 +1018,14 @@ extern "C" int bsvi_bnn_create(const bsvi_bnn_desc* desc, bsvi_bnn** out) {
     }
     if (desc->layers[desc->n_layers - 1].activation != BSVI_BNN_ACT_NONE) return fail(BSVI_ERR_INVALID, "the last layer yields the logits");
     if (desc->likelihood == BSVI_LIK_BERNOULLI && width != 1) return fail(BSVI_ERR_INVALID, "Bernoulli likelihood needs one output");
+    if (normal) {
+        // sigma of output c: entry scale_uniform + c * scale_stride, every one of them a constant of the model
+        if (scale_stride > 1u) return fail(BSVI_ERR_INVALID, "scale_stride is 0 (one scale for every output) or 1 (one per output)");
+        const uint64_t last = (uint64_t)scale_uniform + (uint64_t)scale_stride * (width - 1u);
+        if (last >= desc->n_uniform) return fail(BSVI_ERR_INVALID, "scale entry out of the uniform table");
+        if (scale_uniform < desc->n_uniform_grad)
+            return fail(BSVI_ERR_UNSUPPORTED, "the scale of the Normal likelihood must be a constant of the model: a learnable scale is not implemented");
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(BSVI_ERR_NO_DEVICE, "no HIP device visible");
     bsvi_bnn* p = new bsvi_bnn();
@@ -969,6 +1036,7 @@ extern "C" int bsvi_bnn_create(const bsvi_bnn_desc* desc, bsvi_bnn** out) {
     p->R1 = p->H1 * p->P; p->Rs = R - p->R1;
     p->Kp = (p->P + 31) / 32 * 32; p->P_ld = (p->P + 3) / 4 * 4;
     p->B_pad = (desc->batch_size + 31) / 32 * 32;
+    if (normal) { p->LC = width; p->scale_u = scale_uniform; p->scale_stride = scale_stride; }
     for (uint32_t l = 0; l < desc->n_layers; ++l) { p->act_off[l] = (uint32_t)p->act_floats; p->act_floats += p->layers[l].rows; }
     p->delta_floats = p->act_floats;
     {   // exact data: both products on the bf16 matrix cores (three MFMAs on the exact pieces of the other operand); BSVI_DENSE_XGEMM=0: f32
@@ -991,7 +1059,7 @@ extern "C" int bsvi_bnn_create(const bsvi_bnn_desc* desc, bsvi_bnn** out) {
     }
     const size_t sizes[9] = {(size_t)desc->n_uniform * sizeof(bsvi_uniform_entry), (size_t)desc->n_consts * 4, ((size_t)desc->n_params + 1) * 4,
                              (size_t)desc->n_uniform_grad * 4, 4 * (size_t)R * 4, ur_ptr.size() * 4, ur_item.size() * 4,
-                             (size_t)desc->dataset_size * desc->n_features * 4, (size_t)desc->dataset_size * 4};
+                             (size_t)desc->dataset_size * desc->n_features * 4, (size_t)desc->dataset_size * p->LC * 4};
     const void* srcs[9] = {desc->uniform, desc->consts, desc->param_uniform_ptr, desc->param_uniform_idx, desc->row_uniform, ur_ptr.data(),
                            ur_item.data(), desc->dataset, desc->labels};
     size_t offs[9], total = 0;
@@ -1020,6 +1088,12 @@ extern "C" int bsvi_bnn_create(const bsvi_bnn_desc* desc, bsvi_bnn** out) {
     return BSVI_OK;
 }
 
+extern "C" int bsvi_bnn_create(const bsvi_bnn_desc* desc, bsvi_bnn** out) { return bnn_create(desc, false, 0u, 0u, out); }
+
+extern "C" int bsvi_bnn_create_normal(const bsvi_bnn_desc* desc, uint32_t scale_uniform, uint32_t scale_stride, bsvi_bnn** out) {
+    return bnn_create(desc, true, scale_uniform, scale_stride, out);
+}
+
 extern "C" void bsvi_bnn_destroy(bsvi_bnn* p) {
     if (!p) return;
     if (p->dev_blob) (void)hipFree(p->dev_blob);
@@ -1043,7 +1117,9 @@ static BnnLayout bnn_layout(const bsvi_bnn* p, uint32_t n_local) {
     size_t o = 0;
     auto take = [&](size_t bytes) { const size_t at = o; o += align_up(bytes, 256); return at; };
     const size_t nb = (size_t)L.n_pad * p->B_pad;
-    L.rowp = take(4 * (size_t)p->R * 4); L.idx = take((size_t)p->B_pad * 4); L.lab = take((size_t)p->B_pad * 4);
+    L.rowp = take(4 * (size_t)p->R * 4); L.idx = take((size_t)p->B_pad * 4);
+    // (targets [B_pad][LC]; the Normal likelihood keeps sigma and its log term, [2][C], behind them)
+    L.lab = take(((size_t)p->B_pad * p->LC + (p->d.likelihood == BSVI_LIK_NORMAL ? 2u * (size_t)p->C : 0u)) * 4);
     L.Xb = take(p->exact ? 0 : (size_t)p->B_pad * p->P_ld * 4);
     L.Xb_bf = take(p->exact ? (size_t)p->B_pad * p->Kp * 2 : 0); L.XbT_bf = take(p->exact ? (size_t)p->P * p->B_pad * 2 : 0);
     L.W1f = take(p->exact ? 0 : (size_t)L.NC * p->P_ld * 4); L.Wp = take(p->exact ? 3 * (size_t)L.NC * p->Kp * 2 : 0);
@@ -1092,6 +1168,7 @@ static int bnn_fill(const bsvi_bnn* p, const bsvi_bnn_args* a, BParams& Q, BnnLa
     Q.B_pad = p->B_pad; Q.Kp = p->Kp; Q.P_ld = p->P_ld; Q.n_local = a->n_samples_local; Q.n_pad = L.n_pad; Q.n_global = a->n_samples_global;
     Q.sample_base = a->sample_base; Q.NC = L.NC; Q.n_uniform_grad = p->d.n_uniform_grad; Q.likelihood = p->d.likelihood;
     Q.estimator = p->d.estimator; Q.exact = p->exact ? 1u : 0u; Q.act_width = (uint32_t)p->act_floats;
+    Q.LC = p->LC; Q.scale_u = p->scale_u; Q.scale_stride = p->scale_stride;
     Q.lik_weight = p->d.lik_weight; Q.prior_weight = p->d.prior_weight; Q.entropy_weight = p->d.entropy_weight;
     Q.seed_lo = (uint32_t)a->seed; Q.seed_hi = (uint32_t)(a->seed >> 32); Q.offset_lo = (uint32_t)a->offset; Q.offset_hi = (uint32_t)(a->offset >> 32);
     Q.noise_in = a->noise_dev; Q.noise_out = a->noise_out_dev; Q.indices_in = a->indices_dev; Q.indices_out = a->indices_out_dev;

@@ -804,6 +804,65 @@ def build_bayesian_neural_network(api, dataset_size=48, batch_size=30, n_feature
     return model
 
 
+def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_hidden=9, n_outputs=1, hidden2=0, activation="tanh",
+                         sigma=0.5, data="integers", bias=True, seed=0, prior_scale=2., q_scale=0.1, q_scale1=None, q_loc_scale=0.5):
+    """The regression model of the Bayesian-neural-network family: the network of `build_bayesian_neural_network` (latent weight
+    matrices and biases under a mean-field Normal posterior) as the loc of an observed Normal,
+    `y ~ NormalVariable(matmul(weights2, act(matmul(weights1, x) + b1)) + b2, sigma)`, the targets [DS, C, 1] an EmpiricalVariable that
+    shares the minibatch indices of x.  n_hidden = 0: one layer — minibatched Bayesian linear regression at any width; bias=False: no
+    bias variables; sigma: one number, or one per output (a list: a constant [C, 1]).  data="integers": features in -3 .. 3 (exactly
+    bf16 numbers: the products run on exact bf16 pieces), "normal": standard normal features (the f32-input products).  The targets
+    come from a teacher network of the same shape plus noise of scale sigma.  Posterior means are drawn at `q_loc_scale` posterior
+    scales from zero, and the scale of the first layer (default 0.4 / sqrt(sum_p E x_p^2)) keeps every hidden unit off saturation."""
+    BF = api.BF
+    rng = np.random.RandomState(seed)
+    if data == "integers":
+        X = rng.randint(-3, 4, size=(dataset_size, n_features, 1)).astype(np.float32)
+    elif data == "normal":
+        X = rng.normal(0., 1., size=(dataset_size, n_features, 1)).astype(np.float32)
+    else:
+        raise ValueError("data is 'integers' or 'normal'")
+    widths = [n_features] + ([n_hidden] if n_hidden else []) + ([hidden2] if n_hidden and hidden2 else []) + [n_outputs]
+    np_act = dict(tanh=np.tanh, relu=lambda v: np.maximum(v, 0.), sigmoid=lambda v: 1. / (1. + np.exp(-v)),
+                  softplus=lambda v: np.log1p(np.exp(v)))[activation]
+    sig = np.asarray(sigma, dtype=np.float64).reshape(-1)
+    if sig.size not in (1, n_outputs):
+        raise ValueError("sigma is one number or one per output")
+    # the teacher: unit-variance pre-activations in every layer
+    h = X[:, :, 0].astype(np.float64)
+    for l in range(1, len(widths)):
+        wt = rng.normal(0., 1., (widths[l], widths[l - 1])) / np.sqrt(max((h ** 2).mean(axis=0).sum(), 1e-6))
+        h = h @ wt.T + (0.3 * rng.normal(0., 1., widths[l]) if bias else 0.)
+        if l + 1 < len(widths):
+            h = np_act(h)
+    Y = (h + sig * rng.normal(0., 1., h.shape)).astype(np.float32).reshape(dataset_size, n_outputs, 1)
+    if q_scale1 is None:
+        q_scale1 = 0.4 / np.sqrt(float((X.astype(np.float64) ** 2).mean(axis=0).sum()))
+    rng = np.random.RandomState(seed + 7)
+    act = getattr(BF, activation)
+    indices = api.RandomIndices(dataset_size=dataset_size, batch_size=batch_size, name="indices", is_observed=True)
+    x = api.EmpiricalVariable(X, indices=indices, name="x", is_observed=True)
+    targets = api.EmpiricalVariable(Y, indices=indices, name="targets", is_observed=True)
+    layer, q_vars = x, []
+    for l in range(1, len(widths)):
+        rows, cols = widths[l], widths[l - 1]
+        sw = q_scale1 if l == 1 else q_scale
+        w = api.NormalVariable(np.zeros((rows, cols)), prior_scale * np.ones((rows, cols)), "weights%d" % l)
+        pre = BF.matmul(w, layer)
+        if bias:
+            pre = pre + api.NormalVariable(np.zeros((rows, 1)), prior_scale * np.ones((rows, 1)), "b%d" % l)
+            q_vars.append(api.NormalVariable(q_loc_scale * q_scale * rng.normal(0., 1., (rows, 1)), q_scale * np.ones((rows, 1)),
+                                             "b%d" % l, learnable=True))
+        layer = act(pre) if l + 1 < len(widths) else pre
+        q_vars.append(api.NormalVariable(q_loc_scale * sw * rng.normal(0., 1., (rows, cols)), sw * np.ones((rows, cols)),
+                                         "weights%d" % l, learnable=True))
+    y = api.NormalVariable(layer, float(sig[0]) if sig.size == 1 else sig.reshape(n_outputs, 1), "y")
+    model = api.ProbabilisticModel([y])
+    y.observe(targets)
+    model.set_posterior_model(api.ProbabilisticModel(q_vars))
+    return model
+
+
 def vae_modules(n_features, latent_size, hidden1, hidden2, seed=0, decoder_sd_head=False):
     """Encoder / decoder networks with the layer plan of `examples/VAE_playground.py:27-62` (there: 784-256-512-(2,2)
     and 2-512-256-784): two ReLU layers, then a mean head and a softplus(+0.1) scale head; the decoder mirrors the

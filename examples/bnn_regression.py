@@ -1,0 +1,50 @@
+"""Regression with a Bayesian neural network: the first thing one tries with the family.
+
+    y ~ NormalVariable(BF.matmul(weights2, BF.tanh(BF.matmul(weights1, x) + b1)) + b2, sigma)
+
+Every weight matrix and bias is a latent under a mean-field Normal posterior, the noise scale sigma a constant of the model, and `x`
+and the targets two EmpiricalVariables that share a RandomIndices variable — another minibatch in every iteration.  At 784 features
+the model is far beyond the scalar engine: `engine.compile_model` sends it to the matrix-core path of the Bayesian-neural-network
+family (two MFMA products with the minibatch, the Normal likelihood between them; csrc/bnn_kernel.inc).  Run on a machine with an
+MI355X:
+
+    python examples/bnn_regression.py
+"""
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from brancher_amd import engine, inference, workloads as W
+
+KW = dict(dataset_size=512, batch_size=30, n_features=784, n_hidden=20, n_outputs=1, sigma=0.5)
+
+
+def dataset_of(variable):
+    """[DS, rows] array behind an EmpiricalVariable"""
+    a = np.asarray(variable.link.expressions()["dataset"].expr.attr.value, dtype=np.float64)
+    return a.reshape(KW["dataset_size"], -1)
+
+
+def posterior_mean_rmse(model):
+    """root mean squared error, over the whole dataset, of the network evaluated at the posterior means of its weights"""
+    y = next(v for v in model.flatten() if v.name == "y")
+    X, Y = dataset_of(next(v for v in model.flatten() if v.name == "x")), dataset_of(y.dataset)
+    p = engine.compile_model(model).named_params()
+    hidden = np.tanh(X @ p["weights1_loc"].reshape(KW["n_hidden"], -1).T + p["b1_loc"].reshape(1, -1))
+    pred = hidden @ p["weights2_loc"].reshape(KW["n_outputs"], -1).T + p["b2_loc"].reshape(1, -1)
+    return float(np.sqrt(np.mean((pred - Y) ** 2)))
+
+
+model = W.build_bnn_regression(W.native_api(), **KW)
+print("engine: %s, data path %s" % (type(engine.compile_model(model)).__name__, engine.compile_model(model).data_path()))
+print("RMSE of the posterior-mean prediction before training: %.3f (noise scale %.2f)" % (posterior_mean_rmse(model), KW["sigma"]))
+t0 = time.time()
+inference.perform_inference(model, number_iterations=1500, number_samples=50, optimizer="Adam", lr=0.005)
+seconds = time.time() - t0
+loss = np.asarray(model.diagnostics["loss curve"])
+print("1500 iterations in %.2f s; loss %.1f -> %.1f" % (seconds, loss[:20].mean(), loss[-20:].mean()))
+print("RMSE of the posterior-mean prediction after training:  %.3f" % posterior_mean_rmse(model))

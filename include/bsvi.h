@@ -453,7 +453,8 @@ int bsvi_query_geometry(const bsvi_program* prog, uint32_t n_samples_local, uint
  * ========================================================================================= */
 typedef enum bsvi_dense_likelihood {
     BSVI_LIK_CATEGORICAL = 0,   /* CategoricalVariable(logits=...)            distributions.py:294-311 */
-    BSVI_LIK_BERNOULLI = 1      /* Binomial(1, logits=...) / Bernulli(logits) distributions.py:561-592 */
+    BSVI_LIK_BERNOULLI = 1,     /* Binomial(1, logits=...) / Bernulli(logits) distributions.py:561-592 */
+    BSVI_LIK_NORMAL = 2         /* NormalVariable(loc, scale) with a constant scale: regression; bsvi_bnn_create_normal only */
 } bsvi_dense_likelihood;
 
 typedef struct bsvi_dense_desc {
@@ -525,7 +526,8 @@ int bsvi_dense_step(const bsvi_dense* d, const bsvi_dense_args* args, const bsvi
  *  Bayesian neural networks on the dense-link path (the reference's tests/test_MNIST_bayesian_neural_network.py:20-60):
  *      logits = W_L act( ... act(W_1 x + b_1) ... ) + b_L        (`BF.tanh(BF.matmul(weights1, x) + b1)`, functions.py:28-41)
  *  with EVERY weight matrix and bias a latent under a mean-field Normal posterior, an observed Categorical / Binomial(1)
- *  likelihood and a random minibatch per iteration.  All latent scalars form one vector of n_rows rows — weights1 first
+ *  likelihood — or, for regression, an observed Normal whose loc is the last layer and whose scale is a constant of the model
+ *  (bsvi_bnn_create_normal; one layer without a hidden one is Bayesian linear regression) — and a random minibatch per iteration.  All latent scalars form one vector of n_rows rows — weights1 first
  *  (H_1 x P, row r = h * P + p), the other tensors behind it — whose noise is the dense path's [n_rows][N] matrix (Philox
  *  counters (sample, row >> 2)); every row reads its q loc / q scale / prior loc / prior scale from the uniform table through
  *  row_uniform.  The two products with the minibatch (2 x 2 N H_1 P B flops) run on the matrix cores — on exact bf16 pieces when
@@ -559,7 +561,7 @@ typedef struct bsvi_bnn_desc {
     const uint32_t* param_uniform_ptr;
     const uint32_t* param_uniform_idx;
     const float* dataset;            /* [dataset_size][n_features] host copy */
-    const float* labels;             /* [dataset_size] host copy            */
+    const float* labels;             /* [dataset_size] host copy ([dataset_size][outputs] for BSVI_LIK_NORMAL) */
 } bsvi_bnn_desc;
 
 typedef struct bsvi_bnn bsvi_bnn;
@@ -588,6 +590,13 @@ typedef struct bsvi_bnn_args {
 } bsvi_bnn_args;
 
 int bsvi_bnn_create(const bsvi_bnn_desc* desc, bsvi_bnn** out);
+/* The regression model of the family: desc->likelihood == BSVI_LIK_NORMAL, targets y ~ Normal(last layer, sigma) with one target
+ * per output, so desc->labels is [dataset_size][rows of the last layer] (row-major).  sigma is a CONSTANT of the model read from the
+ * uniform table: output c takes entry scale_uniform + c * scale_stride, scale_stride 0 (one sigma for every output) or 1; every
+ * such entry must be a constant (index >= n_uniform_grad), a learnable scale is BSVI_ERR_UNSUPPORTED.  Per minibatch row, sample and
+ * output:  f += lik_weight * (-1/2 u^2 - log sigma_c - 1/2 log 2 pi),  u = (y_c - z_c) / sigma_c.  Everything else is as for
+ * bsvi_bnn_create, whose handle type and calls it shares; bsvi_bnn_create itself refuses this likelihood. */
+int bsvi_bnn_create_normal(const bsvi_bnn_desc* desc, uint32_t scale_uniform, uint32_t scale_stride, bsvi_bnn** out);
 void bsvi_bnn_destroy(bsvi_bnn* b);
 size_t bsvi_bnn_workspace_bytes(const bsvi_bnn* b, uint32_t n_samples_local);
 int bsvi_bnn_exact_data(const bsvi_bnn* b);
