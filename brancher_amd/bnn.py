@@ -32,6 +32,8 @@ from brancher_amd.variables import RandomVariable, RootVariable
 LIK_CATEGORICAL, LIK_BERNOULLI, LIK_NORMAL = 0, 1, 2
 ACTIVATIONS = dict(tanh=1, relu=2, sigmoid=3, softplus=4)
 NO_BIAS = 0xFFFFFFFF
+MAX_LAYERS = 8                                                         # BNN_MAX_LAYERS (csrc/bnn_kernel.inc)
+MIDDLE_PATHS = ("mid_gen", "upper_gen", "upper_lds", "upper_mem")      # bsvi_bnn_select::BnnMiddle (csrc/bnn_select.h)
 
 
 class BnnProgram:
@@ -154,6 +156,8 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
         if "logits" not in links:
             raise LoweringError("bnn path: the likelihood must be parameterised by logits")
         chain, x_var = _chain(links["logits"].expr)
+    if len(chain) > MAX_LAYERS:
+        raise LoweringError("bnn path: the network has %d layers, the kernels serve at most %d" % (len(chain), MAX_LAYERS))
     latents = []
     for W, b, _ in chain:
         latents.append(W)
@@ -311,6 +315,16 @@ class CompiledBnn:
         """which matrix-core path serves the two products with the minibatch: "bf16x3" when every dataset value is exactly a
         bf16 number (three bf16 MFMAs on the exact pieces of the f32 operand), else "f32" (the f32-input MFMA kernels)"""
         return "bf16x3" if self._exact_data else "f32"
+
+    def middle_path(self):
+        """which kernel serves the upper layers, the likelihood and the reverse sweep of the next launch (csrc/bnn_select.h, from the
+        network's size and BSVI_BNN_MID / BSVI_BNN_JIT as they stand at the first launch or call of this): "mid_gen" and "upper_gen"
+        are generated for the network (compiled here if no launch has yet; one that does not compile reports what serves instead),
+        "upper_lds" and "upper_mem" the static kernel with its activations in LDS or in global memory"""
+        kind = int(self.lib.bsvi_bnn_middle(self.handle))
+        if not 0 <= kind < len(MIDDLE_PATHS):
+            raise native.NativeError("bsvi_bnn_middle returned %d" % kind)
+        return MIDDLE_PATHS[kind]
 
     def __init__(self, joint_model, posterior_model, estimator="pathwise", device=None, program=None):
         from brancher_amd import engine

@@ -28,6 +28,8 @@
 //   bnn_row_sums (its last part) / bnn_epilogue / bnn_uniform_grads / dense_param_kernel      closed-form prior and entropy terms, the value, chain rule
 // The two products carry the flops (2 x 2 N H_1 P B); everything else is elementwise or tiny and written for clarity.
 
+#include "bnn_select.h"
+
 constexpr uint32_t BNN_MAX_LAYERS = 8;
 
 struct BnnLayerDev { uint32_t rows, cols, w0, b0, act, act_off, delta_off, in_off; };
@@ -924,8 +926,12 @@ static std::string bnn_mid_source(const bsvi_bnn* p) {
     return s;
 }
 
-static size_t bnn_mid_lds_bytes(const bsvi_bnn* p) {
-    return (((size_t)(p->Rs ? p->Rs : 1) + 3u) / 4u * 4u + 2u * (size_t)p->act_floats * (p->B_pad + 4u)) * 4u;
+static size_t bnn_mid_lds_bytes(const bsvi_bnn* p) { return bsvi_bnn_select::mid_lds_bytes(p->Rs, p->act_floats, p->B_pad); }
+// the middle kernel of this network under the given switches (bnn_select.h: sizes only — a failed compile is handled where it is tried)
+static bsvi_bnn_select::BnnMiddle bnn_middle_for(const bsvi_bnn* p, bool mid_off, bool jit_off) {
+    bsvi_bnn_select::Switches sw;
+    sw.mid_off = mid_off; sw.jit_off = jit_off;
+    return bsvi_bnn_select::middle(p->Rs, p->act_floats, p->B_pad, p->exact, sw);
 }
 // bnn_mid_gen compiled on first use; false: the separate launches serve (BSVI_BNN_MID=0, data that is not exactly bf16, a tile beyond
 // LDS, a failed compile)
@@ -934,8 +940,7 @@ static bool bnn_mid_ready(const bsvi_bnn* p) {
     if (p->mid_state) return p->mid_state > 0;
     p->mid_state = -1;
     const char* e = getenv("BSVI_BNN_MID");
-    if (e && e[0] == '0') return false;
-    if (!p->exact || bnn_mid_lds_bytes(p) > 150u * 1024u || p->act_floats > 96u || p->B_pad % 4u) return false;
+    if (bnn_middle_for(p, e && e[0] == '0', false) != bsvi_bnn_select::MID_GEN) return false;
     const std::string src = bnn_mid_source(p);
     if (const char* dump = getenv("BSVI_BNN_SOURCE_DUMP")) {
         if (FILE* f = fopen((std::string(dump) + ".mid").c_str(), "w")) { fputs(src.c_str(), f); fclose(f); }
@@ -961,8 +966,7 @@ static bool bnn_upper_ready(const bsvi_bnn* p) {
     if (p->jit_state) return p->jit_state > 0;
     p->jit_state = -1;
     const char* e = getenv("BSVI_BNN_JIT");
-    if (e && e[0] == '0') return false;
-    if (p->Rs + 2u * (uint32_t)p->act_floats > 400u || (size_t)(p->Rs ? p->Rs : 1) * 65u * 4u > 150u * 1024u) return false;
+    if (bnn_middle_for(p, true, e && e[0] == '0') != bsvi_bnn_select::UPPER_GEN) return false;      // (asked once bnn_mid_gen does not serve)
     std::vector<char> code;
     std::string log;
     const std::string src = bnn_upper_source(p);
@@ -975,7 +979,7 @@ static bool bnn_upper_ready(const bsvi_bnn* p) {
     }
     hipError_t err = hipModuleLoadData(&p->jit_module, code.data());
     if (err == hipSuccess) err = hipModuleGetFunction(&p->jit_fn, p->jit_module, "bnn_upper_gen");
-    if (err == hipSuccess) err = hipFuncSetAttribute((const void*)p->jit_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)(p->Rs ? p->Rs : 1) * 65u * 4u));
+    if (err == hipSuccess) err = hipFuncSetAttribute((const void*)p->jit_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bsvi_bnn_select::upper_gen_lds_bytes(p->Rs));
     if (err != hipSuccess) { (void)hipGetLastError(); p->jit_fn = nullptr; return false; }
     p->jit_state = 1;
     return true;
@@ -1075,10 +1079,10 @@ static int bnn_create(const bsvi_bnn_desc* desc, const bool normal, const uint32
     p->row_uniform = (const uint32_t*)(base + offs[4]); p->ur_ptr = (const uint32_t*)(base + offs[5]); p->ur_item = (const uint32_t*)(base + offs[6]);
     p->dataset = (const float*)(base + offs[7]); p->labels = (const float*)(base + offs[8]);
     {
-        const size_t wl_bytes = ((size_t)(p->Rs ? p->Rs : 1) * 65u + 2u * (size_t)p->act_floats * 256u) * 4u;
+        const size_t wl_bytes = bsvi_bnn_select::upper_lds_bytes(p->Rs, p->act_floats);
         int dev = 0, n_cu = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n_cu > 0) p->n_cu = (uint32_t)n_cu;
-        p->upper_lds = wl_bytes <= 150u * 1024u &&
+        p->upper_lds = bnn_middle_for(p, true, true) == bsvi_bnn_select::UPPER_LDS &&
                        hipFuncSetAttribute((const void*)bnn_upper<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl_bytes) == hipSuccess;
         if (!p->upper_lds) (void)hipGetLastError();
     }
@@ -1103,6 +1107,15 @@ extern "C" void bsvi_bnn_destroy(bsvi_bnn* p) {
 }
 
 extern "C" int bsvi_bnn_exact_data(const bsvi_bnn* p) { return (p && p->exact) ? 1 : 0; }
+
+// the middle kernel the next launch runs (bnn_launch asks the same questions in the same order): the generated kernels are compiled here
+// as a launch would compile them, and one that did not compile reports what serves in its place
+extern "C" int bsvi_bnn_middle(const bsvi_bnn* p) {
+    if (!p) return -1;
+    if (bnn_mid_ready(p)) return bsvi_bnn_select::MID_GEN;
+    if (bnn_upper_ready(p)) return bsvi_bnn_select::UPPER_GEN;
+    return p->upper_lds ? bsvi_bnn_select::UPPER_LDS : bsvi_bnn_select::UPPER_MEM;
+}
 
 struct BnnLayout {
     size_t rowp, idx, lab, Xb, Xb_bf, XbT_bf, W1f, Wp, Wsm, a1T, acts, deltas, liknb, da1T, dlogp, GT, gsm, lik, pv, qv, sums, rowg, hpart, partial, fs, total;
@@ -1208,7 +1221,7 @@ static int bnn_launch(const bsvi_bnn* p, const BParams& Q, const BnnLayout& L, h
         HIP_TRY(hipModuleLaunchKernel(p->mid_fn, Q.n_pad, 1, 1, 256, 1, 1, (unsigned)bnn_mid_lds_bytes(p), s, nullptr, config));
     } else {
         const dim3 ugrid(Q.n_pad / 64, (Q.B_pad + 7) / 8);
-        const size_t wl_bytes = ((size_t)Q.Rs * 65u + 2u * (size_t)Q.act_width * 256u) * 4u;
+        const size_t wl_bytes = bsvi_bnn_select::upper_lds_bytes(p->Rs, p->act_floats);
         if (bnn_upper_ready(p)) {
             // (no LDS beyond the staging tile and registers only: several workgroups per CU — two rows per wave as above)
             BnnUpperArgs U{Q.Wsm, Q.a1T, Q.lab, Q.acts, Q.deltas, Q.liknb, Q.da1T, Q.dlogp, Q.n_local, Q.n_pad, Q.B, Q.B_pad, Q.NC, 2u, Q.exact, Q.lik_weight, Q.f_weight};
@@ -1217,7 +1230,7 @@ static int bnn_launch(const bsvi_bnn* p, const BParams& Q, const BnnLayout& L, h
             size_t size = sizeof U;
             void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &U, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
             const uint32_t gy = (Q.B_pad + 4u * U.rows_per_wave - 1u) / (4u * U.rows_per_wave);
-            HIP_TRY(hipModuleLaunchKernel(p->jit_fn, Q.n_pad / 64, gy, 1, 256, 1, 1, (unsigned)((size_t)Q.Rs * 65u * 4u), s, nullptr, config));
+            HIP_TRY(hipModuleLaunchKernel(p->jit_fn, Q.n_pad / 64, gy, 1, 256, 1, 1, (unsigned)bsvi_bnn_select::upper_gen_lds_bytes(p->Rs), s, nullptr, config));
         }
         else if (p->upper_lds) hipLaunchKernelGGL(bnn_upper<true>, ugrid, dim3(256), wl_bytes, s, Q);
         else hipLaunchKernelGGL(bnn_upper<false>, ugrid, dim3(256), 0, s, Q);

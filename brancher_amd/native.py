@@ -182,6 +182,7 @@ EXPORTS.update({
     "bsvi_bnn_destroy": (None, [C.c_void_p]),
     "bsvi_bnn_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_uint32]),
     "bsvi_bnn_exact_data": (C.c_int, [C.c_void_p]),
+    "bsvi_bnn_middle": (C.c_int, [C.c_void_p]),
     "bsvi_bnn_fwd_bwd": (C.c_int, [C.c_void_p, C.POINTER(BnnArgs)]),
     "bsvi_bnn_finalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "bsvi_bnn_step": (C.c_int, [C.c_void_p, C.POINTER(BnnArgs), C.POINTER(OptCfg), C.c_void_p, C.c_void_p, C.c_void_p,

@@ -762,9 +762,36 @@ def build_minibatch_linear_regression(api, dataset_size=40, batch_size=8, n_feat
     return model
 
 
+def _bnn_widths(widths, n_features, hidden, n_outputs):
+    """the layer widths of the two Bayesian-neural-network builders, features first and outputs last: `widths` as given, or the
+    builder's own keywords -> (n_features, n_outputs, widths)"""
+    if widths is None:
+        return n_features, n_outputs, [n_features] + list(hidden) + [n_outputs]
+    widths = [int(w) for w in widths]
+    if len(widths) < 2 or min(widths) < 1:
+        raise ValueError("widths lists the features, every hidden layer and the outputs: at least two positive numbers")
+    return widths[0], widths[-1], widths
+
+
+def _bnn_activations(activations, activation, n_hidden_layers):
+    if activations is None:
+        return [activation] * n_hidden_layers
+    if len(activations) != n_hidden_layers:
+        raise ValueError("activations names one function per hidden layer: %d, not %d" % (n_hidden_layers, len(activations)))
+    return list(activations)
+
+
+def _bnn_features(rng, data, dataset_size, n_features):
+    if data == "integers":
+        return rng.randint(-3, 4, size=(dataset_size, n_features, 1)).astype(np.float32)
+    if data == "normal":
+        return rng.normal(0., 1., size=(dataset_size, n_features, 1)).astype(np.float32)
+    raise ValueError("data is 'integers' or 'normal'")
+
+
 def build_bayesian_neural_network(api, dataset_size=48, batch_size=30, n_features=784, n_hidden=20, n_classes=10, seed=0,
                                   prior_scale=10., q_scale=0.2, q_scale1=None, q_loc_scale=0.0, pixels="uint8",
-                                  activation="tanh", hidden2=0):
+                                  activation="tanh", hidden2=0, widths=None, activations=None):
     """`tests/test_MNIST_bayesian_neural_network.py:20-60` of the reference: a one-hidden-layer network whose weight matrices AND
     biases are latent — weights1 [H, P], b1 [H, 1], weights2 [C, H], b2 [C, 1], priors N(0, 10), a mean-field Normal posterior
     over all four (scale 0.2) — `tanh(matmul(weights1, x) + b1)`, `matmul(weights2, hidden) + b2` as the logits of an observed
@@ -772,24 +799,32 @@ def build_bayesian_neural_network(api, dataset_size=48, batch_size=30, n_feature
     CategoricalVariable does not accept; `logits=` is what the sibling examples use.)  MNIST is not available offline: pixel
     counts 0..255 as in `logreg_data`.  q_scale1: the posterior scale of weights1 alone (with raw pixel counts and 0.2 every
     tanh saturates and every gradient of the first layer vanishes: the fixtures use a scale that keeps the units alive);
-    q_loc_scale: posterior means drawn at that many posterior scales from zero; hidden2 > 0: a second hidden layer."""
+    q_loc_scale: posterior means drawn at that many posterior scales from zero; hidden2 > 0: a second hidden layer.
+    widths: the full list of layer widths, features first, outputs last (it overrides n_features, n_hidden, hidden2 and n_classes: any
+    depth); activations: one name per hidden layer (default: `activation` everywhere).  pixels="integers" / "normal": the features of
+    `build_bnn_regression` (-3 .. 3, exactly bf16 | standard normal)."""
     BF = api.BF
-    X, labels = logreg_data(dataset_size, n_features, max(n_classes, 2), seed, pixels)
+    n_features, n_classes, widths = _bnn_widths(widths, n_features, [n_hidden] + ([hidden2] if hidden2 else []), n_classes)
+    if pixels in ("integers", "normal"):
+        rng = np.random.RandomState(seed)
+        X = _bnn_features(rng, pixels, dataset_size, n_features)
+        labels = rng.randint(0, max(n_classes, 2), size=dataset_size)
+    else:
+        X, labels = logreg_data(dataset_size, n_features, max(n_classes, 2), seed, pixels)
     if n_classes == 1:
         labels = labels.astype(np.float32).reshape(-1, 1)          # (0 / 1, as minibatch_logistic_regression.py:20 stores them)
     rng = np.random.RandomState(seed + 7)
-    act = getattr(BF, activation)
+    acts = _bnn_activations(activations, activation, len(widths) - 2)
     indices = api.RandomIndices(dataset_size=dataset_size, batch_size=batch_size, name="indices", is_observed=True)
     x = api.EmpiricalVariable(X, indices=indices, name="x", is_observed=True)
     y = api.EmpiricalVariable(labels, indices=indices, name="labels", is_observed=True)
-    widths = [n_features, n_hidden] + ([hidden2] if hidden2 else []) + [n_classes]
     layer, q_vars = x, []
     for l in range(1, len(widths)):
         rows, cols = widths[l], widths[l - 1]
         b = api.NormalVariable(np.zeros((rows, 1)), prior_scale * np.ones((rows, 1)), "b%d" % l)
         w = api.NormalVariable(np.zeros((rows, cols)), prior_scale * np.ones((rows, cols)), "weights%d" % l)
         pre = BF.matmul(w, layer) + b
-        layer = act(pre) if l + 1 < len(widths) else pre
+        layer = getattr(BF, acts[l - 1])(pre) if l + 1 < len(widths) else pre
         sw = q_scale1 if (l == 1 and q_scale1 is not None) else q_scale
         q_vars.append(api.NormalVariable(q_loc_scale * q_scale * rng.normal(0., 1., (rows, 1)), q_scale * np.ones((rows, 1)),
                                          "b%d" % l, learnable=True))
@@ -805,7 +840,8 @@ def build_bayesian_neural_network(api, dataset_size=48, batch_size=30, n_feature
 
 
 def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_hidden=9, n_outputs=1, hidden2=0, activation="tanh",
-                         sigma=0.5, data="integers", bias=True, seed=0, prior_scale=2., q_scale=0.1, q_scale1=None, q_loc_scale=0.5):
+                         sigma=0.5, data="integers", bias=True, seed=0, prior_scale=2., q_scale=0.1, q_scale1=None, q_loc_scale=0.5,
+                         widths=None, activations=None):
     """The regression model of the Bayesian-neural-network family: the network of `build_bayesian_neural_network` (latent weight
     matrices and biases under a mean-field Normal posterior) as the loc of an observed Normal,
     `y ~ NormalVariable(matmul(weights2, act(matmul(weights1, x) + b1)) + b2, sigma)`, the targets [DS, C, 1] an EmpiricalVariable that
@@ -813,18 +849,17 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
     bias variables; sigma: one number, or one per output (a list: a constant [C, 1]).  data="integers": features in -3 .. 3 (exactly
     bf16 numbers: the products run on exact bf16 pieces), "normal": standard normal features (the f32-input products).  The targets
     come from a teacher network of the same shape plus noise of scale sigma.  Posterior means are drawn at `q_loc_scale` posterior
-    scales from zero, and the scale of the first layer (default 0.4 / sqrt(sum_p E x_p^2)) keeps every hidden unit off saturation."""
+    scales from zero, and the scale of the first layer (default 0.4 / sqrt(sum_p E x_p^2)) keeps every hidden unit off saturation.
+    widths: the full list of layer widths, features first, outputs last (it overrides n_features, n_hidden, hidden2 and n_outputs: any
+    depth); activations: one name per hidden layer (default: `activation` everywhere)."""
     BF = api.BF
+    n_features, n_outputs, widths = _bnn_widths(widths, n_features, ([n_hidden] if n_hidden else []) + ([hidden2] if n_hidden and hidden2 else []),
+                                                n_outputs)
     rng = np.random.RandomState(seed)
-    if data == "integers":
-        X = rng.randint(-3, 4, size=(dataset_size, n_features, 1)).astype(np.float32)
-    elif data == "normal":
-        X = rng.normal(0., 1., size=(dataset_size, n_features, 1)).astype(np.float32)
-    else:
-        raise ValueError("data is 'integers' or 'normal'")
-    widths = [n_features] + ([n_hidden] if n_hidden else []) + ([hidden2] if n_hidden and hidden2 else []) + [n_outputs]
-    np_act = dict(tanh=np.tanh, relu=lambda v: np.maximum(v, 0.), sigmoid=lambda v: 1. / (1. + np.exp(-v)),
-                  softplus=lambda v: np.log1p(np.exp(v)))[activation]
+    X = _bnn_features(rng, data, dataset_size, n_features)
+    acts = _bnn_activations(activations, activation, len(widths) - 2)
+    np_acts = dict(tanh=np.tanh, relu=lambda v: np.maximum(v, 0.), sigmoid=lambda v: 1. / (1. + np.exp(-v)),
+                   softplus=lambda v: np.log1p(np.exp(v)))
     sig = np.asarray(sigma, dtype=np.float64).reshape(-1)
     if sig.size not in (1, n_outputs):
         raise ValueError("sigma is one number or one per output")
@@ -834,12 +869,11 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
         wt = rng.normal(0., 1., (widths[l], widths[l - 1])) / np.sqrt(max((h ** 2).mean(axis=0).sum(), 1e-6))
         h = h @ wt.T + (0.3 * rng.normal(0., 1., widths[l]) if bias else 0.)
         if l + 1 < len(widths):
-            h = np_act(h)
+            h = np_acts[acts[l - 1]](h)
     Y = (h + sig * rng.normal(0., 1., h.shape)).astype(np.float32).reshape(dataset_size, n_outputs, 1)
     if q_scale1 is None:
         q_scale1 = 0.4 / np.sqrt(float((X.astype(np.float64) ** 2).mean(axis=0).sum()))
     rng = np.random.RandomState(seed + 7)
-    act = getattr(BF, activation)
     indices = api.RandomIndices(dataset_size=dataset_size, batch_size=batch_size, name="indices", is_observed=True)
     x = api.EmpiricalVariable(X, indices=indices, name="x", is_observed=True)
     targets = api.EmpiricalVariable(Y, indices=indices, name="targets", is_observed=True)
@@ -853,7 +887,7 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
             pre = pre + api.NormalVariable(np.zeros((rows, 1)), prior_scale * np.ones((rows, 1)), "b%d" % l)
             q_vars.append(api.NormalVariable(q_loc_scale * q_scale * rng.normal(0., 1., (rows, 1)), q_scale * np.ones((rows, 1)),
                                              "b%d" % l, learnable=True))
-        layer = act(pre) if l + 1 < len(widths) else pre
+        layer = getattr(BF, acts[l - 1])(pre) if l + 1 < len(widths) else pre
         q_vars.append(api.NormalVariable(q_loc_scale * sw * rng.normal(0., 1., (rows, cols)), sw * np.ones((rows, cols)),
                                          "weights%d" % l, learnable=True))
     y = api.NormalVariable(layer, float(sig[0]) if sig.size == 1 else sig.reshape(n_outputs, 1), "y")

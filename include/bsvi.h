@@ -600,6 +600,11 @@ int bsvi_bnn_create_normal(const bsvi_bnn_desc* desc, uint32_t scale_uniform, ui
 void bsvi_bnn_destroy(bsvi_bnn* b);
 size_t bsvi_bnn_workspace_bytes(const bsvi_bnn* b, uint32_t n_samples_local);
 int bsvi_bnn_exact_data(const bsvi_bnn* b);
+/* Which kernel serves the upper layers, the likelihood and the reverse sweep of the next launch (csrc/bnn_select.h, chosen from the
+ * network's size): 0 bnn_mid_gen, 1 bnn_upper_gen (both generated for the network; compiled by this call as a launch would compile
+ * them, and one that does not compile reports what serves in its place), 2 bnn_upper in LDS, 3 bnn_upper through global memory;
+ * -1 for a null handle. */
+int bsvi_bnn_middle(const bsvi_bnn* b);
 /* ELBO forward + backward over this GPU's sample shard; sums in out_dev (then all-reduce / bsvi_bnn_finalize / bsvi_finalize_step) */
 int bsvi_bnn_fwd_bwd(const bsvi_bnn* b, const bsvi_bnn_args* args);
 int bsvi_bnn_finalize(const bsvi_bnn* b, float* out_dev, uint32_t n_samples_global, void* stream);
