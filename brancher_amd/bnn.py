@@ -34,6 +34,7 @@ ACTIVATIONS = dict(tanh=1, relu=2, sigmoid=3, softplus=4)
 NO_BIAS = 0xFFFFFFFF
 MAX_LAYERS = 8                                                         # BNN_MAX_LAYERS (csrc/bnn_kernel.inc)
 MIDDLE_PATHS = ("mid_gen", "upper_gen", "upper_lds", "upper_mem")      # bsvi_bnn_select::BnnMiddle (csrc/bnn_select.h)
+PREDICT_PATHS = ("global", "lds")                                      # bsvi_bnn_predict_lds
 
 
 class BnnProgram:
@@ -283,10 +284,34 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     prog.dataset = np.ascontiguousarray(Xm, dtype=np.float32)
     prog.labels = np.ascontiguousarray(Ym, dtype=np.float32)
     prog.indices_name = ind_x.name
+    prog.x_name, prog.likelihood_name = x_var.name, k.name       # (engine.posterior_sample: the variables a prediction is keyed by)
     prog.lik_weight, prog.prior_weight, prog.entropy_weight = 1.0, 1.0, 1.0
     prog.n_noise = R
     prog.bmax = 1
     return prog
+
+
+def row_parameters(p, theta=None):
+    """(q loc [R], q scale [R]) of a lowered program at the flat parameter values `theta` (default: the values the program was lowered
+    with) — the uniform table evaluated on the host, in double precision: what `bnn_head_body` leaves in `rowp` on the device"""
+    if theta is None:
+        theta = np.zeros(max(p.n_params, 1), dtype=np.float64)
+        for par, off, size, _ in p.parameters:
+            theta[off:off + size] = par.numpy().reshape(-1)
+    theta = np.asarray(theta, dtype=np.float64)
+    UT = lowering.UT
+    g = {UT["identity"]: lambda x: x, UT["softplus"]: lambda x: np.where(x > 20.0, x, np.log1p(np.exp(np.minimum(x, 20.0)))),
+         UT["sigmoid"]: lambda x: 1.0 / (1.0 + np.exp(-x)), UT["exp"]: np.exp, UT["log"]: np.log, UT["tanh"]: np.tanh,
+         UT["sqrt"]: np.sqrt, UT["square"]: np.square}
+    uni = p.uniform
+    x = np.where(uni["is_param"] != 0, theta[np.minimum(uni["src"], theta.size - 1)],
+                 np.asarray(p.consts, dtype=np.float64)[np.minimum(uni["src"], max(len(p.consts), 1) - 1)] if len(p.consts) else 0.0)
+    values = np.empty(len(uni), dtype=np.float64)
+    for t in np.unique(uni["transform"]):
+        sel = uni["transform"] == t
+        values[sel] = g[int(t)](x[sel])
+    values = uni["a"].astype(np.float64) + uni["b"].astype(np.float64) * values
+    return values[p.row_uniform[0]], values[p.row_uniform[1]]
 
 
 def make_desc(p):
@@ -482,6 +507,85 @@ class CompiledBnn:
             res["f"] = fvals
             if logq is not None:
                 res["lq"] = logq
+        return res
+
+    def predict_path(self):
+        """where the forward-only kernel of `predict` keeps the small tensors and its two activation buffers (csrc/bnn_select.h,
+        predict_lds: from the network's size alone): "lds" or "global\""""
+        kind = int(self.lib.bsvi_bnn_predict_lds(self.handle))
+        if kind not in (0, 1):
+            raise native.NativeError("bsvi_bnn_predict_lds returned %d" % kind)
+        return PREDICT_PATHS[kind]
+
+    def _predict_rows(self, x):
+        """the caller's rows as a contiguous f32 device tensor [M, P]: from [M, P], [M, P, 1] or the reference's [1, M, P, 1]"""
+        a = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x, dtype=np.float32))
+        if a.ndim == 4 and a.shape[0] == 1:
+            a = a[0]
+        if a.ndim == 3 and a.shape[-1] == 1:
+            a = a[..., 0]
+        P = self.program.n_features
+        if a.ndim != 2:
+            raise ValueError("predict takes rows as [M, {P}], [M, {P}, 1] or [1, M, {P}, 1]: got shape {}".format(
+                tuple(x.shape) if hasattr(x, "shape") else np.shape(x), P=P))
+        if a.shape[1] != P:
+            raise ValueError("the rows have {} features, the model was built on {}".format(a.shape[1], P))
+        if a.shape[0] < 1:
+            raise ValueError("predict needs at least one row")
+        return a.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def predict(self, x, number_samples, seed=None, offset=None, noise=None, want_outputs=False, want_draws=False, want_noise=False,
+                rows_per_pass=None, sample_base=0):
+        """Posterior predictive on rows the caller hands in (bsvi_bnn_predict): `number_samples` weight sets from the CURRENT posterior
+        — the draw of a training launch at the same (seed, offset, sample_base), or `noise` ([n_rows, N], or named as the oracle
+        takes it) — and the chain forward on every row of `x`.  Device tensors: "probs" [N, M, C] (softmax probabilities | sigmoid of
+        the logit | the Normal's loc), "mean" [M, C] (their mean over the samples, fixed order), "var" [M, C] (Normal likelihood only:
+        population variance of the loc over the samples + sigma^2), and on request "outputs" [N, M, C] (logits | loc), "draws"
+        [N, M, C] (one draw of the likelihood per sample and row: one-hot | 0 / 1 | real) and "noise" [n_rows, N] (the eps drawn).
+        offset=None draws from the sampling range (1 << 62) + tick, as the samplers of the engine do; `self.iteration`, `self.out` and
+        the gradients are left alone.  Not sharded: every rank computes all N samples, no collective.  rows_per_pass (a multiple of
+        32; default: from the network's size) bounds the workspace and changes no value."""
+        p, dev, N = self.program, self.device, int(number_samples)
+        if N < 1:
+            raise ValueError("number_samples must be at least 1")
+        rows = self._predict_rows(x)
+        M, Cn = int(rows.shape[0]), p.n_classes
+        rpp = 0 if rows_per_pass is None else int(rows_per_pass)
+        if rpp < 0 or rpp % 32:
+            raise ValueError("rows_per_pass must be a multiple of 32: got {}".format(rows_per_pass))
+        if offset is None:
+            _engine._sample_tick[0] += 1
+            offset = (1 << 62) + _engine._sample_tick[0]
+        if getattr(p, "estimator", "pathwise") == "taylor1":
+            noise = self._zero_noise(N)                       # (f at the posterior's means: `_args`)
+        noise_t = self._noise_tensor(noise, N, 0, N)
+        if noise_t is not None and tuple(noise_t.shape) != (p.n_noise, N):
+            raise ValueError("noise must be [{}, {}]: got {}".format(p.n_noise, N, tuple(noise_t.shape)))
+        if not isinstance(seed, int) or seed is True:
+            seed = _engine.shared_seed(seed, dev)
+        key = (N, M, rpp)
+        ws = self.__dict__.get("_predict_ws")
+        if ws is None or ws[0] != key:                        # (one workspace kept: the shape of the last call)
+            ws = self._predict_ws = (key, torch.zeros(int(self.lib.bsvi_bnn_predict_workspace_bytes(self.handle, N, M, rpp)),
+                                                      dtype=torch.uint8, device=dev))
+        new = lambda *shape: torch.empty(shape, device=dev)
+        probs, mean = new(N, M, Cn), new(M, Cn)
+        var = new(M, Cn) if p.likelihood == LIK_NORMAL else None
+        outputs = new(N, M, Cn) if want_outputs else None
+        draws = new(N, M, Cn) if want_draws else None
+        noise_o = new(p.n_noise, N) if want_noise else None
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        args = native.BnnPredictArgs(params_dev=ptr(self.params), x_dev=ptr(rows), noise_dev=ptr(noise_t), seed=int(seed),
+                                     offset=int(offset), n_samples_local=N, sample_base=int(sample_base), n_rows=M, rows_per_pass=rpp,
+                                     z_out=ptr(outputs), p_out=ptr(probs), mean_out=ptr(mean), var_out=ptr(var), draw_out=ptr(draws),
+                                     noise_out=ptr(noise_o), workspace_dev=ptr(ws[1]), stream=self._stream())
+        native.check(self.lib.bsvi_bnn_predict(self.handle, C.byref(args)))
+        res = dict(probs=probs, mean=mean, n_rows=M, seed=int(seed), offset=int(offset),
+                   rows_per_pass=int(self.lib.bsvi_bnn_predict_rows_per_pass(self.handle, N, M, rpp)),
+                   data_path="bf16x3" if self.lib.bsvi_bnn_predict_last_exact() == 1 else "f32")
+        for k, t in (("var", var), ("outputs", outputs), ("draws", draws), ("noise", noise_o)):
+            if t is not None:
+                res[k] = t
         return res
 
     def evaluate_weighted(self, number_samples, f_weight, q_weight, seed, offset, noise=None, minibatch=None):

@@ -1304,3 +1304,311 @@ extern "C" int bsvi_bnn_step(const bsvi_bnn* p, const bsvi_bnn_args* a, const bs
     HIP_TRY(hipGetLastError());
     return BSVI_OK;
 }
+
+// ---- posterior predictive (bsvi_bnn_predict, include/bsvi.h) ----------------------------------------------------------------
+// N weight sets from the current posterior (bnn_draw as it is: the same weights a training launch of (seed, offset, sample_base) sees;
+// its per-sample prior / log q partials are written and never read), the chain forward on rows the CALLER hands in, in passes of
+// rows_pass rows:
+//   bnn_predict_exact   are all values of x exactly bf16?  (one flag, read back by the host once per call: it chooses the product)
+//   bnn_predict_head    row parameters, sigma of the Normal likelihood
+//   bnn_draw            once per call
+//   per pass:  bnn_predict_gather   x_new rows as the first product's operand (bf16 [rows][Kp] | f32 [rows][P_ld]; pads zero)
+//              product 1            bsvi_xgemm_nt | bsvi_gemm_f32, as bnn_launch makes them: a1 [rows][(h, n)]
+//              bnn_predict_fwd      one thread per (sample, row): bias + activation, the upper layers (TWO activation buffers of the
+//                                   widest layer, ping-pong), the head: z, p, and the likelihood's draw
+//              bnn_predict_reduce   one thread per (row, output): mean over the samples (and var), sample order, double precision
+// The likelihood's noise is a Philox stream of its own (philox.h): c0 = global sample, c1 = row m of x_new, c2 / c3 = the offset, the
+// key word k0 xor-ed with BNN_KEY_PREDICT — no training stream of the same seed has that key.
+//   Categorical   inverse CDF on the STORED f32 probabilities: partial sums in class order c = 0, 1, ... in single precision, the first
+//                 class whose partial sum is >= u01(word 0), the last class if none is
+//   Bernoulli     u01(word 0) < p
+//   Normal        loc_c + sigma_c e: output c takes normal c & 3 of the four box_muller_fast normals ((x, y) -> 0, 1; (z, w) -> 2, 3) of
+//                 the call whose key word k1 is xor-ed with c >> 2: one call serves four outputs, no counter is used twice
+constexpr uint32_t BNN_KEY_PREDICT = 0x2545F491u;
+
+struct BnnPredict {
+    const float* x_new;          // [M][P]
+    uint32_t M, m0, rows_pass;   // rows of the call, first row of this pass, rows of a pass (a multiple of 32)
+    const float* a1;             // [rows_pass][NC]
+    float* act;                  // global arm: [2 max_width][rows_pass][n_pad]
+    uint32_t max_width;
+    const float* sg;             // Normal: sigma [C]
+    uint32_t* flag;
+    float* z_out; float* draw_out;        // [n_local][M][C] or null
+    float* p;                    // the pass's p: element (n, j, c) of the pass at p[n * p_stride + j * C + c]
+    size_t p_stride;
+    float* mean_out; float* var_out;      // [M][C] or null
+};
+
+// grid: any, block 256.  flag must hold 1; a value with low mantissa bits clears it (every writer writes the same 0)
+__global__ void __launch_bounds__(256) bnn_predict_exact(const float* __restrict__ x, const size_t n, uint32_t* flag) {
+    bool bad = false;
+    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u)
+        bad = bad || (__float_as_uint(x[i]) & 0xFFFFu) != 0u;
+    if (bad) *flag = 0u;
+}
+
+// threads: max(R, C)
+__global__ void __launch_bounds__(256) bnn_predict_head(const BParams Q, const BnnPredict V) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < Q.R) {
+#pragma unroll
+        for (uint32_t q = 0; q < 4u; ++q) Q.rowp[(size_t)q * Q.R + i] = bnn_uniform_value(Q, Q.row_uniform[(size_t)q * Q.R + i]);
+    }
+    if (Q.likelihood == BSVI_LIK_NORMAL && i < Q.C) const_cast<float*>(V.sg)[i] = bnn_uniform_value(Q, Q.scale_u + i * Q.scale_stride);
+}
+
+// row m0 + j of x_new as row j of the pass's operand, as bnn_gather_body writes the minibatch's (no transpose: there is no second
+// product).  Rows from M on and columns from P on are zero; nothing is read beyond x_new[M][P].  blocks: rows_pass x ceil(Kp / 256)
+__global__ void __launch_bounds__(256) bnn_predict_gather(const BParams Q, const BnnPredict V, const uint32_t gy) {
+    const uint32_t j = blockIdx.x / gy, p = (blockIdx.x % gy) * 256u + threadIdx.x, m = V.m0 + j;
+    const float v = (m < V.M && p < Q.P) ? V.x_new[(size_t)m * Q.P + p] : 0.0f;
+    if (Q.exact) {
+        if (p < Q.Kp) Q.Xb_bf[(size_t)j * Q.Kp + p] = dense_bf16_bits(v);
+    } else if (p < Q.P_ld) {
+        Q.Xb[(size_t)j * Q.P_ld + p] = v;
+    }
+}
+
+// One thread per (sample n, row j of the pass), lanes along n; a workgroup = 64 samples x 8 rows (a wave takes two), as bnn_upper.
+// LDSW: the small tensors of the 64 samples staged once per workgroup, transposed ([row][sample]), and the thread's two activation
+// buffers a column of LDS each ([unit][thread]); else both in global memory.  The arithmetic of the forward sweep is bnn_upper's, in
+// its order.  Padded samples (n >= n_local) and padded rows (m >= M) compute on zeros and write nothing.
+// grid: ceil(n_pad / 64) x ceil(rows_pass / 8), block 256
+template <bool LDSW>
+__global__ void __launch_bounds__(256) bnn_predict_fwd(const BParams Q, const BnnPredict V) {
+    float* const wl = g_lds;                                      // [Rs][65]
+    float* const ya = g_lds + (size_t)Q.Rs * 65u + threadIdx.x;   // buffer 0 [max_width][256] of this thread, then buffer 1
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, n = blockIdx.x * 64u + lane;
+    if (LDSW) {
+        for (uint32_t i = threadIdx.x; i < 64u * Q.Rs; i += 256u) {
+            const uint32_t sn = i / Q.Rs, r = i - sn * Q.Rs;
+            wl[r * 65u + sn] = Q.Wsm[(size_t)(blockIdx.x * 64u + sn) * Q.Rs + r];
+        }
+        __syncthreads();
+    }
+    const float* const wsm = Q.Wsm + (size_t)n * Q.Rs;
+    auto W = [&](uint32_t r) { return LDSW ? wl[r * 65u + lane] : wsm[r]; };
+    const BnnLayerDev L1 = Q.layer[0], LL = Q.layer[Q.n_layers - 1];
+    const uint32_t C = LL.rows;
+    for (uint32_t bi = 0; bi < 2u; ++bi) {
+        const uint32_t j = blockIdx.y * 8u + wave * 2u + bi;
+        if (j >= V.rows_pass) continue;
+        const uint32_t m = V.m0 + j;
+        const bool live = n < Q.n_local && m < V.M;
+        auto Y = [&](uint32_t buf, uint32_t u) -> float& {
+            return LDSW ? ya[(size_t)(buf * V.max_width + u) * 256u]
+                        : V.act[((size_t)(buf * V.max_width + u) * V.rows_pass + j) * Q.n_pad + n];
+        };
+        uint32_t cur = 0;
+        for (uint32_t h = 0; h < L1.rows; ++h) {
+            float v = V.a1[(size_t)j * Q.NC + (size_t)h * Q.n_pad + n];
+            if (L1.b0 != 0xFFFFFFFFu) v += W(L1.b0 - Q.R1 + h);
+            Y(cur, h) = bnn_act(L1.act, v);
+        }
+        for (uint32_t l = 1; l < Q.n_layers; ++l) {
+            const BnnLayerDev L = Q.layer[l];
+            for (uint32_t i = 0; i < L.rows; ++i) {
+                float s = L.b0 != 0xFFFFFFFFu ? W(L.b0 - Q.R1 + i) : 0.0f;
+                // (unrolled by four: eight reads in flight in front of four dependent FMAs, the additions in the same order)
+#pragma unroll 4
+                for (uint32_t k = 0; k < L.cols; ++k) s += W(L.w0 - Q.R1 + i * L.cols + k) * Y(cur, k);
+                Y(cur ^ 1u, i) = bnn_act(L.act, s);
+            }
+            cur ^= 1u;
+        }
+        if (!live) continue;
+        const size_t at = ((size_t)n * V.M + m) * C;
+        float* const pp = V.p + (size_t)n * V.p_stride + (size_t)j * C;
+        if (V.z_out) for (uint32_t c = 0; c < C; ++c) V.z_out[at + c] = Y(cur, c);
+        u32x4 x = {0u, 0u, 0u, 0u};
+        if (V.draw_out && Q.likelihood != BSVI_LIK_NORMAL)
+            x = philox4x32(Q.sample_base + n, m, Q.offset_lo, Q.offset_hi, Q.seed_lo ^ BNN_KEY_PREDICT, Q.seed_hi);
+        if (Q.likelihood == BSVI_LIK_NORMAL) {
+            for (uint32_t c = 0; c < C; ++c) pp[c] = Y(cur, c);
+            if (V.draw_out) {
+                for (uint32_t c0 = 0; c0 < C; c0 += 4u) {
+                    const u32x4 w = philox4x32(Q.sample_base + n, m, Q.offset_lo, Q.offset_hi, Q.seed_lo ^ BNN_KEY_PREDICT, Q.seed_hi ^ (c0 >> 2));
+                    float e[4];
+                    box_muller_fast(w.x, w.y, e[0], e[1]);
+                    box_muller_fast(w.z, w.w, e[2], e[3]);
+                    for (uint32_t c = c0; c < C && c < c0 + 4u; ++c) V.draw_out[at + c] = Y(cur, c) + V.sg[c] * e[c - c0];
+                }
+            }
+        } else if (Q.likelihood == BSVI_LIK_CATEGORICAL) {
+            // log-softmax as bnn_upper does it, then expf: the probabilities as they are stored
+            float mx = -INFINITY;
+            for (uint32_t c = 0; c < C; ++c) mx = fmaxf(mx, Y(cur, c));
+            float se = 0.0f;
+            for (uint32_t c = 0; c < C; ++c) se += expf(Y(cur, c) - mx);
+            const float lse = mx + logf(se), u = u01(x.x);
+            float cum = 0.0f;
+            uint32_t pick = C - 1u;
+            bool found = false;
+            for (uint32_t c = 0; c < C; ++c) {
+                const float pc = expf(Y(cur, c) - lse);
+                pp[c] = pc;
+                cum += pc;
+                if (!found && cum >= u) { pick = c; found = true; }
+            }
+            if (V.draw_out) for (uint32_t c = 0; c < C; ++c) V.draw_out[at + c] = c == pick ? 1.0f : 0.0f;
+        } else {
+            const float pb = sigmoidf_(Y(cur, 0));
+            pp[0] = pb;
+            if (V.draw_out) V.draw_out[at] = u01(x.x) < pb ? 1.0f : 0.0f;
+        }
+    }
+}
+
+// mean over the samples of p (and, Normal: the population variance of the loc about that mean, plus sigma_c^2) for the rows of a pass:
+// one thread per (row j, output c), the samples in order n = 0, 1, ... in double precision — no atomics, and nothing that depends on
+// how the rows were cut into passes.  grid: ceil(rows * C / 256), block 256
+__global__ void __launch_bounds__(256) bnn_predict_reduce(const BParams Q, const BnnPredict V, const uint32_t rows) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x, C = Q.C;
+    if (i >= rows * C) return;
+    const uint32_t c = i % C;
+    const float* const src = V.p + i;
+    double s = 0.0;
+    for (uint32_t n = 0; n < Q.n_local; ++n) s += (double)src[(size_t)n * V.p_stride];
+    const double mean = s / (double)Q.n_local;
+    const size_t at = (size_t)V.m0 * C + i;
+    if (V.mean_out) V.mean_out[at] = (float)mean;
+    if (V.var_out) {
+        double q = 0.0;
+        for (uint32_t n = 0; n < Q.n_local; ++n) { const double d = (double)src[(size_t)n * V.p_stride] - mean; q += d * d; }
+        const double sigma = (double)V.sg[c];
+        V.var_out[at] = (float)(q / (double)Q.n_local + sigma * sigma);
+    }
+}
+
+static uint32_t bnn_max_width(const bsvi_bnn* p) {
+    uint32_t w = 0;
+    for (const bsvi_bnn_layer& l : p->layers) w = std::max(w, l.rows);
+    return w;
+}
+
+static bsvi_bnn_select::PredictLayout bnn_predict_layout(const bsvi_bnn* p, uint32_t n_local, uint32_t n_rows, uint32_t rows_per_pass) {
+    return bsvi_bnn_select::predict_layout(p->R, p->Rs, p->P, p->C, p->H1, bnn_max_width(p), n_local, n_rows, rows_per_pass);
+}
+
+extern "C" size_t bsvi_bnn_predict_args_size(void) { return sizeof(bsvi_bnn_predict_args); }
+
+extern "C" size_t bsvi_bnn_predict_workspace_bytes(const bsvi_bnn* p, uint32_t n_samples_local, uint32_t n_rows, uint32_t rows_per_pass) {
+    if (!p || !n_samples_local || !n_rows || rows_per_pass % 32u) return 0;
+    return bnn_predict_layout(p, n_samples_local, n_rows, rows_per_pass).total;
+}
+
+extern "C" uint32_t bsvi_bnn_predict_rows_per_pass(const bsvi_bnn* p, uint32_t n_samples_local, uint32_t n_rows, uint32_t rows_per_pass) {
+    if (!p || !n_samples_local || !n_rows || rows_per_pass % 32u) return 0;
+    return bnn_predict_layout(p, n_samples_local, n_rows, rows_per_pass).rows_pass;
+}
+
+extern "C" int bsvi_bnn_predict_lds(const bsvi_bnn* p) {
+    return p ? (bsvi_bnn_select::predict_lds(p->Rs, bnn_max_width(p)) ? 1 : 0) : -1;
+}
+
+static thread_local int bnn_predict_last_exact = -1;
+extern "C" int bsvi_bnn_predict_last_exact(void) { return bnn_predict_last_exact; }
+
+extern "C" int bsvi_bnn_predict(const bsvi_bnn* p, const bsvi_bnn_predict_args* a) {
+    // every check in front of any device work
+    if (!a) return fail(BSVI_ERR_INVALID, "bsvi_bnn_predict: null argument");
+    BSVI_CHECK_STRUCT(a, bsvi_bnn_predict_args);
+    if (!a->x_dev) return fail(BSVI_ERR_INVALID, "bsvi_bnn_predict: x_dev is null");
+    if (!a->n_rows) return fail(BSVI_ERR_INVALID, "bsvi_bnn_predict: n_rows is 0");
+    if (!a->n_samples_local) return fail(BSVI_ERR_INVALID, "bsvi_bnn_predict: zero samples");
+    if (a->rows_per_pass % 32u) return fail(BSVI_ERR_INVALID, "bsvi_bnn_predict: rows_per_pass must be a multiple of 32 (0: the default)");
+    if (!a->workspace_dev) return fail(BSVI_ERR_INVALID, "bsvi_bnn_predict: workspace_dev is null");
+    if (!p) return fail(BSVI_ERR_INVALID, "bsvi_bnn_predict: null handle");
+    if (!a->params_dev && p->d.n_params) return fail(BSVI_ERR_INVALID, "bsvi_bnn_predict: params_dev is null");
+    if (a->var_out && p->d.likelihood != BSVI_LIK_NORMAL)
+        return fail(BSVI_ERR_INVALID, "bsvi_bnn_predict: var_out is for the Normal likelihood (a classifier's variance is p (1 - p) of mean_out)");
+    const bsvi_bnn_select::PredictLayout L = bnn_predict_layout(p, a->n_samples_local, a->n_rows, a->rows_per_pass);
+    if ((uint64_t)L.NC * (uint64_t)std::max(p->Kp, L.rows_pass) >= (1ull << 31))
+        return fail(BSVI_ERR_UNSUPPORTED, "bsvi_bnn_predict: number_samples x hidden units x max(features, rows_per_pass) beyond the 32-bit index range of the product kernels");
+    if ((uint64_t)a->n_samples_local * a->n_rows * p->C >= (1ull << 40))
+        return fail(BSVI_ERR_UNSUPPORTED, "bsvi_bnn_predict: number_samples x rows x outputs too large");
+    const uint32_t max_width = bnn_max_width(p);
+    const bool lds = bsvi_bnn_select::predict_lds(p->Rs, max_width);
+    hipStream_t s = (hipStream_t)a->stream;
+    char* ws = (char*)a->workspace_dev;
+
+    BParams Q;
+    memset(&Q, 0, sizeof Q);
+    Q.uniform = p->uniform; Q.consts = p->consts; Q.params = a->params_dev; Q.row_uniform = p->row_uniform;
+    Q.n_layers = p->d.n_layers;
+    for (uint32_t l = 0; l < Q.n_layers; ++l) {
+        const bsvi_bnn_layer& S = p->layers[l];
+        BnnLayerDev& D = Q.layer[l];
+        D.rows = S.rows; D.cols = S.cols; D.w0 = S.weight_row0; D.b0 = S.bias_row0; D.act = S.activation;
+    }
+    Q.R = p->R; Q.R1 = p->R1; Q.Rs = p->Rs ? p->Rs : 1; Q.P = p->P; Q.C = p->C; Q.H1 = p->H1;
+    Q.Kp = p->Kp; Q.P_ld = p->P_ld; Q.n_local = a->n_samples_local; Q.n_pad = L.n_pad; Q.n_global = a->n_samples_local;
+    Q.sample_base = a->sample_base; Q.NC = L.NC; Q.likelihood = p->d.likelihood;
+    Q.LC = p->LC; Q.scale_u = p->scale_u; Q.scale_stride = p->scale_stride;
+    Q.seed_lo = (uint32_t)a->seed; Q.seed_hi = (uint32_t)(a->seed >> 32); Q.offset_lo = (uint32_t)a->offset; Q.offset_hi = (uint32_t)(a->offset >> 32);
+    Q.noise_in = a->noise_dev; Q.noise_out = a->noise_out;
+    Q.rowp = (float*)(ws + L.rowp); Q.Wsm = (float*)(ws + L.Wsm);
+    Q.W1f = (float*)(ws + L.W1); Q.Wp = (uint16_t*)(ws + L.W1);
+    Q.pv_part = (float*)(ws + L.part); Q.qv_part = Q.pv_part + (size_t)L.row_chunks * L.n_pad;
+    Q.Xb = (float*)(ws + L.X); Q.Xb_bf = (uint16_t*)(ws + L.X);
+    Q.row_chunks = L.row_chunks;
+
+    BnnPredict V;
+    memset(&V, 0, sizeof V);
+    V.x_new = a->x_dev; V.M = a->n_rows; V.rows_pass = L.rows_pass; V.a1 = (const float*)(ws + L.a1); V.act = (float*)(ws + L.act);
+    V.max_width = max_width; V.sg = (const float*)(ws + L.sg); V.flag = (uint32_t*)(ws + L.flag);
+    V.z_out = a->z_out; V.draw_out = a->draw_out; V.mean_out = a->mean_out; V.var_out = a->var_out;
+
+    // exact data?  decided for the rows handed in, on the device, read back once (BSVI_DENSE_XGEMM=0: the f32 kernels, as at create)
+    bool exact = false;
+    {
+        const char* xe = getenv("BSVI_DENSE_XGEMM");
+        if (!(xe && xe[0] == '0')) {
+            const uint32_t one = 1u;
+            uint32_t flag = 0u;
+            const size_t n_values = (size_t)a->n_rows * p->P;
+            HIP_TRY(hipMemcpyAsync(V.flag, &one, 4, hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(bnn_predict_exact, dim3((unsigned)std::min<size_t>((n_values + 255) / 256, 1024)), dim3(256), 0, s, a->x_dev, n_values, V.flag);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(&flag, V.flag, 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            exact = flag == 1u;
+        }
+    }
+    Q.exact = exact ? 1u : 0u;
+    bnn_predict_last_exact = exact ? 1 : 0;
+    if (lds) {
+        static std::mutex mu;
+        static size_t asked = 0;
+        const size_t bytes = bsvi_bnn_select::predict_lds_bytes(p->Rs, max_width);
+        std::lock_guard<std::mutex> lock(mu);
+        if (bytes > asked) {
+            HIP_TRY(hipFuncSetAttribute((const void*)bnn_predict_fwd<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+            asked = bytes;
+        }
+    }
+    const uint32_t head_n = std::max(Q.R, Q.C);
+    hipLaunchKernelGGL(bnn_predict_head, dim3((head_n + 255) / 256), dim3(256), 0, s, Q, V);
+    hipLaunchKernelGGL(bnn_draw, dim3(L.row_chunks, (Q.n_pad + 3u) / 4u), dim3(256), 0, s, Q);
+    HIP_TRY(hipGetLastError());
+    const uint32_t gy = (std::max(Q.Kp, Q.P_ld) + 255) / 256;
+    for (uint32_t m0 = 0; m0 < a->n_rows; m0 += L.rows_pass) {
+        const uint32_t rows = std::min(L.rows_pass, a->n_rows - m0);
+        V.m0 = m0;
+        if (a->p_out) { V.p = a->p_out + (size_t)m0 * p->C; V.p_stride = (size_t)a->n_rows * p->C; }
+        else { V.p = (float*)(ws + L.p); V.p_stride = (size_t)L.rows_pass * p->C; }
+        hipLaunchKernelGGL(bnn_predict_gather, dim3(L.rows_pass * gy), dim3(256), 0, s, Q, V, gy);
+        int rc;
+        if (exact) rc = bsvi_xgemm_nt(Q.Xb_bf, nullptr, Q.Wp, (long)Q.NC * Q.Kp, const_cast<float*>(V.a1), (int)Q.NC, (int)L.rows_pass, (int)Q.NC, (int)Q.Kp, s);
+        else rc = bsvi_gemm_f32(0, Q.Xb, (int)Q.P_ld, Q.W1f, (int)Q.P_ld, const_cast<float*>(V.a1), (int)Q.NC, (int)L.rows_pass, (int)Q.NC, (int)Q.P, s);
+        if (rc) return rc;
+        const dim3 grid(Q.n_pad / 64, (L.rows_pass + 7) / 8);
+        if (lds) hipLaunchKernelGGL(bnn_predict_fwd<true>, grid, dim3(256), bsvi_bnn_select::predict_lds_bytes(p->Rs, max_width), s, Q, V);
+        else hipLaunchKernelGGL(bnn_predict_fwd<false>, grid, dim3(256), 0, s, Q, V);
+        if (a->mean_out || a->var_out)
+            hipLaunchKernelGGL(bnn_predict_reduce, dim3((rows * p->C + 255) / 256), dim3(256), 0, s, Q, V, rows);
+        HIP_TRY(hipGetLastError());
+    }
+    return BSVI_OK;
+}

@@ -9,6 +9,13 @@
 // the bound of the dense path's two launches (a drawing wave per SIMD at ~140 vector instructions per four normals), and
 // three rounds are ~20 of them: config 4 103.8 -> 101.1 us per iteration (profiles/r6/philox_rounds.txt).  Parity is always on the
 // noise a kernel REPORTS (the oracle replays it), so nothing else moves; seeds of earlier rounds give other streams.
+//
+// The posterior-predictive pass of the Bayesian neural networks (bnn_kernel.inc, bsvi_bnn_predict) draws from the likelihood on a
+// stream of its own:  c0 = global sample index, c1 = row m of the caller's x, c2 / c3 = the 64-bit offset, key word k0 = seed low ^
+// 0x2545f491 (another constant than the three of the minibatch / drawn-data streams, and not 0: no stream of the same seed has this
+// key), k1 = seed high ^ call.  Categorical and Bernoulli read u01(word 0) of call 0; the Normal likelihood's output c takes normal
+// c & 3 of the four box_muller_fast normals ((x, y) -> 0, 1; (z, w) -> 2, 3) of call c >> 2.  The weights of that pass are the BNN
+// path's ordinary draw (c1 = (row >> 2) | 0x40000000, the seed as it is).
 #pragma once
 #if !defined(__HIPCC_RTC__)
 #include <hip/hip_runtime.h>

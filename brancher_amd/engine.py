@@ -1311,6 +1311,90 @@ def _amortized_posterior_sample(model, compiled, number_samples):
             by_name[p.latent_name]: z.reshape(N, p.batch_size, p.latent_dim)}
 
 
+def _bnn_predictor(model, compiled):
+    """the engine that answers a prediction of a Bayesian neural network: the model's own when it trains on `bnn.CompiledBnn`; for a
+    network small enough for the scalar engine (which trains it, and whose sampler still refuses the minibatch variables) a
+    CompiledBnn kept for prediction alone — the parameters stay bound to the engine that trains them and their current values are
+    copied in before every call.  None: not a network of the family."""
+    from brancher_amd import bnn
+    if type(compiled).__name__ == "CompiledBnn":
+        return compiled
+    posterior = model.posterior_model
+    kept = model.__dict__.get("_bnn_predictor")
+    if kept is None or kept[0] is not posterior:
+        try:
+            program = bnn.lower_bnn(model, posterior)
+        except lowering.LoweringError:
+            return None
+        bound = [(par, par._store, par._offset) for par, _, _, _ in program.parameters]
+        predictor = bnn.CompiledBnn(model, posterior, program=program)
+        for par, store, offset in bound:                   # (the constructor bound them to itself)
+            if store is None:
+                par.unbind()
+            else:
+                par.bind(store, offset)
+        kept = model.__dict__["_bnn_predictor"] = (posterior, predictor)
+    predictor = kept[1]
+    theta = np.zeros(max(predictor.n_params, 1), dtype=np.float32)
+    for par, off, size, _ in predictor.program.parameters:
+        theta[off:off + size] = par.numpy().reshape(-1)
+    predictor.params.copy_(torch.from_numpy(theta[:predictor.params.numel()]).to(predictor.device))
+    return predictor
+
+
+def _bnn_posterior_sample(model, compiled, number_samples, input_values):
+    """`ProbabilisticModel._get_posterior_sample` of a Bayesian neural network (variables.py:796-805; the prediction step of
+    tests/test_MNIST_bayesian_neural_network.py:79): N weight sets from the posterior and the likelihood's draw on the rows of
+    `input_values[x]` — or, without them, on one minibatch of the dataset at the call's (seed, offset), as the reference draws one —
+    through `CompiledBnn.predict`.  Keyed by the JOINT model's variables in the reference's shapes: every latent tensor
+    [N, 1, rows, cols] (what was drawn: the reported noise through `named_noise`, then mu + s eps), x as given ([N, B, P, 1] for the
+    minibatch), the likelihood variable one-hot [N, M, C, 1] | 0 / 1 [N, M, 1, 1] | real [N, M, C, 1], and the roots above them,
+    tiled (`RootVariable._get_sample`, variables.py:367-375)."""
+    from brancher_amd import bnn
+    from brancher_amd.variables import RootVariable
+    p, dev, N = compiled.program, compiled.device, int(number_samples)
+    by_name = {v.name: v for v in model.flatten()}
+    x_var, lik_var = by_name[p.x_name], by_name[p.likelihood_name]
+    _sample_tick[0] += 1
+    seed, offset = int(shared_seed(None, dev)), (1 << 62) + _sample_tick[0]
+    given = _given(input_values, x_var)
+    out = {}
+    if given is not None:
+        rows = torch.from_numpy(np.ascontiguousarray(given, dtype=np.float32))
+    else:
+        # the minibatch of (seed, offset) through the launch that draws it; the caller's gradients are left alone
+        keep, valid = compiled.out.clone(), compiled.grads_valid
+        idx = compiled.evaluate(N, seed=seed, offset=offset, want_indices=True)["indices"].long()
+        compiled.out.copy_(keep)
+        compiled.grads_valid = valid
+        rows = torch.from_numpy(p.dataset).to(dev)[idx]
+        out[by_name[p.indices_name]] = idx
+        out[x_var] = rows.reshape(1, p.batch_size, p.n_features, 1).expand(N, -1, -1, -1).contiguous()
+    res = compiled.predict(rows, N, seed=seed, offset=offset, want_draws=True, want_noise=True)
+    M = res["n_rows"]
+    out[lik_var] = res["draws"].reshape(N, M, p.n_classes, 1)
+    loc, scale = bnn.row_parameters(p, compiled.params.detach().cpu().numpy())
+    eps = res["noise"].cpu().numpy()
+    weights = (loc.astype(np.float32)[:, None] + scale.astype(np.float32)[:, None] * eps).astype(np.float32)
+    for name, value in compiled.named_noise(weights, N).items():
+        out[by_name[name]] = torch.from_numpy(np.ascontiguousarray(value)).to(dev)
+    # the roots above the likelihood, not looking past a variable the caller gave
+    seen, stack = set(), [lik_var]
+    while stack:
+        v = stack.pop()
+        if v in seen:
+            continue
+        seen.add(v)
+        if v is x_var and given is not None:
+            continue
+        if isinstance(v, RootVariable) and v not in out and isinstance(v.value, (np.ndarray, list, tuple)):
+            # (a list: the row numbers behind RandomIndices, which the reference hands back as they are)
+            t = torch.from_numpy(np.ascontiguousarray(v.value, dtype=np.float32)).to(dev)
+            out[v] = t.expand((N,) + tuple(t.shape[1:])).contiguous() if t.ndim > 1 and t.shape[0] == 1 else t
+        stack.extend(v.parents)
+    return out
+
+
 def sample_model(model, number_samples, observed=False, input_values={}):
     """`ProbabilisticModel._get_sample` (variables.py:732-742)."""
     if observed:
@@ -1341,13 +1425,19 @@ def posterior_sample(model, number_samples, input_values={}):
     try:
         raw = _run_sampler(model, model.posterior_model, number_samples, input_values)
     except lowering.LoweringError as scalar_error:
+        # the scalar sampler serves small graphs; an amortised model and a Bayesian neural network answer from their own engines
         try:
-            compiled = _amortized_engine(model)
+            compiled = compile_model(model, model.posterior_model, None) if getattr(model, "posterior_model", None) else None
         except lowering.LoweringError:
             compiled = None
+        if compiled is not None and type(compiled).__name__ != "CompiledAmortized":
+            compiled = _bnn_predictor(model, compiled)
         if compiled is None:
             raise scalar_error
-        out = _amortized_posterior_sample(model, compiled, number_samples)
+        if type(compiled).__name__ == "CompiledBnn":
+            out = _bnn_posterior_sample(model, compiled, number_samples, input_values)
+        else:
+            out = _amortized_posterior_sample(model, compiled, number_samples)
         for var, value in (input_values or {}).items():
             out[var] = value if torch.is_tensor(value) else torch.as_tensor(np.asarray(value, dtype=np.float32))
         return out
@@ -1372,7 +1462,14 @@ def get_sample_frame(model, number_samples, input_values={}):
 
 
 def get_posterior_sample_frame(model, number_samples, input_values={}):
-    return _frame(posterior_sample(model, number_samples, input_values))
+    sample = posterior_sample(model, number_samples, input_values)
+    # a value the caller gave once for every sample ([1, ...]) takes a row per sample, as the reference's `reformat_sampler_input`
+    # tiles it in front of the call (utilities.py:269-271): a frame's columns have one length
+    for var in list((input_values or {}).keys()):
+        value = sample.get(var)
+        if torch.is_tensor(value) and value.ndim > 0 and value.shape[0] == 1 and int(number_samples) > 1:
+            sample[var] = value.expand((int(number_samples),) + tuple(value.shape[1:]))
+    return _frame(sample)
 
 
 def importance_log_weights(joint_model, posterior_model, q_samples):

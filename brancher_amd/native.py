@@ -190,6 +190,26 @@ EXPORTS.update({
 })
 
 
+class BnnPredictArgs(Sized):
+    """bsvi_bnn_predict_args (no bsvi_struct_kind of its own: load() checks it against bsvi_bnn_predict_args_size())"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32),
+                ("params_dev", C.c_void_p), ("x_dev", C.c_void_p), ("noise_dev", C.c_void_p),
+                ("seed", C.c_uint64), ("offset", C.c_uint64),
+                ("n_samples_local", C.c_uint32), ("sample_base", C.c_uint32), ("n_rows", C.c_uint32), ("rows_per_pass", C.c_uint32),
+                ("z_out", C.c_void_p), ("p_out", C.c_void_p), ("mean_out", C.c_void_p), ("var_out", C.c_void_p),
+                ("draw_out", C.c_void_p), ("noise_out", C.c_void_p), ("workspace_dev", C.c_void_p), ("stream", C.c_void_p)]
+
+
+EXPORTS.update({
+    "bsvi_bnn_predict_args_size": (C.c_size_t, []),
+    "bsvi_bnn_predict_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "bsvi_bnn_predict_rows_per_pass": (C.c_uint32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "bsvi_bnn_predict_lds": (C.c_int, [C.c_void_p]),
+    "bsvi_bnn_predict": (C.c_int, [C.c_void_p, C.POINTER(BnnPredictArgs)]),
+    "bsvi_bnn_predict_last_exact": (C.c_int, []),
+})
+
+
 class MlpLayer(C.Structure):
     _fields_ = [("in_value", C.c_uint32), ("out_value", C.c_uint32), ("n_in", C.c_uint32), ("n_out", C.c_uint32),
                 ("weight_off", C.c_uint32), ("bias_off", C.c_uint32), ("activation", C.c_uint32),
@@ -444,6 +464,9 @@ def load():
         if lib.bsvi_sizeof(kind) != C.sizeof(cls):
             raise NativeError("{}: this binding declares {} bytes, libbsvi.so {} (include/bsvi.h and native.py disagree)".format(
                 cls.__name__, C.sizeof(cls), lib.bsvi_sizeof(kind)))
+    if lib.bsvi_bnn_predict_args_size() != C.sizeof(BnnPredictArgs):
+        raise NativeError("BnnPredictArgs: this binding declares {} bytes, libbsvi.so {} (include/bsvi.h and native.py disagree)".format(
+            C.sizeof(BnnPredictArgs), lib.bsvi_bnn_predict_args_size()))
     _lib = lib
     return lib
 

@@ -791,7 +791,7 @@ def _bnn_features(rng, data, dataset_size, n_features):
 
 def build_bayesian_neural_network(api, dataset_size=48, batch_size=30, n_features=784, n_hidden=20, n_classes=10, seed=0,
                                   prior_scale=10., q_scale=0.2, q_scale1=None, q_loc_scale=0.0, pixels="uint8",
-                                  activation="tanh", hidden2=0, widths=None, activations=None):
+                                  activation="tanh", hidden2=0, widths=None, activations=None, teacher=None):
     """`tests/test_MNIST_bayesian_neural_network.py:20-60` of the reference: a one-hidden-layer network whose weight matrices AND
     biases are latent — weights1 [H, P], b1 [H, 1], weights2 [C, H], b2 [C, 1], priors N(0, 10), a mean-field Normal posterior
     over all four (scale 0.2) — `tanh(matmul(weights1, x) + b1)`, `matmul(weights2, hidden) + b2` as the logits of an observed
@@ -802,7 +802,9 @@ def build_bayesian_neural_network(api, dataset_size=48, batch_size=30, n_feature
     q_loc_scale: posterior means drawn at that many posterior scales from zero; hidden2 > 0: a second hidden layer.
     widths: the full list of layer widths, features first, outputs last (it overrides n_features, n_hidden, hidden2 and n_classes: any
     depth); activations: one name per hidden layer (default: `activation` everywhere).  pixels="integers" / "normal": the features of
-    `build_bnn_regression` (-3 .. 3, exactly bf16 | standard normal)."""
+    `build_bnn_regression` (-3 .. 3, exactly bf16 | standard normal).  teacher: an integer — the labels are what a fixed random linear
+    map of the centred features (drawn from that seed, whatever `seed` is) ranks highest, so that there is something to learn and a
+    second build with another `seed` is held-out data of the same task (examples/bnn_predict.py); None: uniformly random labels."""
     BF = api.BF
     n_features, n_classes, widths = _bnn_widths(widths, n_features, [n_hidden] + ([hidden2] if hidden2 else []), n_classes)
     if pixels in ("integers", "normal"):
@@ -811,6 +813,9 @@ def build_bayesian_neural_network(api, dataset_size=48, batch_size=30, n_feature
         labels = rng.randint(0, max(n_classes, 2), size=dataset_size)
     else:
         X, labels = logreg_data(dataset_size, n_features, max(n_classes, 2), seed, pixels)
+    if teacher is not None:
+        centre = {"uint8": 127.5, "unit": 0.5}.get(pixels, 0.0)
+        labels = ((X[:, :, 0].astype(np.float64) - centre) @ np.random.RandomState(int(teacher)).normal(size=(n_features, max(n_classes, 2)))).argmax(axis=1)
     if n_classes == 1:
         labels = labels.astype(np.float32).reshape(-1, 1)          # (0 / 1, as minibatch_logistic_regression.py:20 stores them)
     rng = np.random.RandomState(seed + 7)

@@ -612,6 +612,56 @@ int bsvi_bnn_finalize(const bsvi_bnn* b, float* out_dev, uint32_t n_samples_glob
 int bsvi_bnn_step(const bsvi_bnn* b, const bsvi_bnn_args* args, const bsvi_opt_cfg* cfg, float* params_dev, float* state_dev,
                   const uint8_t* active_mask_dev, float* loss_slot_dev, float* finite_slot_dev);
 
+/* ---- posterior predictive (the reference's `model._get_posterior_sample(N, input_values={x: rows})`,
+ *      tests/test_MNIST_bayesian_neural_network.py:66-81): N weight sets from the CURRENT posterior — the draw of bsvi_bnn_fwd_bwd,
+ *      so (seed, offset, sample_base) or a caller's noise matrix give exactly the weights a training launch would see — the chain
+ *      forward on n_rows rows the CALLER hands in (x_dev [n_rows][n_features], f32, device), and per (sample n, row m):
+ *        z [N][n_rows][C]   the head's raw outputs: logits, or the Normal's loc
+ *        p [N][n_rows][C]   the likelihood's mean parameter: softmax probabilities | sigmoid of the single logit | the loc
+ *      their fixed-order mean over the samples, mean [n_rows][C], for the Normal likelihood also var [n_rows][C] = the population
+ *      variance of the loc over the N samples (about the mean) + sigma_c^2, and on request one draw from the likelihood per
+ *      (n, m): one-hot [N][n_rows][C] (Categorical), 0 / 1 [N][n_rows][1] (Bernoulli), real values [N][n_rows][C] (Normal), from a
+ *      Philox stream of its own (csrc/philox.h: key word k0 ^ 0x2545F491, c0 = sample_base + n, c1 = m).  Categorical: inverse CDF on
+ *      the STORED f32 probabilities — partial sums in class order in single precision, the first class whose partial sum is
+ *      >= u01(word 0), the last class if none is; Bernoulli: u01(word 0) < p; Normal: loc + sigma_c e, e = normal c & 3 of the four
+ *      Box-Muller normals (words (0, 1) -> normals 0, 1; words (2, 3) -> normals 2, 3) of the call whose k1 is xor-ed with c >> 2.
+ *      Every output pointer is optional (NULL: not written).  The products run on exact bf16 pieces when every value of x_dev is
+ *      exactly a bf16 number (tested on the device, once per call), else on the f32-input kernels — whatever the training dataset
+ *      was.  The rows are processed in passes of at most rows_per_pass (a multiple of 32; 0: chosen from the network's size), which
+ *      bounds the workspace and never changes a value; the weights are drawn once per call.  Nothing of the model's training state
+ *      is touched: the workspace is the caller's own (bsvi_bnn_predict_workspace_bytes), not that of bsvi_bnn_fwd_bwd.
+ *      Not sharded: a rank that calls this computes all of its n_samples_local samples, and mean / var are over those. */
+typedef struct bsvi_bnn_predict_args {
+    uint32_t struct_size;            /* sizeof(bsvi_bnn_predict_args) */
+    uint32_t reserved0;
+    const float* params_dev;         /* [n_params]                                                              */
+    const float* x_dev;              /* [n_rows][n_features]                                                    */
+    const float* noise_dev;          /* eps [n_rows of the latent vector][n_samples_local] or NULL -> Philox    */
+    uint64_t seed, offset;
+    uint32_t n_samples_local, sample_base, n_rows, rows_per_pass;
+    float* z_out;                    /* [n_samples_local][n_rows][C] or NULL                                    */
+    float* p_out;                    /* [n_samples_local][n_rows][C] or NULL                                    */
+    float* mean_out;                 /* [n_rows][C] or NULL                                                     */
+    float* var_out;                  /* [n_rows][C] or NULL; BSVI_LIK_NORMAL only                               */
+    float* draw_out;                 /* [n_samples_local][n_rows][C] or NULL                                    */
+    float* noise_out;                /* eps used [n_rows of the latent vector][n_samples_local] or NULL         */
+    void* workspace_dev;
+    void* stream;
+} bsvi_bnn_predict_args;
+/* sizeof(bsvi_bnn_predict_args) inside this build of the library (the struct is no bsvi_struct_kind: the kinds are a closed list) */
+size_t bsvi_bnn_predict_args_size(void);
+/* bytes of workspace of a call with these sizes (rows_per_pass 0: the default); 0 for a null handle, zero samples or rows, or a
+ * rows_per_pass that is no multiple of 32 */
+size_t bsvi_bnn_predict_workspace_bytes(const bsvi_bnn* b, uint32_t n_samples_local, uint32_t n_rows, uint32_t rows_per_pass);
+/* rows of a pass of such a call: rows_per_pass, or the default when it is 0 */
+uint32_t bsvi_bnn_predict_rows_per_pass(const bsvi_bnn* b, uint32_t n_samples_local, uint32_t n_rows, uint32_t rows_per_pass);
+/* 1: the forward kernel keeps the small tensors and its two activation buffers in LDS, 0: in global memory (csrc/bnn_select.h,
+ * predict_lds); -1 for a null handle */
+int bsvi_bnn_predict_lds(const bsvi_bnn* b);
+int bsvi_bnn_predict(const bsvi_bnn* b, const bsvi_bnn_predict_args* args);
+/* which products served this thread's last bsvi_bnn_predict: 1 exact bf16 pieces, 0 the f32-input kernels, -1 no call yet */
+int bsvi_bnn_predict_last_exact(void);
+
 /* =========================================================================================
  *  Amortised path (BASELINE config 5, examples/VAE_playground.py:18-88): the posterior of a latent
  *  vector z is a Normal whose loc / scale are the heads of an encoder network applied to a minibatch
