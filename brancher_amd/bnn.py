@@ -12,9 +12,10 @@ between the layers, biases optional) — and the regression model of the same fa
 
     y = NormalVariable(BF.matmul(weights2, hidden) + b2, sigma, name="y");  y.observe(targets)        # targets [DS, C, 1]
 
-with sigma a constant of the model (one value, or [C, 1]), from one layer (minibatched Bayesian linear regression) to eight:
-`bsvi_bnn_create_normal`.  `dense.lower_dense` serves ONE latent matrix without a bias; this module serves the
-rest of the family through `bsvi_bnn_*` (include/bsvi.h, csrc/bnn_kernel.inc).  The reference's semantics are kept as on the
+with sigma (one value, or [C, 1]) a constant of the model (`bsvi_bnn_create_normal`) or learnable — the reference's
+`NormalVariable(chain, 0.5, "y", learnable=True)`, or any a + b g(root) of a learnable root with g softplus / exp / sigmoid
+(`bsvi_bnn_create_normal_learnable`) —, from one layer (minibatched Bayesian linear regression) to eight.
+`dense.lower_dense` serves ONE latent matrix without a bias; this module serves the rest of the family through `bsvi_bnn_*` (include/bsvi.h, csrc/bnn_kernel.inc).  The reference's semantics are kept as on the
 dense path: priors and posteriors are matched by NAME, auto-created roots `<var>_<arg>` collide by name, no
 minibatch rescaling of the likelihood (`variables.py:849` TODO).
 """
@@ -40,11 +41,15 @@ PREDICT_PATHS = ("global", "lds")                                      # bsvi_bn
 class BnnProgram:
     """What `lower_bnn` extracts from the graph."""
     estimator = "pathwise"
+    scale_learnable = False
 
     def summary(self):
-        return dict(kind="bnn", layers=[(l["rows"], l["cols"], l["activation"]) for l in self.layers], n_rows=self.n_rows,
-                    dataset_size=self.dataset_size, batch_size=self.batch_size, n_params=self.n_params,
-                    likelihood=("categorical", "bernoulli", "normal")[self.likelihood], latents=[t["name"] for t in self.tensors])
+        s = dict(kind="bnn", layers=[(l["rows"], l["cols"], l["activation"]) for l in self.layers], n_rows=self.n_rows,
+                 dataset_size=self.dataset_size, batch_size=self.batch_size, n_params=self.n_params,
+                 likelihood=("categorical", "bernoulli", "normal")[self.likelihood], latents=[t["name"] for t in self.tensors])
+        if self.likelihood == LIK_NORMAL:
+            s["scale"] = "learnable" if self.scale_learnable else "constant"
+        return s
 
 
 def _is_random(v):
@@ -91,24 +96,31 @@ def _depends_on_latent(e):
     return any(_depends_on_latent(a) for a in e.args if hasattr(a, "op"))
 
 
-def _normal_scale(L, k, links, n_outputs):
-    """the scale of the Normal likelihood -> (first entry among the uniform table's constants, stride): one for every output
-    (stride 0) or one per output (stride 1).  (A learnable scale needs a reduction over (sample, row) of its own through every middle
-    kernel: DESIGN.md §9.)"""
+LEARNABLE_SCALE_TRANSFORMS = ("softplus", "exp", "sigmoid")          # what keeps sigma off zero whatever a step does to its root
+
+
+def _normal_scale(L, k, links, n_outputs, joint_roots=()):
+    """the scale of the Normal likelihood -> (first entry of the uniform table, stride, learnable): one for every output (stride 0) or
+    one per output (stride 1); a constant (an entry among the table's constants), or a + b g(root) of a learnable root of the joint
+    model with g one of softplus / exp / sigmoid, a >= 0, b > 0 (an entry with a gradient: bsvi_bnn_create_normal_learnable)"""
     e = links["scale"].expr
     m = L.match_uniform(L.from_expr(e, L.p_value))
     if m is None:
         raise LoweringError("bnn path: the scale of the Normal likelihood %r must be a constant or a transform of one" % k.name)
     leaf, g, a, b = m
-    if leaf.op == "root" and leaf.attr.learnable:
-        raise LoweringError("bnn path: the scale of the Normal likelihood %r is learnable (it must be a constant of the model)" % k.name)
+    learnable = leaf.op == "root" and leaf.attr.learnable
+    if learnable and (g not in LEARNABLE_SCALE_TRANSFORMS or not (a >= 0 and b > 0) or leaf.attr not in joint_roots):
+        # (a bare root: a step can carry it through zero)
+        raise LoweringError("bnn path: the scale of the Normal likelihood %r is learnable (it must be a constant of the model, or "
+                            "a + b * g(root) of a learnable root of the joint model with g one of %s, a >= 0 and b > 0)"
+                            % (k.name, " / ".join(LEARNABLE_SCALE_TRANSFORMS)))
     size = int(np.prod(leaf.shape))
     shape = tuple(int(d) for d in leaf.shape)
     if size != 1 and (size != n_outputs or shape[-1] != 1):
         raise LoweringError("bnn path: the scale of the Normal likelihood %r has shape %r: neither one value nor one per output [%d, 1]"
                             % (k.name, shape[1:], n_outputs))
-    _, k0 = L.uniform_entries(leaf, g, a, b)
-    return k0, (1 if size > 1 else 0)
+    is_param, k0 = L.uniform_entries(leaf, g, a, b)
+    return k0, (1 if size > 1 else 0), bool(is_param)
 
 
 def lower_bnn(joint, posterior, estimator="pathwise"):
@@ -125,7 +137,8 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     for v in sorted(L.q_roots, key=lambda v: v.name):
         if v.learnable:
             L.param_offset(v.parameter, 0)
-    for v in sorted([v for v in joint.flatten() if isinstance(v, RootVariable)], key=lambda v: v.name):
+    joint_roots = [v for v in joint.flatten() if isinstance(v, RootVariable)]
+    for v in sorted(joint_roots, key=lambda v: v.name):
         if v.learnable:
             L.param_offset(v.parameter, 1)
     q_random = [v for v in q_flat if _is_random(v)]
@@ -254,7 +267,7 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     if normal:
         if Ym.shape[1] != width:
             raise LoweringError("bnn path: the targets have %d columns but the last layer has %d rows" % (Ym.shape[1], width))
-        scale_entries = _normal_scale(L, k, links, width)
+        scale_entries = _normal_scale(L, k, links, width, joint_roots)
     if lik == LIK_BERNOULLI:
         if width != 1:
             raise LoweringError("bnn path: a Bernoulli/Binomial likelihood needs a single output")
@@ -279,8 +292,9 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     prog.n_features, prog.n_classes, prog.dataset_size, prog.batch_size = P, width, DS, int(ind_x.batch_size)
     prog.likelihood = lik
     if normal:
-        # (constants stand behind the entries with a gradient in the uniform table)
-        prog.scale_uniform, prog.scale_stride = n_up + scale_entries[0], scale_entries[1]
+        # (constants stand behind the entries with a gradient in the uniform table; a learnable scale is one of those)
+        prog.scale_learnable = scale_entries[2]
+        prog.scale_uniform, prog.scale_stride = (0 if prog.scale_learnable else n_up) + scale_entries[0], scale_entries[1]
     prog.dataset = np.ascontiguousarray(Xm, dtype=np.float32)
     prog.labels = np.ascontiguousarray(Ym, dtype=np.float32)
     prog.indices_name = ind_x.name
@@ -363,7 +377,8 @@ class CompiledBnn:
         d, self._keep = make_desc(p)
         handle = C.c_void_p()
         if p.likelihood == LIK_NORMAL:
-            native.check(lib.bsvi_bnn_create_normal(C.byref(d), p.scale_uniform, p.scale_stride, C.byref(handle)))
+            create = lib.bsvi_bnn_create_normal_learnable if getattr(p, "scale_learnable", False) else lib.bsvi_bnn_create_normal
+            native.check(create(C.byref(d), p.scale_uniform, p.scale_stride, C.byref(handle)))
         else:
             native.check(lib.bsvi_bnn_create(C.byref(d), C.byref(handle)))
         self.handle = handle

@@ -8,7 +8,11 @@
 // lab [B_pad][C], where the classifiers keep one label per row.  Per (row b, sample n):
 //     lik = wgt sum_c (-1/2 u_c^2 - log sigma_c - 1/2 log 2 pi),  u_c = (y[b][c] - z_c) / sigma_c;   delta_c = wgt u_c / sigma_c
 // at the three sites that hold a likelihood (bnn_upper, bnn_upper_gen, bnn_mid_gen); everything behind the deltas is unchanged.
-// A learnable sigma would need a reduction over (sample, row) of its own through each of them: not built (DESIGN.md 9).
+// A learnable sigma (bsvi_bnn_create_normal_learnable: sigma_c = a + b g(theta), a parameter entry of the uniform table) takes
+//     G_c = sum_n sum_b wgt (u_c^2 - 1) / sigma_c
+// into the gradient of its entry: per (c, b, n) beside liknb at the two bnn_upper sites and summed over b by bnn_sig_rows (bnn_lik's
+// order), per (c, n) out of the tile in bnn_mid_gen; then over n in double precision (bnn_epilogue) and into the entry (bnn_uniform_grads).
+// All of it behind BParams::scale_learn / a generator switch: a constant sigma and the classifiers run what they ran.
 // All latent scalars form ONE vector of R rows (weights1 first: H_1 x P
 // rows r = h * P + p, then the other tensors); row r draws eps from the dense path's Philox counters (sample, r >> 2), so the
 // noise of a model is one [R][N] matrix as on the dense path, and reads its four parameters (q loc, q scale, prior loc, prior
@@ -43,6 +47,7 @@ struct BParams {
     uint32_t n_layers, R, R1, Rs, P, C, H1, DS, B, B_pad, Kp, P_ld, n_local, n_pad, n_global, sample_base, NC;
     uint32_t n_uniform_grad, likelihood, estimator, exact, act_width;
     uint32_t LC, scale_u, scale_stride;       // targets per minibatch row (1 label; C for the Normal likelihood) and sigma's uniform entries
+    uint32_t scale_learn;                     // sigma's entries are parameters: its gradient is accumulated (launch-uniform)
     float lik_weight, prior_weight, entropy_weight;
     uint32_t seed_lo, seed_hi, offset_lo, offset_hi;
     const float* noise_in; float* noise_out; const int32_t* indices_in; int32_t* indices_out; float* fvalue_out; float* logq_out;
@@ -64,6 +69,11 @@ struct BParams {
     float* GT;              // exact: [P][NC]; f32: [NC][P_ld]
     float* gsm; float* lik; float* pv_part; float* qv_part; float* sums; float* rowg; double* hpart; float* partial; float* fs;
     uint32_t row_chunks;
+    // a learnable sigma only (null otherwise): wgt (u^2 - 1) / sigma per (c, b, n) of the bnn_upper sites, its sum over b per (c, n),
+    // and that over n
+    float* sigt;            // [C][B_pad][n_pad]
+    float* gsig;            // [C][n_pad]
+    double* gsd;            // [C]
 };
 
 __device__ __forceinline__ float bnn_act(uint32_t act, float v) {
@@ -309,6 +319,7 @@ __global__ void __launch_bounds__(256) bnn_upper(const BParams Q) {
                 const float sigma = sg[c], u = (yb[c] - Y(LL, c)) / sigma;
                 s += -0.5f * u * u + sg[LL.rows + c];
                 Dl(LL, c) = wgt * u / sigma;
+                if (Q.scale_learn) Q.sigt[((size_t)c * Q.B_pad + b) * Q.n_pad + n] = wgt * (u * u - 1.0f) / sigma;
             }
             lik = wgt * s;
         } else if (Q.likelihood == BSVI_LIK_CATEGORICAL) {
@@ -424,6 +435,24 @@ __global__ void __launch_bounds__(256) bnn_lik(const BParams Q) {
     part[wave][lane] = s;
     __syncthreads();
     if (wave == 0) Q.lik[n] = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
+}
+
+// a learnable sigma behind the bnn_upper sites: the sum over the minibatch rows of output c's terms, in bnn_lik's order.
+// grid: ceil(n_pad / 64) x C, block 256
+__global__ void __launch_bounds__(256) bnn_sig_rows(const BParams Q) {
+    __shared__ float part[4][64];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, n = blockIdx.x * 64u + lane, c = blockIdx.y;
+    const float* const t = Q.sigt + (size_t)c * Q.B_pad * Q.n_pad;
+    float s = 0.0f;
+    for (uint32_t b0 = wave; b0 < Q.B; b0 += 32u) {
+        float v[8];
+#pragma unroll
+        for (uint32_t u = 0; u < 8u; ++u) v[u] = b0 + 4u * u < Q.B ? t[(size_t)(b0 + 4u * u) * Q.n_pad + n] : 0.0f;
+        s += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+    }
+    part[wave][lane] = s;
+    __syncthreads();
+    if (wave == 0) Q.gsig[(size_t)c * Q.n_pad + n] = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
 }
 
 // one row: gradients with respect to its four uniform entries (the formulas of dense_rows_body) and its sample-independent terms of f
@@ -551,6 +580,14 @@ __global__ void __launch_bounds__(1024) bnn_epilogue(const BParams Q, uint32_t r
     }
     const double fs = total(fsum), vs = total(vsum), bs = total(bad);
     if (tid == 0) { Q.partial[0] = (float)vs; Q.partial[1] = (float)bs; Q.fs[0] = (float)fs; }
+    if (Q.scale_learn) {      // a learnable sigma: G_c = sum_n of the per-sample sums, in the same fixed order
+        for (uint32_t c = 0; c < Q.C; ++c) {
+            double g = 0.0;
+            for (uint32_t n = tid; n < Q.n_local; n += 1024u) g += (double)Q.gsig[(size_t)c * Q.n_pad + n];
+            const double gt = total(g);
+            if (tid == 0) Q.gsd[c] = gt;
+        }
+    }
 }
 
 // one thread per uniform entry with a gradient: its rows' contributions in item order.  BlackBox (gradient_estimators.py:29-36
@@ -567,6 +604,12 @@ __global__ void __launch_bounds__(256) bnn_uniform_grads(const BParams Q) {
         s += Q.rowg[item];
         if (blackbox && role == 1u) s += -fs / Q.rowp[Q.R + r];
     }
+    if (Q.scale_learn) {      // sigma's entries: output c adds G_c to entry scale_u + c * scale_stride (stride 0: the sum over c), to what
+        double g = 0.0;       // the entry's rows gave above — one root may be a prior scale and sigma
+        for (uint32_t c = 0; c < Q.C; ++c)
+            if (Q.scale_u + c * Q.scale_stride == k) g += Q.gsd[c];
+        s += (float)g;
+    }
     Q.partial[2 + k] = s;
 }
 
@@ -581,7 +624,8 @@ struct bsvi_bnn {
     const float* dataset = nullptr; const float* labels = nullptr;
     uint32_t R = 0, R1 = 0, Rs = 0, P = 0, C = 0, H1 = 0, B_pad = 0, Kp = 0, P_ld = 0;
     uint32_t LC = 1;             // targets per dataset row: one label, or C for the Normal likelihood
-    uint32_t scale_u = 0, scale_stride = 0;      // Normal likelihood: sigma of output c is uniform entry scale_u + c * scale_stride (constants)
+    uint32_t scale_u = 0, scale_stride = 0;      // Normal likelihood: sigma of output c is uniform entry scale_u + c * scale_stride
+    bool scale_learn = false;    // ... parameter entries (bsvi_bnn_create_normal_learnable), else constants
     uint64_t act_floats = 0, delta_floats = 0;      // per (sample, minibatch row)
     uint32_t act_off[BNN_MAX_LAYERS] = {};
     bool exact = false;
@@ -604,11 +648,14 @@ struct BnnUpperArgs {
     float lik_weight;
     const float* f_weight;      // a_n per sample, or null
 };
+// ... of a network with a learnable sigma: the same fields, then where its terms go (the generated struct gains the same last member)
+struct BnnUpperArgsSig { BnnUpperArgs a; float* sigt; };
 
 // the Normal likelihood of the two generated kernels (the text bnn_upper runs with loop bounds): targets [B_pad][C] in A.lab, then
 // sigma [C] and -log sigma - 1/2 log 2 pi [C] as bnn_head_body leaves them — the values of the uniform table, never a host copy
-static std::string bnn_normal_source(uint32_t C, uint32_t yl) {
-    char buf[1024];
+// sig_terms (bnn_upper_gen with a learnable sigma): wgt (u^2 - 1) / sigma per (c, b, n) leaves for bnn_sig_rows
+static std::string bnn_normal_source(uint32_t C, uint32_t yl, bool sig_terms = false) {
+    char buf[1280];
     snprintf(buf, sizeof buf,
              "        {\n"
              "            const float* const yb = A.lab + (size_t)b * %uu;\n"
@@ -619,9 +666,11 @@ static std::string bnn_normal_source(uint32_t C, uint32_t yl) {
              "                const float sigma = sg[c], u = (yb[c] - y[%uu + c]) / sigma;\n"
              "                sn += -0.5f * u * u + sg[%uu + c];\n"
              "                d[%uu + c] = wgt * u / sigma;\n"
+             "%s"
              "            }\n"
              "            lik = wgt * sn;\n"
-             "        }\n", C, C, C, yl, C, yl);
+             "        }\n", C, C, C, yl, C, yl,
+             sig_terms ? "                A.sigt[((size_t)c * A.B_pad + b) * A.n_pad + n] = wgt * (u * u - 1.0f) / sigma;\n" : "");
     return std::string(buf);
 }
 
@@ -656,7 +705,8 @@ static std::string bnn_upper_source(const bsvi_bnn* p) {
     s += "// generated by libbsvi (bnn_kernel.inc) for one Bayesian neural network: do not edit\n";
     s += "#include \"bsvi_device.h\"\nusing namespace bsvi;\n";
     s += "struct BnnUpperArgs { const float* Wsm; const float* a1T; const float* lab; float* acts; float* deltas; float* liknb; float* da1T; uint16_t* dlogp;\n"
-         "    uint32_t n_local, n_pad, B, B_pad, NC, rows_per_wave, exact; float lik_weight; const float* f_weight; };\n";
+         "    uint32_t n_local, n_pad, B, B_pad, NC, rows_per_wave, exact; float lik_weight; const float* f_weight;";
+    s += p->scale_learn ? " float* sigt; };\n" : " };\n";
     s += "__device__ __forceinline__ uint16_t gen_bf16(float x) { const uint32_t u = __float_as_uint(x); return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16); }\n";
     s += fmt("#define RS %uu\n#define AW %uu\n", RS, AW);
     s += "extern \"C\" __global__ void __launch_bounds__(256) bnn_upper_gen(const BnnUpperArgs A) {\n"
@@ -696,7 +746,7 @@ static std::string bnn_upper_source(const bsvi_bnn* p) {
     s += std::string("        const float wgt = live ? A.lik_weight * (A.f_weight ? A.f_weight[n] : 1.0f) : 0.0f") +
          (p->d.likelihood == BSVI_LIK_NORMAL ? ";\n" : ", label = A.lab[b];\n") + "        float lik = 0.0f;\n";
     if (p->d.likelihood == BSVI_LIK_NORMAL) {
-        s += bnn_normal_source(LL.rows, yl);
+        s += bnn_normal_source(LL.rows, yl, p->scale_learn);
     } else if (p->d.likelihood == BSVI_LIK_CATEGORICAL) {
         s += "        {\n            float m = -INFINITY;\n#pragma unroll\n";
         s += fmt("            for (uint32_t c = 0; c < %uu; ++c) m = fmaxf(m, y[%uu + c]);\n", LL.rows, yl);
@@ -759,6 +809,7 @@ struct BnnMidArgs {
     float lik_weight;
     const float* f_weight;      // a_n per sample, or null
 };
+struct BnnMidArgsSig { BnnMidArgs a; float* gsig; };      // a learnable sigma: its per-sample sums [C][n_pad] (as BnnUpperArgsSig)
 static std::string bnn_mid_source(const bsvi_bnn* p) {
     auto fmt = [](const char* f, ...) { char buf[512]; va_list ap; va_start(ap, f); vsnprintf(buf, sizeof buf, f, ap); va_end(ap); return std::string(buf); };
     const uint32_t NL = p->d.n_layers, RS = p->Rs ? p->Rs : 1, R1 = p->R1, AW = (uint32_t)p->act_floats;
@@ -798,7 +849,8 @@ static std::string bnn_mid_source(const bsvi_bnn* p) {
     s += "// generated by libbsvi (bnn_kernel.inc) for one Bayesian neural network: do not edit\n";
     s += "#include \"bsvi_device.h\"\nusing namespace bsvi;\n";
     s += "struct BnnMidArgs { const float* Wsm; const float* a1; const float* lab; float* gsm; float* lik; uint16_t* dlogp;\n"
-         "    uint32_t n_local, n_pad, B, B_pad, NC; float lik_weight; const float* f_weight; };\n";
+         "    uint32_t n_local, n_pad, B, B_pad, NC; float lik_weight; const float* f_weight;";
+    s += p->scale_learn ? " float* gsig; };\n" : " };\n";
     s += "typedef float gen_f4 __attribute__((ext_vector_type(4)));\n";
     s += "__device__ __forceinline__ uint16_t gen_bf16(float x) { const uint32_t u = __float_as_uint(x); return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16); }\n";
     s += fmt("#define RS %uu\n#define RSP %uu\n#define AW %uu\n", RS, (RS + 3u) / 4u * 4u, AW);
@@ -870,6 +922,9 @@ static std::string bnn_mid_source(const bsvi_bnn* p) {
         s += "            d[" + fmt("%uu", p->act_off[l - 1]) + " + j] = sm * " + act_grad(Lp.activation, "y[" + fmt("%uu", p->act_off[l - 1]) + " + j]") + ";\n        }\n";
     }
     s += "#pragma unroll\n        for (uint32_t u = 0; u < AW; ++u) { T[(size_t)u * BS + b] = y[u]; T[(size_t)(AW + u) * BS + b] = d[u]; }\n";
+    if (p->scale_learn)      // (the residuals where the last layer's outputs stood: what sigma's elements of the loop below read)
+        s += fmt("#pragma unroll\n        for (uint32_t c = 0; c < %uu; ++c) T[(size_t)(%uu + c) * BS + b] = A.lab[(size_t)b * %uu + c] - y[%uu + c];\n",
+                 LL.rows, yl, LL.rows, yl);
     s += "#pragma unroll\n";
     s += fmt("        for (uint32_t h = 0; h < %uu; ++h) {\n", L0.rows);
     s += fmt("            const float g = live ? d[%uu + h] : 0.0f;\n", p->act_off[0]);
@@ -906,8 +961,9 @@ static std::string bnn_mid_source(const bsvi_bnn* p) {
          "    }\n"
          "    __syncthreads();                                   // (and the tile is complete)\n"
          "    if (tid == 0u) A.lik[n] = (red[0] + red[1]) + (red[2] + red[3]);\n"
-         "    // gradients of the small tensors: element r = sum_b d[du(r)][b] * y[yu(r)][b] (a bias: y = 1), rows in order\n"
-         "    for (uint32_t r = tid; r < RS; r += 256u) {\n"
+         "    // gradients of the small tensors: element r = sum_b d[du(r)][b] * y[yu(r)][b] (a bias: y = 1), rows in order\n";
+    s += "    for (uint32_t r = tid; r < RS; r += 256u) {\n";
+    s += ""
          "        const uint32_t du = GEN_DU[r], yu = GEN_YU[r];\n"
          "        const gen_f4* const dr = reinterpret_cast<const gen_f4*>(T + (size_t)du * BS);\n"
          "        const gen_f4* const yr = reinterpret_cast<const gen_f4*>(T + (size_t)(yu == 0xFFFFu ? du : yu) * BS);\n"
@@ -921,8 +977,26 @@ static std::string bnn_mid_source(const bsvi_bnn* p) {
          "            }\n"
          "        }\n"
          "        A.gsm[(size_t)n * RS + r] = sm;\n"
-         "    }\n"
-         "}\n";
+         "    }\n";
+    // a learnable sigma: its C per-sample sums are C more elements of this kind (a thread each, rows in order, 16-byte LDS reads, no LDS of
+    // their own), taken from the LAST thread down — with Rs <= 192 a wave that has no element of the small tensors, so that no wave runs
+    // both kinds one after the other.  The tile holds y_c - z_c (in the place of z_c, which no element reads) and d_c = wgt u / sigma_c of
+    // the last layer, and d_c (y_c - z_c) = wgt u^2: the loop of a weight element, instruction for instruction (four conditional
+    // subtractions of wgt per iteration made this one 17 us of a 94 us launch at config 4's scale, profiles/r16); rows behind the
+    // minibatch have d_c = 0, and sum_b wgt = wgt B leaves once, behind the loop
+    if (p->scale_learn)
+        s += fmt("    for (uint32_t c = 255u - tid; c < %uu; c += 256u) {\n"
+                 "        const gen_f4* const dr = reinterpret_cast<const gen_f4*>(T + (size_t)(AW + %uu + c) * BS);\n"
+                 "        const gen_f4* const rr = reinterpret_cast<const gen_f4*>(T + (size_t)(%uu + c) * BS);\n", LL.rows, yl, yl) +
+             "        const float wv = n < A.n_local ? A.lik_weight * (A.f_weight ? A.f_weight[n] : 1.0f) : 0.0f;\n"
+             "        float sm = 0.0f;\n"
+             "        for (uint32_t q = 0; q < A.B_pad / 4u; ++q) {\n"
+             "            const gen_f4 dv = dr[q], rv = rr[q];\n"
+             "            sm += dv.x * rv.x; sm += dv.y * rv.y; sm += dv.z * rv.z; sm += dv.w * rv.w;\n"
+             "        }\n" +
+             fmt("        A.gsig[(size_t)c * A.n_pad + n] = (sm - wv * (float)A.B) / A.lab[(size_t)A.B_pad * %uu + c];\n"
+                 "    }\n", LL.rows);
+    s += "}\n";
     return s;
 }
 
@@ -986,8 +1060,10 @@ static bool bnn_upper_ready(const bsvi_bnn* p) {
 }
 
 
-// the two entry points' common body; normal: bsvi_bnn_create_normal (the scale entries are its plain arguments)
-static int bnn_create(const bsvi_bnn_desc* desc, const bool normal, const uint32_t scale_uniform, const uint32_t scale_stride, bsvi_bnn** out) {
+// the three entry points' common body; normal: bsvi_bnn_create_normal (the scale entries are its plain arguments: constants), learn:
+// bsvi_bnn_create_normal_learnable (parameter entries)
+static int bnn_create(const bsvi_bnn_desc* desc, const bool normal, const uint32_t scale_uniform, const uint32_t scale_stride, bsvi_bnn** out,
+                      const bool learn = false) {
     if (!desc || !out) return fail(BSVI_ERR_INVALID, "null argument");
     *out = nullptr;
     BSVI_CHECK_STRUCT(desc, bsvi_bnn_desc);
@@ -997,7 +1073,8 @@ static int bnn_create(const bsvi_bnn_desc* desc, const bool normal, const uint32
     if (desc->n_features % 4) return fail(BSVI_ERR_UNSUPPORTED, "the number of features must be a multiple of 4 (the noise is drawn in quads of rows)");
     if (!normal && desc->likelihood == BSVI_LIK_NORMAL)
         return fail(BSVI_ERR_UNSUPPORTED, "the Normal likelihood needs its scale entries: create the model with bsvi_bnn_create_normal");
-    if (normal && desc->likelihood != BSVI_LIK_NORMAL) return fail(BSVI_ERR_INVALID, "bsvi_bnn_create_normal takes likelihood BSVI_LIK_NORMAL");
+    if (normal && desc->likelihood != BSVI_LIK_NORMAL)
+        return fail(BSVI_ERR_INVALID, learn ? "bsvi_bnn_create_normal_learnable takes likelihood BSVI_LIK_NORMAL" : "bsvi_bnn_create_normal takes likelihood BSVI_LIK_NORMAL");
     if (desc->likelihood > BSVI_LIK_NORMAL) return fail(BSVI_ERR_UNSUPPORTED, "unknown likelihood");
     if (desc->estimator > BSVI_EST_BLACKBOX) return fail(BSVI_ERR_INVALID, "unknown estimator");
     for (uint32_t k = 0; k < desc->n_uniform; ++k) {
@@ -1027,8 +1104,21 @@ static int bnn_create(const bsvi_bnn_desc* desc, const bool normal, const uint32
         if (scale_stride > 1u) return fail(BSVI_ERR_INVALID, "scale_stride is 0 (one scale for every output) or 1 (one per output)");
         const uint64_t last = (uint64_t)scale_uniform + (uint64_t)scale_stride * (width - 1u);
         if (last >= desc->n_uniform) return fail(BSVI_ERR_INVALID, "scale entry out of the uniform table");
-        if (scale_uniform < desc->n_uniform_grad)
+        if (!learn && scale_uniform < desc->n_uniform_grad)
             return fail(BSVI_ERR_UNSUPPORTED, "the scale of the Normal likelihood must be a constant of the model: a learnable scale is not implemented");
+        if (learn) {
+            // ... every one of them a parameter's, behind a transform that keeps sigma off zero whatever a step does to the parameter
+            uint32_t n_param = 0;
+            for (uint32_t c = 0; c < width; ++c) n_param += scale_uniform + c * scale_stride < desc->n_uniform_grad ? 1u : 0u;
+            if (!n_param)
+                return fail(BSVI_ERR_INVALID, "bsvi_bnn_create_normal_learnable: the scale entries are constants (a constant scale: bsvi_bnn_create_normal)");
+            if (n_param != width) return fail(BSVI_ERR_INVALID, "bsvi_bnn_create_normal_learnable: the scale entries are a mix of constants and parameters");
+            for (uint32_t c = 0; c < width; ++c) {
+                const uint32_t t = desc->uniform[scale_uniform + c * scale_stride].transform;
+                if (t != BSVI_UT_SOFTPLUS && t != BSVI_UT_EXP && t != BSVI_UT_SIGMOID)
+                    return fail(BSVI_ERR_UNSUPPORTED, "bsvi_bnn_create_normal_learnable: the transform of a learnable scale is softplus, exp or sigmoid");
+            }
+        }
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(BSVI_ERR_NO_DEVICE, "no HIP device visible");
@@ -1040,7 +1130,7 @@ static int bnn_create(const bsvi_bnn_desc* desc, const bool normal, const uint32
     p->R1 = p->H1 * p->P; p->Rs = R - p->R1;
     p->Kp = (p->P + 31) / 32 * 32; p->P_ld = (p->P + 3) / 4 * 4;
     p->B_pad = (desc->batch_size + 31) / 32 * 32;
-    if (normal) { p->LC = width; p->scale_u = scale_uniform; p->scale_stride = scale_stride; }
+    if (normal) { p->LC = width; p->scale_u = scale_uniform; p->scale_stride = scale_stride; p->scale_learn = learn; }
     for (uint32_t l = 0; l < desc->n_layers; ++l) { p->act_off[l] = (uint32_t)p->act_floats; p->act_floats += p->layers[l].rows; }
     p->delta_floats = p->act_floats;
     {   // exact data: both products on the bf16 matrix cores (three MFMAs on the exact pieces of the other operand); BSVI_DENSE_XGEMM=0: f32
@@ -1098,6 +1188,10 @@ extern "C" int bsvi_bnn_create_normal(const bsvi_bnn_desc* desc, uint32_t scale_
     return bnn_create(desc, true, scale_uniform, scale_stride, out);
 }
 
+extern "C" int bsvi_bnn_create_normal_learnable(const bsvi_bnn_desc* desc, uint32_t scale_uniform, uint32_t scale_stride, bsvi_bnn** out) {
+    return bnn_create(desc, true, scale_uniform, scale_stride, out, true);
+}
+
 extern "C" void bsvi_bnn_destroy(bsvi_bnn* p) {
     if (!p) return;
     if (p->dev_blob) (void)hipFree(p->dev_blob);
@@ -1119,6 +1213,7 @@ extern "C" int bsvi_bnn_middle(const bsvi_bnn* p) {
 
 struct BnnLayout {
     size_t rowp, idx, lab, Xb, Xb_bf, XbT_bf, W1f, Wp, Wsm, a1T, acts, deltas, liknb, da1T, dlogp, GT, gsm, lik, pv, qv, sums, rowg, hpart, partial, fs, total;
+    size_t sigt, gsig, gsd;
     uint32_t n_pad, NC, row_chunks, row_blocks;
 };
 static BnnLayout bnn_layout(const bsvi_bnn* p, uint32_t n_local) {
@@ -1145,6 +1240,8 @@ static BnnLayout bnn_layout(const bsvi_bnn* p, uint32_t n_local) {
     L.pv = take((size_t)L.row_chunks * L.n_pad * 4); L.qv = take((size_t)L.row_chunks * L.n_pad * 4);
     L.sums = take(4 * (size_t)p->R * 4); L.rowg = take(4 * (size_t)p->R * 4); L.hpart = take(2 * (size_t)L.row_blocks * 8);
     L.partial = take((2 + (size_t)p->d.n_uniform_grad) * 4); L.fs = take(256);
+    // (a learnable sigma's three arrays behind everything else: nothing moves, and nothing is added, for the networks without one)
+    if (p->scale_learn) { L.sigt = take(nb * p->C * 4); L.gsig = take((size_t)L.n_pad * p->C * 4); L.gsd = take((size_t)p->C * 8); }
     L.total = o + 256;
     return L;
 }
@@ -1181,7 +1278,7 @@ static int bnn_fill(const bsvi_bnn* p, const bsvi_bnn_args* a, BParams& Q, BnnLa
     Q.B_pad = p->B_pad; Q.Kp = p->Kp; Q.P_ld = p->P_ld; Q.n_local = a->n_samples_local; Q.n_pad = L.n_pad; Q.n_global = a->n_samples_global;
     Q.sample_base = a->sample_base; Q.NC = L.NC; Q.n_uniform_grad = p->d.n_uniform_grad; Q.likelihood = p->d.likelihood;
     Q.estimator = p->d.estimator; Q.exact = p->exact ? 1u : 0u; Q.act_width = (uint32_t)p->act_floats;
-    Q.LC = p->LC; Q.scale_u = p->scale_u; Q.scale_stride = p->scale_stride;
+    Q.LC = p->LC; Q.scale_u = p->scale_u; Q.scale_stride = p->scale_stride; Q.scale_learn = p->scale_learn ? 1u : 0u;
     Q.lik_weight = p->d.lik_weight; Q.prior_weight = p->d.prior_weight; Q.entropy_weight = p->d.entropy_weight;
     Q.seed_lo = (uint32_t)a->seed; Q.seed_hi = (uint32_t)(a->seed >> 32); Q.offset_lo = (uint32_t)a->offset; Q.offset_hi = (uint32_t)(a->offset >> 32);
     Q.noise_in = a->noise_dev; Q.noise_out = a->noise_out_dev; Q.indices_in = a->indices_dev; Q.indices_out = a->indices_out_dev;
@@ -1199,6 +1296,7 @@ static int bnn_fill(const bsvi_bnn* p, const bsvi_bnn_args* a, BParams& Q, BnnLa
     Q.gsm = (float*)(ws + L.gsm); Q.lik = (float*)(ws + L.lik); Q.pv_part = (float*)(ws + L.pv); Q.qv_part = (float*)(ws + L.qv);
     Q.sums = (float*)(ws + L.sums); Q.rowg = (float*)(ws + L.rowg); Q.hpart = (double*)(ws + L.hpart); Q.partial = (float*)(ws + L.partial);
     Q.fs = (float*)(ws + L.fs); Q.row_chunks = L.row_chunks;
+    if (p->scale_learn) { Q.sigt = (float*)(ws + L.sigt); Q.gsig = (float*)(ws + L.gsig); Q.gsd = (double*)(ws + L.gsd); }
     return BSVI_OK;
 }
 
@@ -1215,20 +1313,21 @@ static int bnn_launch(const bsvi_bnn* p, const BParams& Q, const BnnLayout& L, h
     if (rc) return rc;
     if (mid) {
         // one workgroup per sample: upper layers, likelihood, reverse sweep, pieces of d f / d a1, gradients of the small tensors
-        BnnMidArgs M{Q.Wsm, Q.a1T, Q.lab, Q.gsm, Q.lik, Q.dlogp, Q.n_local, Q.n_pad, Q.B, Q.B_pad, Q.NC, Q.lik_weight, Q.f_weight};
-        size_t size = sizeof M;
-        void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &M, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+        const BnnMidArgsSig M{{Q.Wsm, Q.a1T, Q.lab, Q.gsm, Q.lik, Q.dlogp, Q.n_local, Q.n_pad, Q.B, Q.B_pad, Q.NC, Q.lik_weight, Q.f_weight}, Q.gsig};
+        size_t size = p->scale_learn ? sizeof M : sizeof M.a;      // (the kernel of a constant sigma declares the first part alone)
+        void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, (void*)&M, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
         HIP_TRY(hipModuleLaunchKernel(p->mid_fn, Q.n_pad, 1, 1, 256, 1, 1, (unsigned)bnn_mid_lds_bytes(p), s, nullptr, config));
     } else {
         const dim3 ugrid(Q.n_pad / 64, (Q.B_pad + 7) / 8);
         const size_t wl_bytes = bsvi_bnn_select::upper_lds_bytes(p->Rs, p->act_floats);
         if (bnn_upper_ready(p)) {
             // (no LDS beyond the staging tile and registers only: several workgroups per CU — two rows per wave as above)
-            BnnUpperArgs U{Q.Wsm, Q.a1T, Q.lab, Q.acts, Q.deltas, Q.liknb, Q.da1T, Q.dlogp, Q.n_local, Q.n_pad, Q.B, Q.B_pad, Q.NC, 2u, Q.exact, Q.lik_weight, Q.f_weight};
+            BnnUpperArgsSig US{{Q.Wsm, Q.a1T, Q.lab, Q.acts, Q.deltas, Q.liknb, Q.da1T, Q.dlogp, Q.n_local, Q.n_pad, Q.B, Q.B_pad, Q.NC, 2u, Q.exact, Q.lik_weight, Q.f_weight}, Q.sigt};
+            BnnUpperArgs& U = US.a;
             static const uint32_t rpw = [] { const char* e = getenv("BSVI_BNN_ROWS_PER_WAVE"); return e ? (uint32_t)atoi(e) : 0u; }();
             if (rpw) U.rows_per_wave = rpw;
-            size_t size = sizeof U;
-            void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &U, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+            size_t size = p->scale_learn ? sizeof US : sizeof U;
+            void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &US, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
             const uint32_t gy = (Q.B_pad + 4u * U.rows_per_wave - 1u) / (4u * U.rows_per_wave);
             HIP_TRY(hipModuleLaunchKernel(p->jit_fn, Q.n_pad / 64, gy, 1, 256, 1, 1, (unsigned)bsvi_bnn_select::upper_gen_lds_bytes(p->Rs), s, nullptr, config));
         }
@@ -1241,6 +1340,7 @@ static int bnn_launch(const bsvi_bnn* p, const BParams& Q, const BnnLayout& L, h
             hipLaunchKernelGGL(bnn_small, dim3(Q.n_pad / 64, (D.rows + 3) / 4, (jn + 3) / 4), dim3(256), 0, s, Q, l);
         }
         hipLaunchKernelGGL(bnn_lik, dim3(Q.n_pad / 64), dim3(256), 0, s, Q);
+        if (Q.scale_learn) hipLaunchKernelGGL(bnn_sig_rows, dim3(Q.n_pad / 64, Q.C), dim3(256), 0, s, Q);
     }
     if (Q.exact) rc = bsvi_xgemm_nt(Q.XbT_bf, nullptr, Q.dlogp, (long)Q.NC * Q.B_pad, Q.GT, (int)Q.NC, (int)Q.P, (int)Q.NC, (int)Q.B_pad, s);
     else rc = bsvi_gemm_f32(1, Q.da1T, (int)Q.B_pad, Q.Xb, (int)Q.P_ld, Q.GT, (int)Q.P_ld, (int)Q.NC, (int)Q.P, (int)Q.B_pad, s);

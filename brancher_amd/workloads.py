@@ -846,7 +846,7 @@ def build_bayesian_neural_network(api, dataset_size=48, batch_size=30, n_feature
 
 def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_hidden=9, n_outputs=1, hidden2=0, activation="tanh",
                          sigma=0.5, data="integers", bias=True, seed=0, prior_scale=2., q_scale=0.1, q_scale1=None, q_loc_scale=0.5,
-                         widths=None, activations=None):
+                         widths=None, activations=None, learnable_sigma=False, sigma_init=None):
     """The regression model of the Bayesian-neural-network family: the network of `build_bayesian_neural_network` (latent weight
     matrices and biases under a mean-field Normal posterior) as the loc of an observed Normal,
     `y ~ NormalVariable(matmul(weights2, act(matmul(weights1, x) + b1)) + b2, sigma)`, the targets [DS, C, 1] an EmpiricalVariable that
@@ -856,8 +856,15 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
     come from a teacher network of the same shape plus noise of scale sigma.  Posterior means are drawn at `q_loc_scale` posterior
     scales from zero, and the scale of the first layer (default 0.4 / sqrt(sum_p E x_p^2)) keeps every hidden unit off saturation.
     widths: the full list of layer widths, features first, outputs last (it overrides n_features, n_hidden, hidden2 and n_outputs: any
-    depth); activations: one name per hidden layer (default: `activation` everywhere)."""
+    depth); activations: one name per hidden layer (default: `activation` everywhere).  learnable_sigma: True — the reference's idiom,
+    `NormalVariable(chain, sigma, "y", learnable=True)`: a learnable root `y_scale` behind a softplus in the joint model's parameter
+    group; "exp" — `BF.exp` of a learnable root `y_log_scale`; the model's sigma then starts at sigma_init (one number or one per
+    output; default: the teacher's sigma).  Without the keyword every model is built draw for draw as before."""
     BF = api.BF
+    if learnable_sigma not in (False, True, "exp"):
+        raise ValueError("learnable_sigma is False, True (the reference's flag) or \"exp\"")
+    if sigma_init is not None and not learnable_sigma:
+        raise ValueError("sigma_init is the start of a learnable sigma")
     n_features, n_outputs, widths = _bnn_widths(widths, n_features, ([n_hidden] if n_hidden else []) + ([hidden2] if n_hidden and hidden2 else []),
                                                 n_outputs)
     rng = np.random.RandomState(seed)
@@ -895,7 +902,14 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
         layer = getattr(BF, acts[l - 1])(pre) if l + 1 < len(widths) else pre
         q_vars.append(api.NormalVariable(q_loc_scale * sw * rng.normal(0., 1., (rows, cols)), sw * np.ones((rows, cols)),
                                          "weights%d" % l, learnable=True))
-    y = api.NormalVariable(layer, float(sig[0]) if sig.size == 1 else sig.reshape(n_outputs, 1), "y")
+    if sigma_init is not None:
+        sig = np.asarray(sigma_init, dtype=np.float64).reshape(-1)
+        if sig.size not in (1, n_outputs):
+            raise ValueError("sigma_init is one number or one per output")
+    scale = float(sig[0]) if sig.size == 1 else sig.reshape(n_outputs, 1)
+    if learnable_sigma == "exp":
+        scale = BF.exp(api.RootVariable(np.log(scale), "y_log_scale", learnable=True))
+    y = api.NormalVariable(layer, scale, "y", learnable=bool(learnable_sigma is True))
     model = api.ProbabilisticModel([y])
     y.observe(targets)
     model.set_posterior_model(api.ProbabilisticModel(q_vars))

@@ -9,6 +9,11 @@ family (two MFMA products with the minibatch, the Normal likelihood between them
 MI355X:
 
     python examples/bnn_regression.py
+    python examples/bnn_regression.py --learn-sigma      # sigma learnable: NormalVariable(chain, 1.0, "y", learnable=True)
+
+With --learn-sigma the model starts from a guess of 1.0 and learns the noise scale with the posterior (a learnable root `y_scale`
+behind a softplus in the joint model's parameter group, stepped from the second iteration on, as the reference steps it); the learned
+value is printed beside the teacher's.
 """
 import os
 import sys
@@ -20,7 +25,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from brancher_amd import engine, inference, workloads as W
 
+LEARN_SIGMA = "--learn-sigma" in sys.argv[1:]
 KW = dict(dataset_size=512, batch_size=30, n_features=784, n_hidden=20, n_outputs=1, sigma=0.5)
+if LEARN_SIGMA:
+    KW.update(learnable_sigma=True, sigma_init=1.0)
 
 
 def dataset_of(variable):
@@ -48,3 +56,7 @@ seconds = time.time() - t0
 loss = np.asarray(model.diagnostics["loss curve"])
 print("1500 iterations in %.2f s; loss %.1f -> %.1f" % (seconds, loss[:20].mean(), loss[-20:].mean()))
 print("RMSE of the posterior-mean prediction after training:  %.3f" % posterior_mean_rmse(model))
+if LEARN_SIGMA:
+    theta = float(engine.compile_model(model).named_params()["y_scale"].reshape(-1)[0])
+    print("learned noise scale sigma = softplus(y_scale) = %.3f (started at %.2f; the teacher's noise: %.2f)"
+          % (np.log1p(np.exp(theta)), KW["sigma_init"], KW["sigma"]))

@@ -597,6 +597,15 @@ int bsvi_bnn_create(const bsvi_bnn_desc* desc, bsvi_bnn** out);
  * output:  f += lik_weight * (-1/2 u^2 - log sigma_c - 1/2 log 2 pi),  u = (y_c - z_c) / sigma_c.  Everything else is as for
  * bsvi_bnn_create, whose handle type and calls it shares; bsvi_bnn_create itself refuses this likelihood. */
 int bsvi_bnn_create_normal(const bsvi_bnn_desc* desc, uint32_t scale_uniform, uint32_t scale_stride, bsvi_bnn** out);
+/* The same model with a LEARNABLE sigma — the reference's `NormalVariable(chain, 0.5, "y", learnable=True)`
+ * (standard_variables.py:57-67: a learnable root `y_scale` behind the softplus of geometric_ranges.py, in the joint model's parameter
+ * group, which inference.py:99-104 steps from iteration 1 on).  Every entry scale_uniform + c * scale_stride is a PARAMETER's
+ * (index < n_uniform_grad) with transform softplus, exp or sigmoid: all constants or a mix of the two is BSVI_ERR_INVALID (constants
+ * are bsvi_bnn_create_normal's), another transform BSVI_ERR_UNSUPPORTED (a step could carry a bare parameter through zero).  The launches
+ * add  G_c = sum_n sum_b lik_weight a_n (u^2 - 1) / sigma_c  to the gradient of output c's entry (stride 0: the sum over c), in a fixed
+ * order and on top of what the entry's rows contribute — one entry may be a prior scale and sigma; the chain rule through the
+ * transform, finalize and the optimizer step are those of every other entry.  No struct changes, the ABI version stays. */
+int bsvi_bnn_create_normal_learnable(const bsvi_bnn_desc* desc, uint32_t scale_uniform, uint32_t scale_stride, bsvi_bnn** out);
 void bsvi_bnn_destroy(bsvi_bnn* b);
 size_t bsvi_bnn_workspace_bytes(const bsvi_bnn* b, uint32_t n_samples_local);
 int bsvi_bnn_exact_data(const bsvi_bnn* b);
