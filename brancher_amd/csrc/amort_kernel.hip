@@ -36,6 +36,7 @@
 #include <utility>
 #include <vector>
 
+#include "amort_select.h"
 #include "bsvi.h"
 #include "bsvi_internal.h"
 #include "philox.h"
@@ -48,10 +49,49 @@ using bsvi::u32x4;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int BM = 128, BN = 128, BK = 16, NTHREADS = 256;
+namespace sel = bsvi_amort_select;       // the tile constants, the plans and every kernel choice: amort_select.h
+using sel::BM; using sel::BN; using sel::BK; using sel::XBK; using sel::SKINNY;
+using sel::MODE_NT; using sel::MODE_NN; using sel::MODE_TN;
+using sel::TnPlan; using sel::tn_plan; using sel::X6TnPlan; using sel::XdwPlan; using sel::xdw_plan; using sel::align4;
+constexpr int NTHREADS = 256;
 constexpr float kHalfLog2Pi = 0.91893853320467274178f;
 
-enum { MODE_NT = 0, MODE_NN = 1, MODE_TN = 2 };
+// The selection's switches from the environment: the only place in this file that names them.  BSVI_X6_MODES, BSVI_AMORT_FUSE_LIK and
+// BSVI_X6_V are read at every call (once per bsvi_amort_fwd_bwd / bsvi_debug_gemm: tests switch them), the others once per process.
+static const sel::Switches& process_switches() {
+    static const sel::Switches process = [] {
+        sel::Switches sw;
+        auto num = [](const char* var, int unset) { const char* e = getenv(var); return e ? atoi(e) : unset; };
+        auto is = [](const char* var, char c) { const char* e = getenv(var); return e && e[0] == c; };
+        sw.second_generation = !is("BSVI_NARROW_GEN", '1');
+        sw.skinny_rows = num("BSVI_SKINNY_ROWS", sw.skinny_rows);
+        sw.half_below = num("BSVI_GEMM_HALF_BELOW", sw.half_below);
+        if (const char* e = getenv("BSVI_GEMM_PF"))
+            for (int m = 0; m < 3 && strlen(e) == 3; ++m) sw.pf[m] = e[m] == '2' ? 2 : 1;
+        sw.x6_var = num("BSVI_X6_VAR", sw.x6_var);
+        sw.x6_debug = num("BSVI_X6_DEBUG", sw.x6_debug);
+        sw.xgemm_tall = is("BSVI_XGEMM_TALL", '1');
+        sw.xgemm_glds = !is("BSVI_XGEMM_GLDS", '0');
+        sw.x6tn_slots = num("BSVI_X6TN_SLOTS", sw.x6tn_slots);
+        sw.x6_nn_only = num("BSVI_X6_NN_ONLY", sw.x6_nn_only);
+        sw.x6_tn = !is("BSVI_X6_TN", '0');
+        sw.x6_tn_data = !is("BSVI_X6_TN_DATA", '0');
+        return sw;
+    }();
+    return process;
+}
+static sel::Switches read_switches() {
+    sel::Switches sw = process_switches();
+    const char* e = getenv("BSVI_X6_MODES");
+    if (e) sw.x6_modes = atoi(e);
+    e = getenv("BSVI_AMORT_FUSE_LIK");
+    sw.fuse_lik = !(e && e[0] == '0');
+    e = getenv("BSVI_X6_V");
+    sw.x6_v6 = !(e && e[0] == '5');
+    return sw;
+}
+static X6TnPlan x6tn_plan(int M, int N, int K) { return sel::x6tn_plan(M, N, K, process_switches().x6tn_slots); }
+static size_t tn_partial_floats(int M, int N, int K, bool bias) { return sel::tn_partial_floats(M, N, K, bias, process_switches().x6tn_slots); }
 
 struct GemmArgs {
     const float* A;
@@ -415,7 +455,6 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmArgs G) {
 // A dataset with any inexact value runs on the f32 kernel above.  BSVI_AMORT_XGEMM=0 forces that too.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t xu4 __attribute__((ext_vector_type(4)));   // (ext vectors, not HIP's uint4 struct: copies of that through pointer casts land in scratch)
-constexpr int XBK = 32;                 // k per step: two MFMA k chunks of 16
 constexpr int XLD = 80;                 // LDS row stride in bytes (64 data + 16 pad: 16 consecutive rows hit 16 disjoint bank quads)
 constexpr int XPLANE = 128 * XLD;       // one 128-row operand tile
 
@@ -734,23 +773,15 @@ __global__ __launch_bounds__(256, 2) void xgemm_nt_glds_kernel(const XGemmArgs G
         }
 }
 
-static void launch_xgemm(XGemmArgs X, hipStream_t stream) {
-    X.rows_fastest = 3L * X.N > (long)X.M ? 1 : 0;      // which operand is the larger one (both have Kp columns)
-    // (measured, cfg 4's two products: 256-row tiles 66 us each at two waves per SIMD — fewer LDS reads per MFMA, but one
-    //  workgroup per CU at these shapes — against 45 us with 128-row tiles at three; BSVI_XGEMM_TALL=1 selects the tall tile)
-    static const bool tall_env = [] { const char* e = getenv("BSVI_XGEMM_TALL"); return e && e[0] == '1'; }();
-    const bool tall = tall_env && X.M >= 256;
-    static const bool glds = [] { const char* e = getenv("BSVI_XGEMM_GLDS"); return !(e && e[0] == '0'); }();
-    if (glds) {
-        const unsigned tiles_g = (unsigned)(((X.M + (tall ? 255 : 127)) / (tall ? 256 : 128)) * ((X.N + 127) / 128));
-        if (tall) hipLaunchKernelGGL((xgemm_nt_glds_kernel<256, false>), dim3(tiles_g), dim3(256), 0, stream, X);
-        else hipLaunchKernelGGL((xgemm_nt_glds_kernel<128, false>), dim3(tiles_g), dim3(256), 0, stream, X);
-        return;
+static void launch_xgemm(XGemmArgs X, const sel::Switches& sw, hipStream_t stream) {
+    const sel::Selection s = sel::select_xgemm(X.M, X.N, sw);
+    X.rows_fastest = s.rows_fastest;
+    switch (s.kind) {
+    case sel::XGEMM_GLDS_128: hipLaunchKernelGGL((xgemm_nt_glds_kernel<128, false>), dim3(s.grid_x), dim3(s.block), 0, stream, X); break;
+    case sel::XGEMM_GLDS_256: hipLaunchKernelGGL((xgemm_nt_glds_kernel<256, false>), dim3(s.grid_x), dim3(s.block), 0, stream, X); break;
+    case sel::XGEMM_REG_128: hipLaunchKernelGGL((xgemm_nt_kernel<128>), dim3(s.grid_x), dim3(s.block), 0, stream, X); break;
+    default: hipLaunchKernelGGL((xgemm_nt_kernel<256>), dim3(s.grid_x), dim3(s.block), 0, stream, X); break;
     }
-    const int tbm = tall ? 256 : 128;
-    const unsigned tiles = (unsigned)(((X.M + tbm - 1) / tbm) * ((X.N + 127) / 128));
-    if (tall) hipLaunchKernelGGL((xgemm_nt_kernel<256>), dim3(tiles), dim3(256), 0, stream, X);
-    else hipLaunchKernelGGL((xgemm_nt_kernel<128>), dim3(tiles), dim3(256), 0, stream, X);
 }
 
 // ---- the weight gradient of the data layer on the same pieces ---------------------------------------------------------
@@ -758,21 +789,8 @@ static void launch_xgemm(XGemmArgs X, hipStream_t stream) {
 // three bf16 pieces.  The MFMA wants k (= the row r) contiguous in both operands: dy_split_t_kernel writes the pieces
 // transposed, [3][n_out][Rp], and xt_gather_kernel the gathered data rows transposed, [P][Rp] (it only needs the
 // minibatch indices, so it runs on the side stream beside the forward pass).  xgemm_nt_glds_kernel<128, true> then
-// multiplies slices of the rows (split-k) and writes one partial [n_out][P] per slice for reduce_partials.
+// multiplies slices of the rows (split-k, sel::xdw_plan) and writes one partial [n_out][P] per slice for reduce_partials.
 // Rp = R rounded up to 64 (rows beyond R are zero in both operands).
-struct XdwPlan { int Rp, steps, steps_per_split, slices, grid_splits, tiles; };
-static XdwPlan xdw_plan(int P, int n_out, size_t R) {
-    XdwPlan p{};
-    p.Rp = (int)((R + 63) / 64 * 64);
-    p.steps = p.Rp / XBK;
-    p.tiles = ((P + 127) / 128) * ((n_out + 127) / 128);
-    const int want = std::max(1, std::min(p.steps, 512 / std::max(p.tiles, 1)));     // two workgroups per CU, one round
-    p.steps_per_split = (p.steps + want - 1) / want;
-    p.slices = (p.steps + p.steps_per_split - 1) / p.steps_per_split;
-    p.grid_splits = p.slices;
-    while ((p.grid_splits * p.tiles) % 8) ++p.grid_splits;       // whole XCD shares; the padding workgroups exit
-    return p;
-}
 
 // ---- f32 x f32 products on the bf16 matrix cores: six products of exact pieces ("bf16x6") ------------------------------------
 // Every f32 is EXACTLY the sum of three bf16 numbers hi + mid + lo (8 + 8 + 8 significant bits, xw_split_kernel above), and a
@@ -1503,19 +1521,6 @@ __global__ __launch_bounds__(256, 2) void x6tn_kernel(const X6TnArgs G) {
     }
 }
 
-struct X6TnPlan { int tiles, splits, chunk, slices; };
-// 128 x 128 tiles, two workgroups per CU: as many slices of the rows as fill 512 slots in ONE round
-static X6TnPlan x6tn_plan(int M, int N, int K) {
-    X6TnPlan p{};
-    p.tiles = ((M + 127) / 128) * ((N + 127) / 128);
-    static const int slots = [] { const char* e = getenv("BSVI_X6TN_SLOTS"); return e ? atoi(e) : 512; }();
-    const int splits = std::max(1, std::min((K + XBK - 1) / XBK, slots / std::max(p.tiles, 1)));
-    p.chunk = ((K + splits - 1) / splits + XBK - 1) / XBK * XBK;
-    p.slices = (K + p.chunk - 1) / p.chunk;
-    p.splits = p.slices;
-    return p;
-}
-
 // dY [R][ld] f32 -> T [3][N][Rp] bf16 pieces, and the column sums of every 64-row block (the bias gradient's partials)
 __global__ __launch_bounds__(256) void dy_split_t_kernel(const float* dY, int ld, int R, int Rp, int N, uint16_t* T, float* colsum) {
     __shared__ float tile[64][65];
@@ -1612,7 +1617,6 @@ __device__ __forceinline__ float wave_sum64(float v) {
 }
 
 // ---- layers with a side of width <= 8 (latent heads, first decoder layer): memory-bound, no matrix cores ----------
-constexpr int SKINNY = 8;
 
 __device__ __forceinline__ float skinny_epilogue(const GemmArgs& G, int mode, float v, long r, int n) {
     float* c = G.C + r * G.ldc + n;
@@ -2723,7 +2727,7 @@ int bsvi_xgemm_nt(const uint16_t* X, const int32_t* rows, const uint16_t* Wp, lo
     if (Kp % bsvi_amort_impl::XBK != 0 || M <= 0 || N <= 0) return bsvi_fail(BSVI_ERR_INVALID, "bsvi_xgemm_nt: bad shape");
     bsvi_amort_impl::XGemmArgs G{};
     G.X = X; G.rows = rows; G.Wp = Wp; G.plane_stride = plane_stride; G.C = C; G.ldc = ldc; G.M = M; G.N = N; G.Kp = Kp;
-    bsvi_amort_impl::launch_xgemm(G, (hipStream_t)stream);
+    bsvi_amort_impl::launch_xgemm(G, bsvi_amort_impl::read_switches(), (hipStream_t)stream);
     if (hipGetLastError() != hipSuccess) return bsvi_fail(BSVI_ERR_HIP, "xgemm_nt_kernel launch failed");
     return BSVI_OK;
 }
@@ -2766,46 +2770,12 @@ extern "C" void bsvi_amort_destroy(bsvi_amort* a) {
     delete a;
 }
 
-// How a weight-gradient product C[M][N] = A[K][M]^T B[K][N] (K = all rows) is cut along K: every slice writes its own
-// partial [M][N] (and partial column sums of A, [M]) and reduce_partials adds the slices in order.
-struct TnPlan {
-    bool skinny;
-    int tiles, splits, chunk;      // MFMA path: output tiles, grid splits (whole splits per XCD; padding ones exit), rows per split
-    int slices;                    // partials actually written
-};
-static TnPlan tn_plan(int M, int N, int K) {
-    TnPlan p{};
-    if (M <= SKINNY || N <= SKINNY) {
-        p.skinny = true;
-        p.chunk = 64;
-        p.slices = (K + p.chunk - 1) / p.chunk;
-        return p;
-    }
-    // about three workgroups per CU in flight, 64-row output tiles (less padding, half the splits of 128-row tiles);
-    // at most 768 workgroups = three per CU in ONE round (a 769th would make some CU run four)
-    p.tiles = ((M + 63) / 64) * ((N + BN - 1) / BN);
-    int splits = std::max(1, std::min((K + BK - 1) / BK, 768 / std::max(p.tiles, 1)));
-    p.chunk = ((K + splits - 1) / splits + BK - 1) / BK * BK;
-    p.slices = (K + p.chunk - 1) / p.chunk;
-    p.splits = (p.slices + 7) / 8 * 8;
-    return p;
-}
-static size_t align4(size_t n) { return (n + 3) / 4 * 4; }      // partial regions start on 16-byte boundaries
-static size_t tn_partial_floats(int M, int N, int K, bool bias) {
-    const TnPlan p = tn_plan(M, N, K);
-    // (the six-piece form of the same product, x6tn_kernel, cuts the rows into its own number of slices: room for either)
-    const size_t slices = p.skinny ? (size_t)p.slices : std::max<size_t>((size_t)p.slices, (size_t)x6tn_plan(M, N, K).slices);
-    return align4(slices * M * N) + (bias ? align4(slices * M) : 0);
-}
-
 // floats of the partial sums behind the per-row part of the workspace: one slice set per Linear layer (weights + bias)
 // and the workgroup partials of the loss sums
 // does encoder layer li take its weight gradient through the exact-data product at R rows?
 static bool xdw_layer(const bsvi_amort* a, size_t li, size_t R) {
     if (!a->xdw || li >= a->weight_pieces.size() || !a->weight_pieces[li]) return false;
-    const size_t Rp = (R + 63) / 64 * 64;
-    const auto& l = a->enc.layers[li];
-    return std::max<size_t>(3 * (size_t)l.n_out, l.n_in) * Rp * 2 < 0xF0000000ull;      // 32-bit byte offsets in the kernel
+    return sel::xdw_fits(a->enc.layers[li].n_out, a->enc.layers[li].n_in, R);
 }
 static size_t xdw_floats(const bsvi_amort* a, size_t li, size_t R) {      // slice partials, bias partials, the pieces of dY
     const auto& l = a->enc.layers[li];
@@ -2842,153 +2812,83 @@ extern "C" size_t bsvi_amort_workspace_bytes(const bsvi_amort* a, uint32_t n_sam
     return (R * a->floats_per_row + 64 + partial_floats(a, R)) * sizeof(float);
 }
 
-// steps of global loads kept in flight by the MFMA kernels, per operand layout (BSVI_GEMM_PF=<nt><nn><tn>, e.g. 112)
-static int prefetch_depth(int mode) {
-    static const std::string cfg = [] { const char* e = getenv("BSVI_GEMM_PF"); return std::string(e && strlen(e) == 3 ? e : "222"); }();
-    return cfg[mode] == '2' ? 2 : 1;
+// ---- the three launchers: select (amort_select.h), then one switch over the kind that launches
+static uintptr_t addr(const void* p) { return (uintptr_t)p; }
+static sel::Facts facts_of(const GemmArgs& G) {
+    sel::Facts f;
+    f.M = G.M; f.N = G.N; f.K = G.K; f.lda = G.lda; f.ldb = G.ldb; f.ldc = G.ldc; f.ldy = G.ldy; f.part_stride = G.part_stride;
+    f.a = addr(G.A); f.b = addr(G.B); f.c = addr(G.C); f.bias = addr(G.bias); f.y = addr(G.Y); f.bias_grad = addr(G.bias_grad);
+    return f;
+}
+static sel::Facts facts_of(const X6Args& X) {
+    sel::Facts f;
+    f.M = X.M; f.N = X.N; f.K = X.K; f.lda = X.lda; f.ldc = X.ldc; f.ldy = X.ldy; f.plane_stride = X.plane_stride;
+    f.a = addr(X.A); f.b = addr(X.Bp); f.c = addr(X.C); f.bias = addr(X.bias); f.y = addr(X.Y);
+    return f;
 }
 
-// rows from which the 128-row tiles of x6gemm_kernel fill the chip better than the f32 kernel's 64-row ones
-constexpr int kX6MinRows = 256;
-static int launch_x6(bool nn, const X6Args& X, hipStream_t stream) {
-    const int tiles = ((X.M + 127) / 128) * ((X.N + 127) / 128);
-    static const int dbg = [] { const char* e = getenv("BSVI_X6_DEBUG"); return e ? atoi(e) : 0; }();
-    // round 6's kernel (LDS-DMA staging, 16-byte stores) wants 16-byte aligned rows of every matrix it touches with wide accesses;
-    // anything else — and BSVI_X6_V=5 — takes round 5's kernel, which stages through registers
-    static const bool v6 = [] { const char* e = getenv("BSVI_X6_V"); return !(e && e[0] == '5'); }();
-    auto al16 = [](const void* p, int ld) { return ((uintptr_t)p & 15) == 0 && (ld & 3) == 0; };
-    const bool wide_ok = v6 && (X.N & 3) == 0 && al16(X.A, X.lda) && al16(X.C, X.ldc) && (!X.Y || al16(X.Y, X.ldy)) && ((uintptr_t)X.Bp & 15) == 0;
-    static const int var = [] { const char* e = getenv("BSVI_X6_VAR"); return e ? atoi(e) : 1; }();      // 1: the hand-ordered main loop (default), 0: the compiler's order
-    if (wide_ok && ((size_t)(X.M - 1) * X.lda + X.K) * sizeof(float) < 0x7fffffffull && 3 * (size_t)X.plane_stride * 2 < 0x7fffffffull) {
-#define BSVI_X6_LAUNCH(NNV, D, V) hipLaunchKernelGGL((x6gemm_kernel<NNV, D, V>), dim3(tiles), dim3(256), 0, stream, X)
-        if (!nn && dbg == 2) BSVI_X6_LAUNCH(false, 2, 0);
-        else if (!nn && dbg == 3) BSVI_X6_LAUNCH(false, 3, 0);
-        else if (!nn && dbg == 4) BSVI_X6_LAUNCH(false, 4, 0);
-        else if (!nn && dbg == 5) BSVI_X6_LAUNCH(false, 5, 0);
-        else if (!nn && dbg == 9) BSVI_X6_LAUNCH(false, 9, 1);
-        else if (nn && dbg == 12) BSVI_X6_LAUNCH(true, 2, 0);
-        else if (nn && dbg == 13) BSVI_X6_LAUNCH(true, 3, 0);
-        else if (!nn && X.lik_x) hipLaunchKernelGGL((x6gemm_kernel<false, 0, 1, true>), dim3(tiles), dim3(256), 0, stream, X);
-        else if (var == 1) { if (nn) BSVI_X6_LAUNCH(true, 0, 1); else BSVI_X6_LAUNCH(false, 0, 1); }
-        else if (nn) BSVI_X6_LAUNCH(true, 0, 0);
-        else BSVI_X6_LAUNCH(false, 0, 0);
+// s: select_x6's answer for X.  The likelihood's fields of X are filled by the caller only when s.lik says that kernel runs.
+static int launch_x6(const sel::Selection& s, const X6Args& X, hipStream_t stream) {
+    switch (s.kind) {
+#define BSVI_X6_LAUNCH(KIND, ...) case sel::KIND: hipLaunchKernelGGL((__VA_ARGS__), dim3(s.grid_x), dim3(s.block), 0, stream, X); break;
+    BSVI_X6_LAUNCH(X6_NT, x6gemm_kernel<false, 0, 0>)
+    BSVI_X6_LAUNCH(X6_NT_VAR1, x6gemm_kernel<false, 0, 1>)
+    BSVI_X6_LAUNCH(X6_NT_LIK, x6gemm_kernel<false, 0, 1, true>)
+    BSVI_X6_LAUNCH(X6_NT_DBG2, x6gemm_kernel<false, 2, 0>)
+    BSVI_X6_LAUNCH(X6_NT_DBG3, x6gemm_kernel<false, 3, 0>)
+    BSVI_X6_LAUNCH(X6_NT_DBG4, x6gemm_kernel<false, 4, 0>)
+    BSVI_X6_LAUNCH(X6_NT_DBG5, x6gemm_kernel<false, 5, 0>)
+    BSVI_X6_LAUNCH(X6_NT_DBG9, x6gemm_kernel<false, 9, 1>)
+    BSVI_X6_LAUNCH(X6_NN, x6gemm_kernel<true, 0, 0>)
+    BSVI_X6_LAUNCH(X6_NN_VAR1, x6gemm_kernel<true, 0, 1>)
+    BSVI_X6_LAUNCH(X6_NN_DBG2, x6gemm_kernel<true, 2, 0>)
+    BSVI_X6_LAUNCH(X6_NN_DBG3, x6gemm_kernel<true, 3, 0>)
+    BSVI_X6_LAUNCH(X6_R5_NT, x6gemm_r5_kernel<false>)
+    BSVI_X6_LAUNCH(X6_R5_NN, x6gemm_r5_kernel<true>)
 #undef BSVI_X6_LAUNCH
-    } else if (nn) hipLaunchKernelGGL((x6gemm_r5_kernel<true>), dim3(tiles), dim3(256), 0, stream, X);
-    else hipLaunchKernelGGL((x6gemm_r5_kernel<false>), dim3(tiles), dim3(256), 0, stream, X);
+    default: return bsvi_fail(BSVI_ERR_INVALID, "launch_x6: not a six-piece kind");
+    }
     HIP_TRY(hipGetLastError());
     return BSVI_OK;
 }
+static int launch_x6(bool nn, const X6Args& X, const sel::Switches& sw, hipStream_t stream) {
+    return launch_x6(sel::select_x6(nn, facts_of(X), false, sw), X, stream);
+}
 
-static int launch_gemm(int mode, GemmArgs G, hipStream_t stream) {
-    if (G.M <= 0 || G.N <= 0 || G.K <= 0) return BSVI_OK;
-    auto aligned = [](const void* p, int ld) { return ((uintptr_t)p % 16 == 0) && (ld % 4 == 0); };
-    G.vecA = aligned(G.A, G.lda);
-    G.vecB = aligned(G.B, G.ldb);
-    // a side of width <= 8: the memory-bound kernels
-    static const bool second_generation = [] { const char* e = getenv("BSVI_NARROW_GEN"); return !(e && e[0] == '1'); }();
-    if (mode == MODE_TN && (G.M <= SKINNY || G.N <= SKINNY)) {
-        const int narrow_is_a = G.M <= G.N ? 1 : 0;
-        const int wide = narrow_is_a ? G.N : G.M, narrow = narrow_is_a ? G.M : G.N;
-        const int rows_per_block = tn_plan(G.M, G.N, G.K).chunk;
-        const bool wide_vec = narrow_is_a ? G.vecB : G.vecA, narrow_vec = narrow_is_a ? G.vecA : G.vecB;
-        const bool out_vec = !narrow_is_a || (G.ldc % 4 == 0 && (uintptr_t)G.C % 16 == 0 && G.part_stride % 4 == 0);
-        const bool bias_vec = !G.bias_grad || narrow_is_a || (G.M % 4 == 0 && (uintptr_t)G.bias_grad % 16 == 0);
-        if (second_generation && wide % 4 == 0 && wide_vec && narrow_vec && out_vec && bias_vec) {
-            // (the padded leading dimension of the narrow operand covers the 16-byte loads: ld >= 4 ceil(narrow / 4))
-            dim3 grid((wide / 4 + 255) / 256, (G.K + rows_per_block - 1) / rows_per_block);
-            if (narrow <= 4) hipLaunchKernelGGL((outer_kernel<4>), grid, dim3(256), 0, stream, G, narrow_is_a, rows_per_block);
-            else hipLaunchKernelGGL((outer_kernel<8>), grid, dim3(256), 0, stream, G, narrow_is_a, rows_per_block);
-            HIP_TRY(hipGetLastError());
-            return BSVI_OK;
-        }
-        dim3 grid((wide + 255) / 256, (G.K + rows_per_block - 1) / rows_per_block);
-        hipLaunchKernelGGL(skinny_tn_kernel, grid, dim3(256), 0, stream, G, narrow_is_a, rows_per_block);
-        HIP_TRY(hipGetLastError());
-        return BSVI_OK;
-    }
-    if (mode != MODE_TN) {
-        const int sbk = mode == MODE_NT ? 1 : G.ldb, sbn = mode == MODE_NT ? G.ldb : 1;
-        if (second_generation && G.N <= SKINNY && G.K % 4 == 0 && G.vecA && (size_t)G.K * SKINNY * sizeof(float) <= 64 * 1024) {
-            const int rows_per_block = 32;
-            const dim3 grid((G.M + rows_per_block - 1) / rows_per_block);
-            if (G.N <= 2) hipLaunchKernelGGL((rowdot_kernel<2>), grid, dim3(256), (size_t)2 * G.K * sizeof(float), stream, G, sbk, sbn, mode, rows_per_block);
-            else if (G.N <= 4) hipLaunchKernelGGL((rowdot_kernel<4>), grid, dim3(256), (size_t)4 * G.K * sizeof(float), stream, G, sbk, sbn, mode, rows_per_block);
-            else hipLaunchKernelGGL((rowdot_kernel<8>), grid, dim3(256), (size_t)8 * G.K * sizeof(float), stream, G, sbk, sbn, mode, rows_per_block);
-            HIP_TRY(hipGetLastError());
-            return BSVI_OK;
-        }
-        if (G.N <= SKINNY && (size_t)G.N * G.K <= 8192) {
-            static const int rows_per_block = [] { const char* e = getenv("BSVI_SKINNY_ROWS"); return e ? atoi(e) : 16; }();
-            hipLaunchKernelGGL(skinny_n_kernel, dim3((G.M + rows_per_block - 1) / rows_per_block), dim3(256),
-                               (size_t)G.N * G.K * sizeof(float), stream, G, sbk, sbn, mode, rows_per_block);
-            HIP_TRY(hipGetLastError());
-            return BSVI_OK;
-        }
-        if (G.K <= SKINNY && (uint64_t)G.M * (uint64_t)G.N < (1ull << 32) - 256) {
-            auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-            if (second_generation && mode == MODE_NT && G.ldb == G.K && (G.N & 3) == 0 && al16(G.B) && (G.ldc & 3) == 0 && al16(G.C) &&
-                (!G.bias || al16(G.bias))) {
-                const dim3 grid((unsigned)(((long)G.M * (G.N >> 2) + 255) / 256));
-                switch (G.K) {
-#define BSVI_K4NT(KK) case KK: hipLaunchKernelGGL((skinny_k4nt_kernel<KK>), grid, dim3(256), 0, stream, G); break;
-                    BSVI_K4NT(1) BSVI_K4NT(2) BSVI_K4NT(3) BSVI_K4NT(4) BSVI_K4NT(5) BSVI_K4NT(6) BSVI_K4NT(7) BSVI_K4NT(8)
+static int launch_gemm(int mode, GemmArgs G, const sel::Switches& sw, hipStream_t stream) {
+    const sel::Selection s = sel::select_f32(mode, facts_of(G), sw);
+    const dim3 grid(s.grid_x, s.grid_y), block(s.block);
+    G.vecA = s.vecA; G.vecB = s.vecB; G.remap = s.remap; G.k_chunk = s.k_chunk; G.tiles = s.tiles;      // (k_chunk, tiles: 0 but for TN)
+    switch (s.kind) {
+    case sel::NONE: return BSVI_OK;
+#define BSVI_LAUNCH(KIND, KERNEL, ...) case sel::KIND: hipLaunchKernelGGL(KERNEL, grid, block, s.lds, stream, __VA_ARGS__); break;
+    BSVI_LAUNCH(OUTER4, outer_kernel<4>, G, s.narrow_is_a, s.rows_per_block)
+    BSVI_LAUNCH(OUTER8, outer_kernel<8>, G, s.narrow_is_a, s.rows_per_block)
+    BSVI_LAUNCH(SKINNY_TN, skinny_tn_kernel, G, s.narrow_is_a, s.rows_per_block)
+    BSVI_LAUNCH(ROWDOT2, rowdot_kernel<2>, G, s.sbk, s.sbn, mode, s.rows_per_block)
+    BSVI_LAUNCH(ROWDOT4, rowdot_kernel<4>, G, s.sbk, s.sbn, mode, s.rows_per_block)
+    BSVI_LAUNCH(ROWDOT8, rowdot_kernel<8>, G, s.sbk, s.sbn, mode, s.rows_per_block)
+    BSVI_LAUNCH(SKINNY_N, skinny_n_kernel, G, s.sbk, s.sbn, mode, s.rows_per_block)
+#define BSVI_K4NT(KK) BSVI_LAUNCH(SKINNY_K4NT_##KK, skinny_k4nt_kernel<KK>, G)
+    BSVI_K4NT(1) BSVI_K4NT(2) BSVI_K4NT(3) BSVI_K4NT(4) BSVI_K4NT(5) BSVI_K4NT(6) BSVI_K4NT(7) BSVI_K4NT(8)
 #undef BSVI_K4NT
-                }
-                HIP_TRY(hipGetLastError());
-                return BSVI_OK;
-            }
-            // (B stored [N][K], the forward layout, would need strided scalar loads per output: measured slower)
-            const bool vec4 = sbn == 1 && (sbk & 3) == 0 && al16(G.B) && (G.N & 3) == 0 && (G.ldc & 3) == 0 && al16(G.C) &&
-                              (!G.bias || al16(G.bias)) && (!G.Y || ((G.ldy & 3) == 0 && al16(G.Y)));
-            if (vec4) {
-                const long quads = (long)G.M * (G.N >> 2);
-                hipLaunchKernelGGL(skinny_k4_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, stream, G, sbk, sbn, mode);
-                HIP_TRY(hipGetLastError());
-                return BSVI_OK;
-            }
-            const long total = (long)G.M * G.N;
-            hipLaunchKernelGGL(skinny_k_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, G, sbk, sbn, mode);
-            HIP_TRY(hipGetLastError());
-            return BSVI_OK;
-        }
-    }
-    const int tiles_n = (G.N + BN - 1) / BN;
-    int tiles = ((G.M + BM - 1) / BM) * tiles_n;
-    if (mode == MODE_TN) {
-        const TnPlan plan = tn_plan(G.M, G.N, G.K);
-        tiles = plan.tiles;
-        const int splits = plan.splits;
-        G.k_chunk = plan.chunk;
-        G.tiles = tiles;
-        G.remap = 1;
-        dim3 grid(tiles * splits, 1, 1);
-        if (prefetch_depth(mode) == 2) hipLaunchKernelGGL((gemm_kernel<MODE_TN, 64, 2>), grid, dim3(NTHREADS), 0, stream, G);
-        else hipLaunchKernelGGL((gemm_kernel<MODE_TN, 64, 1>), grid, dim3(NTHREADS), 0, stream, G);
-    } else {
-        // (round 4, measured and removed: stream-K — a grid of the resident slots, equal runs of (128 x 128 tile, k step) units
-        //  per workgroup, a cut tile finished by the later workgroup in a fixed order.  cfg 5's layers at 25 600 rows: 136 /
-        //  117 / 94 / 179 us forward and 108 / 158 / 140 us input gradient against 126 / 81 / 84 / 125 and 89 / 93 / 118 here.
-        //  With K = 256 ... 784 a tile is 16 ... 49 steps: what these shapes pay for is the tile's prologue and its 64 scalar
-        //  stores per thread, which four co-resident 64-row workgroups hide from each other and three persistent 128-row ones
-        //  do not — not the uneven last round the shape count suggested.)
-        // 64-row tiles when 128-row tiles would leave most CUs with one or two workgroups
-        static const int half_below = [] { const char* e = getenv("BSVI_GEMM_HALF_BELOW"); return e ? atoi(e) : 1536; }();
-        const bool half = tiles < half_below && G.M > 64;
-        if (half) tiles = ((G.M + 63) / 64) * tiles_n;
-        G.remap = (tiles % 8 == 0) ? 1 : 0;
-        dim3 grid(tiles, 1, 1);
-        const bool deep = prefetch_depth(mode) == 2;
-        if (mode == MODE_NT) {
-            if (half && deep) hipLaunchKernelGGL((gemm_kernel<MODE_NT, 64, 2>), grid, dim3(NTHREADS), 0, stream, G);
-            else if (half) hipLaunchKernelGGL((gemm_kernel<MODE_NT, 64, 1>), grid, dim3(NTHREADS), 0, stream, G);
-            else if (deep) hipLaunchKernelGGL((gemm_kernel<MODE_NT, 128, 2>), grid, dim3(NTHREADS), 0, stream, G);
-            else hipLaunchKernelGGL((gemm_kernel<MODE_NT, 128, 1>), grid, dim3(NTHREADS), 0, stream, G);
-        } else {
-            if (half && deep) hipLaunchKernelGGL((gemm_kernel<MODE_NN, 64, 2>), grid, dim3(NTHREADS), 0, stream, G);
-            else if (half) hipLaunchKernelGGL((gemm_kernel<MODE_NN, 64, 1>), grid, dim3(NTHREADS), 0, stream, G);
-            else if (deep) hipLaunchKernelGGL((gemm_kernel<MODE_NN, 128, 2>), grid, dim3(NTHREADS), 0, stream, G);
-            else hipLaunchKernelGGL((gemm_kernel<MODE_NN, 128, 1>), grid, dim3(NTHREADS), 0, stream, G);
-        }
+    BSVI_LAUNCH(SKINNY_K4, skinny_k4_kernel, G, s.sbk, s.sbn, mode)
+    BSVI_LAUNCH(SKINNY_K, skinny_k_kernel, G, s.sbk, s.sbn, mode)
+#undef BSVI_LAUNCH
+    // (round 4, measured and removed: stream-K — a grid of the resident slots, equal runs of (128 x 128 tile, k step) units
+    //  per workgroup, a cut tile finished by the later workgroup in a fixed order.  cfg 5's layers at 25 600 rows: 136 /
+    //  117 / 94 / 179 us forward and 108 / 158 / 140 us input gradient against 126 / 81 / 84 / 125 and 89 / 93 / 118 here.
+    //  With K = 256 ... 784 a tile is 16 ... 49 steps: what these shapes pay for is the tile's prologue and its 64 scalar
+    //  stores per thread, which four co-resident 64-row workgroups hide from each other and three persistent 128-row ones
+    //  do not — not the uneven last round the shape count suggested.)
+#define BSVI_GEMM(KIND, MODE, TBM, PF) case sel::KIND: hipLaunchKernelGGL((gemm_kernel<MODE, TBM, PF>), grid, block, 0, stream, G); break;
+    BSVI_GEMM(GEMM_TN_64_PF1, MODE_TN, 64, 1) BSVI_GEMM(GEMM_TN_64_PF2, MODE_TN, 64, 2)
+    BSVI_GEMM(GEMM_NT_64_PF1, MODE_NT, 64, 1) BSVI_GEMM(GEMM_NT_64_PF2, MODE_NT, 64, 2)
+    BSVI_GEMM(GEMM_NT_128_PF1, MODE_NT, 128, 1) BSVI_GEMM(GEMM_NT_128_PF2, MODE_NT, 128, 2)
+    BSVI_GEMM(GEMM_NN_64_PF1, MODE_NN, 64, 1) BSVI_GEMM(GEMM_NN_64_PF2, MODE_NN, 64, 2)
+    BSVI_GEMM(GEMM_NN_128_PF1, MODE_NN, 128, 1) BSVI_GEMM(GEMM_NN_128_PF2, MODE_NN, 128, 2)
+#undef BSVI_GEMM
+    default: return bsvi_fail(BSVI_ERR_INVALID, "launch_gemm: not an f32 kind");
     }
     HIP_TRY(hipGetLastError());
     return BSVI_OK;
@@ -3000,17 +2900,22 @@ int bsvi_gemm_f32(int mode, const float* A, int lda, const float* B, int ldb, fl
     if ((mode != MODE_NT && mode != MODE_NN) || !A || !B || !C) return bsvi_fail(BSVI_ERR_INVALID, "bsvi_gemm_f32: bad arguments");
     GemmArgs G{};
     G.A = A; G.B = B; G.C = C; G.M = M; G.N = N; G.K = K; G.lda = lda; G.ldb = ldb; G.ldc = ldc;
-    return launch_gemm(mode, G, (hipStream_t)stream);
+    return launch_gemm(mode, G, read_switches(), (hipStream_t)stream);
 }
 
-extern "C" int bsvi_debug_gemm(int mode, const float* a_dev, const float* b_dev, float* c_dev, const int32_t* rows_dev,
-                               uint32_t m, uint32_t n, uint32_t k, uint32_t lda, uint32_t ldb, uint32_t ldc,
-                               const float* bias_or_y_dev, uint32_t ldy, uint32_t activation, float post_add,
-                               uint32_t accumulate, void* stream) {
+// bsvi_debug_gemm, and with `query` bsvi_debug_gemm_kind: the same arguments through the same code up to the launch (the hook's
+// buffers are grown, their alignment decides too), which is then left out and the selected kind returned
+static int debug_gemm(bool query, int mode, const float* a_dev, const float* b_dev, float* c_dev, const int32_t* rows_dev,
+                      uint32_t m, uint32_t n, uint32_t k, uint32_t lda, uint32_t ldb, uint32_t ldc,
+                      const float* bias_or_y_dev, uint32_t ldy, uint32_t activation, float post_add,
+                      uint32_t accumulate, void* stream) {
+    const sel::Switches sw = read_switches();
+    if (query && (mode == 4 || mode == 7 || mode == 8)) return bsvi_fail(BSVI_ERR_UNSUPPORTED, "modes 4, 7 and 8 have one kernel each");
     if (mode == 3) {
         // the exact-data forward product C = act(A[rows] B^T + bias) through xgemm_nt_kernel: A (whose values must be exact
         // in bf16 — not checked here) is converted, B split into its three pieces, in buffers the hook keeps
         if (!a_dev || !b_dev || !c_dev) return bsvi_fail(BSVI_ERR_INVALID, "bad gemm arguments");
+        if (query) return sel::select_xgemm((int)m, (int)n, sw).kind;
         const int Kp = ((int)k + XBK - 1) / XBK * XBK;
         uint32_t a_rows = m;                       // with a gather the caller passes the number of SOURCE rows in `accumulate`
         if (rows_dev) a_rows = accumulate;
@@ -3026,7 +2931,7 @@ extern "C" int bsvi_debug_gemm(int mode, const float* a_dev, const float* b_dev,
         XGemmArgs X{};
         X.X = xb; X.rows = rows_dev; X.Wp = wp; X.plane_stride = (long)n * Kp; X.C = c_dev; X.ldc = (int)ldc;
         X.M = (int)m; X.N = (int)n; X.Kp = Kp; X.bias = bias_or_y_dev; X.act = (int)activation; X.post_add = post_add;
-        launch_xgemm(X, st);
+        launch_xgemm(X, sw, st);
         HIP_TRY(hipGetLastError());
         return BSVI_OK;
     }
@@ -3087,13 +2992,14 @@ extern "C" int bsvi_debug_gemm(int mode, const float* a_dev, const float* b_dev,
         X6SplitTable T{};
         T.e[0] = {b_dev, wp, (int)n, (int)k, Kp, mode == 6 ? 1 : 0, 0u};
         T.n = 1;
-        hipLaunchKernelGGL(x6_split_kernel, dim3((unsigned)(((size_t)n * Kp + 255) / 256)), dim3(256), 0, st, T);
+        if (!query) hipLaunchKernelGGL(x6_split_kernel, dim3((unsigned)(((size_t)n * Kp + 255) / 256)), dim3(256), 0, st, T);
         X6Args X{};
         X.A = a_dev; X.lda = (int)lda; X.Bp = wp; X.Kp = Kp; X.plane_stride = (long)n * Kp;
         X.C = c_dev; X.ldc = (int)ldc; X.M = (int)m; X.N = (int)n; X.K = (int)k;
         X.act = (int)activation; X.post_add = post_add; X.accumulate = (int)accumulate;
         if (mode == 5) X.bias = bias_or_y_dev; else { X.Y = bias_or_y_dev; X.ldy = (int)ldy; }
-        return launch_x6(mode == 6, X, st);
+        const sel::Selection s = sel::select_x6(mode == 6, facts_of(X), false, sw);
+        return query ? (int)s.kind : launch_x6(s, X, st);
     }
     if (mode == 7) {
         // mode 2 (C[m][n] = sum_k A[k][m] B[k][n], column sums of A into bias_or_y_dev) through x6tn_kernel: six products of exact pieces,
@@ -3138,7 +3044,7 @@ extern "C" int bsvi_debug_gemm(int mode, const float* a_dev, const float* b_dev,
     G.act = (int)activation; G.post_add = post_add; G.accumulate = (int)accumulate;
     if (mode == MODE_NT) G.bias = bias_or_y_dev;
     if (mode == MODE_NN) { G.Y = bias_or_y_dev; G.ldy = (int)ldy; }
-    if (mode != MODE_TN) return launch_gemm(mode, G, (hipStream_t)stream);
+    if (mode != MODE_TN) return query ? (int)sel::select_f32(mode, facts_of(G), sw).kind : launch_gemm(mode, G, sw, (hipStream_t)stream);
     // the product path keeps the partials in its workspace; the hook borrows a buffer for them
     float* bias_acc = const_cast<float*>(bias_or_y_dev);   // [M] accumulator of the column sums of A, or NULL
     const TnPlan plan = tn_plan(G.M, G.N, G.K);
@@ -3154,7 +3060,8 @@ extern "C" int bsvi_debug_gemm(int mode, const float* a_dev, const float* b_dev,
     }
     G.C = part; G.ldc = G.N; G.part_stride = (long)G.M * G.N;
     G.bias_grad = bias_acc ? part + align4((size_t)plan.slices * G.M * G.N) : nullptr;
-    int rc = launch_gemm(mode, G, (hipStream_t)stream);
+    if (query) return sel::select_f32(mode, facts_of(G), sw).kind;
+    int rc = launch_gemm(mode, G, sw, (hipStream_t)stream);
     if (!rc) {
         SegmentTable T{};
         T.seg[0] = Segment{c_dev, part, m, n, ldc, (uint32_t)plan.slices, 0u, 1u, 0u, 0u};
@@ -3170,6 +3077,19 @@ extern "C" int bsvi_debug_gemm(int mode, const float* a_dev, const float* b_dev,
     }
     return rc;
 }
+extern "C" int bsvi_debug_gemm(int mode, const float* a_dev, const float* b_dev, float* c_dev, const int32_t* rows_dev,
+                               uint32_t m, uint32_t n, uint32_t k, uint32_t lda, uint32_t ldb, uint32_t ldc,
+                               const float* bias_or_y_dev, uint32_t ldy, uint32_t activation, float post_add,
+                               uint32_t accumulate, void* stream) {
+    return debug_gemm(false, mode, a_dev, b_dev, c_dev, rows_dev, m, n, k, lda, ldb, ldc, bias_or_y_dev, ldy, activation, post_add, accumulate, stream);
+}
+extern "C" int bsvi_debug_gemm_kind(int mode, const float* a_dev, const float* b_dev, float* c_dev, const int32_t* rows_dev,
+                                    uint32_t m, uint32_t n, uint32_t k, uint32_t lda, uint32_t ldb, uint32_t ldc,
+                                    const float* bias_or_y_dev, uint32_t ldy, uint32_t activation, float post_add,
+                                    uint32_t accumulate, void* stream) {
+    return debug_gemm(true, mode, a_dev, b_dev, c_dev, rows_dev, m, n, k, lda, ldb, ldc, bias_or_y_dev, ldy, activation, post_add, accumulate, stream);
+}
+extern "C" const char* bsvi_amort_kind_name(int kind) { return sel::name(kind); }
 
 extern "C" int bsvi_amort_fwd_bwd(const bsvi_amort* a, const bsvi_amort_args* args) {
     if (args) BSVI_CHECK_STRUCT(args, bsvi_amort_args);
@@ -3177,6 +3097,7 @@ extern "C" int bsvi_amort_fwd_bwd(const bsvi_amort* a, const bsvi_amort_args* ar
         return bsvi_fail(BSVI_ERR_INVALID, "null argument");
     if (args->estimator > 1) return bsvi_fail(BSVI_ERR_UNSUPPORTED, "estimator must be 0 (pathwise) or 1 (BlackBox)");
     hipStream_t stream = (hipStream_t)args->stream;
+    const sel::Switches sw = read_switches();
     const bsvi_amort_desc& d = a->d;
     const int B = (int)d.batch_size, Dz = (int)d.latent_dim, P = (int)d.n_features;
     const size_t R = (size_t)args->n_samples_local * B;
@@ -3270,7 +3191,7 @@ extern "C" int bsvi_amort_fwd_bwd(const bsvi_amort* a, const bsvi_amort_args* ar
     }
     // the pieces of the weights the matrix-core products read — the wide layers' in both orientations (x6gemm_kernel), the data
     // layer's (xgemm_nt_kernel) — ride in the launch that draws the minibatch rows, when they fit its table of eight
-    const bool x6_on = a->x6_any && R >= (size_t)kX6MinRows;
+    const bool x6_on = a->x6_any && sel::x6_rows(R);
     bool data_pieces_done = false;
     {
         std::vector<X6SplitTable::Entry> entries;
@@ -3324,15 +3245,15 @@ extern "C" int bsvi_amort_fwd_bwd(const bsvi_amort* a, const bsvi_amort_args* ar
 
     // (round 6) the Bernoulli likelihood fused into the epilogue of the product that makes the logits (x6_epilogue, LIK): when that product
     // is a six-piece forward product without an activation, the data has its exact bf16 copy and no caller weights scale the seeds.
-    // BSVI_AMORT_FUSE_LIK=0: the separate amort_lik launch (80 MB of logits out, in, and their gradient out again at config 5)
-    const bool fuse_lik_env = [] { const char* e = getenv("BSVI_AMORT_FUSE_LIK"); return !(e && e[0] == '0'); }();      // (read per call: tests switch it)
+    // BSVI_AMORT_FUSE_LIK=0: the separate amort_lik launch (80 MB of logits out, in, and their gradient out again at config 5).
+    // fuse_lik asks for it; lik_fused says that the kernel selected for that product is the one that does it (sel::select_x6)
     bool fuse_lik = false, lik_fused = false;
     float* lik_part = nullptr;
     {
         const int prod = a->dec.producer[d.dec_logits_value];
-        const int x6m = [] { const char* e = getenv("BSVI_X6_MODES"); return e ? atoi(e) : 1; }();
-        if (fuse_lik_env && prod >= 0 && d.likelihood == BSVI_AMORT_LIK_BINOMIAL1 && !args->f_weight_dev && a->data_exact && a->dataset_bf16_dev &&
-            x6_on && (x6m & 1) && (size_t)prod < a->x6[1].size() && a->x6[1][prod].nt && (P & 3) == 0 && (a->data_kp & 3) == 0) {
+        if (sw.fuse_lik && prod >= 0 && d.likelihood == BSVI_AMORT_LIK_BINOMIAL1 && !args->f_weight_dev && a->data_exact && a->dataset_bf16_dev &&
+            sel::forward_path(false, a->data_exact, false, x6_on, (size_t)prod < a->x6[1].size() && a->x6[1][prod].nt, sw) == sel::FWD_X6 &&
+            (P & 3) == 0 && (a->data_kp & 3) == 0) {
             const auto& pl = a->dec.layers[prod];
             const bool plain = pl.activation == BSVI_ACT_NONE && pl.post_add == 0.0f && !(pl.split_col > 0 && pl.split_col < pl.n_out) && (int)pl.n_out == P;
             if (plain) {
@@ -3348,7 +3269,10 @@ extern "C" int bsvi_amort_fwd_bwd(const bsvi_amort* a, const bsvi_amort_args* ar
             const auto& l = net.layers[li];
             GemmArgs G{};
             const bool from_data = gather && l.in_value == 0;
-            if (from_data && a->data_exact && li < a->weight_pieces.size() && a->weight_pieces[li]) {
+            const auto& x6 = a->x6[&net == &a->dec ? 1 : 0];
+            const sel::ForwardPath path = sel::forward_path(from_data, a->data_exact, li < a->weight_pieces.size() && a->weight_pieces[li], x6_on,
+                                                            li < x6.size() && x6[li].nt, sw);
+            if (path == sel::FWD_EXACT_DATA) {
                 // x W^T with x exact in bf16: three bf16 MFMAs per tile and step on the pieces of W (xgemm_nt_kernel)
                 const int Kp = a->data_kp;
                 uint16_t* pieces = a->weight_pieces[li];
@@ -3363,13 +3287,11 @@ extern "C" int bsvi_amort_fwd_bwd(const bsvi_amort* a, const bsvi_amort_args* ar
                 X.bias = l.bias_off != 0xFFFFFFFFu ? params + l.bias_off : nullptr;
                 X.act = (int)l.activation; X.post_add = l.post_add;
                 if (l.split_col > 0 && l.split_col < l.n_out) { X.split = (int)l.split_col; X.act2 = (int)l.activation2; X.post_add2 = l.post_add2; }
-                launch_xgemm(X, stream);
+                launch_xgemm(X, sw, stream);
                 HIP_TRY(hipGetLastError());
                 continue;
             }
-            const auto& x6 = a->x6[&net == &a->dec ? 1 : 0];
-            const int x6_modes = [] { const char* e = getenv("BSVI_X6_MODES"); return e ? atoi(e) : 1; }();      // (bit 0: forward, bit 1: input gradient — see backward; read per call: tests switch it)
-            if (x6_on && (x6_modes & 1) && !from_data && li < x6.size() && x6[li].nt) {
+            if (path == sel::FWD_X6) {
                 X6Args X{};
                 X.A = val(net, l.in_value); X.lda = net.ld[l.in_value];
                 X.Bp = x6[li].nt; X.Kp = x6[li].kp_nt; X.plane_stride = (long)l.n_out * X.Kp;
@@ -3378,13 +3300,14 @@ extern "C" int bsvi_amort_fwd_bwd(const bsvi_amort* a, const bsvi_amort_args* ar
                 X.bias = l.bias_off != 0xFFFFFFFFu ? params + l.bias_off : nullptr;
                 X.act = (int)l.activation; X.post_add = l.post_add;
                 if (l.split_col > 0 && l.split_col < l.n_out) { X.split = (int)l.split_col; X.act2 = (int)l.activation2; X.post_add2 = l.post_add2; }
-                if (fuse_lik && &net == &a->dec && l.out_value == d.dec_logits_value) {
+                const sel::Selection s = sel::select_x6(false, facts_of(X), fuse_lik && &net == &a->dec && l.out_value == d.dec_logits_value, sw);
+                if (s.lik) {
                     // the Bernoulli likelihood in this product's epilogue: d f / d logits where the logits would have gone (the buffers are
                     // one: the logits are overwritten by their own gradient), one partial log-likelihood per (row, column tile)
                     X.lik_x = a->dataset_bf16_dev; X.lik_kp = a->data_kp; X.lik_idx = idx; X.lik_part = lik_part;
                     lik_fused = true;
                 }
-                if (int rc = launch_x6(false, X, stream)) return rc;
+                if (int rc = launch_x6(s, X, stream)) return rc;
                 continue;
             }
             G.A = from_data ? a->dataset_dev : val(net, l.in_value);
@@ -3396,17 +3319,14 @@ extern "C" int bsvi_amort_fwd_bwd(const bsvi_amort* a, const bsvi_amort_args* ar
             G.bias = l.bias_off != 0xFFFFFFFFu ? params + l.bias_off : nullptr;
             G.act = (int)l.activation; G.post_add = l.post_add;
             if (l.split_col > 0 && l.split_col < l.n_out) { G.split = (int)l.split_col; G.act2 = (int)l.activation2; G.post_add2 = l.post_add2; }
-            int rc = launch_gemm(MODE_NT, G, stream);
+            int rc = launch_gemm(MODE_NT, G, sw, stream);
             if (rc) return rc;
         }
         return BSVI_OK;
     };
     size_t next_event = 0;
     // (round 5) the data layer's weight gradient through x6tn_kernel<., true>: no transposed minibatch rows, no pieces of dY in memory.  BSVI_X6_TN_DATA=0: round 4's three launches
-    static const bool data_x6tn_env = [] { const char* e = getenv("BSVI_X6_TN_DATA"); return !(e && e[0] == '0'); }();
-    static const bool x6_tn_env = [] { const char* e = getenv("BSVI_X6_TN"); return !(e && e[0] == '0'); }();
-    const bool data_x6tn = x6_on && x6_tn_env && data_x6tn_env;
-    bool xt_pending = XT != nullptr && !data_x6tn, xt_on_side = false;
+    bool xt_pending = XT != nullptr && !sel::data_x6tn(x6_on, sw), xt_on_side = false;
     auto launch_xt = [&](hipStream_t ts) {
         hipLaunchKernelGGL(xt_gather_kernel, dim3((unsigned)(Rp / 64), (unsigned)((P + 127) / 128)), dim3(256), 0, ts,
                            a->dataset_bf16_dev, idx, a->data_kp, P, (int)R, Rp, XT);
@@ -3437,7 +3357,8 @@ extern "C" int bsvi_amort_fwd_bwd(const bsvi_amort* a, const bsvi_amort_args* ar
             const float* dY = grad(net, l.out_value);
             const int ldy = net.ld[l.out_value];
             const bool from_data = gather && l.in_value == 0;
-            if (from_data && XT && xdw_layer(a, (size_t)i, R) && data_x6tn) {
+            const sel::WeightGradPath wpath = sel::weight_grad_path(from_data, XT && xdw_layer(a, (size_t)i, R), x6_on, (int)l.n_out, (int)l.n_in, sw);
+            if (wpath == sel::WG_X6TN_DATA) {
                 // (round 5) the same product through x6tn_kernel: dY split and transposed on the way into LDS, the data rows gathered by
                 // the kernel and converted (they are exactly bf16: one piece, three products) — no transposed copies in memory, one launch
                 // in place of xt_gather + dy_split_t + the exact-piece product
@@ -3455,8 +3376,7 @@ extern "C" int bsvi_amort_fwd_bwd(const bsvi_amort* a, const bsvi_amort_args* ar
                 int rc = add_segment(grads + l.weight_off, cpart, l.n_out, l.n_in, (uint32_t)xp.slices);
                 if (!rc && has_bias) rc = add_segment(grads + l.bias_off, bpart, 1, l.n_out, (uint32_t)xp.slices);
                 if (rc) return rc;
-            } else
-            if (from_data && XT && xdw_layer(a, (size_t)i, R)) {
+            } else if (wpath == sel::WG_XDW) {
                 // dW = dY^T x with x exact in bf16: the pieces of dY, transposed, times the transposed rows (split-k)
                 const XdwPlan plan = xdw_plan((int)l.n_in, (int)l.n_out, R);
                 const bool has_bias = l.bias_off != 0xFFFFFFFFu;
@@ -3478,8 +3398,7 @@ extern "C" int bsvi_amort_fwd_bwd(const bsvi_amort* a, const bsvi_amort_args* ar
                 int rc = add_segment(grads + l.weight_off, slices, l.n_out, l.n_in, (uint32_t)plan.slices);
                 if (!rc && has_bias) rc = add_segment(grads + l.bias_off, colsum, 1, l.n_out, (uint32_t)(Rp / 64));
                 if (rc) return rc;
-            } else
-            {   // dW[n_out][n_in] = dY^T x, db = 1^T dY (same launch): one partial per slice of the rows
+            } else {   // dW[n_out][n_in] = dY^T x, db = 1^T dY (same launch): one partial per slice of the rows
                 GemmArgs G{};
                 G.A = dY; G.lda = ldy;
                 G.B = from_data ? a->dataset_dev : val(net, l.in_value);
@@ -3494,8 +3413,7 @@ extern "C" int bsvi_amort_fwd_bwd(const bsvi_amort* a, const bsvi_amort_args* ar
                 if (has_bias) part += align4((size_t)plan.slices * G.M);
                 // wide layers whose input is a network value: six products of exact pieces with the transposing split of both operands
                 // on the way into LDS (x6tn_kernel; round 5) — 6 / 16 of the f32-input MFMA's pipe time.  BSVI_X6_TN=0: the f32-input kernel
-                static const bool x6_tn = [] { const char* e = getenv("BSVI_X6_TN"); return !(e && e[0] == '0'); }();
-                if (x6_on && x6_tn && !from_data && !plan.skinny && G.M >= 64 && G.N >= 64) {
+                if (wpath == sel::WG_X6TN) {
                     const X6TnPlan xp = x6tn_plan(G.M, G.N, G.K);
                     // (the partial regions were laid out for the larger of the two plans: tn_partial_floats)
                     float* const cpart = G.C;
@@ -3511,7 +3429,7 @@ extern "C" int bsvi_amort_fwd_bwd(const bsvi_amort* a, const bsvi_amort_args* ar
                     if (!rc && has_bias) rc = add_segment(grads + l.bias_off, bpart, 1, l.n_out, (uint32_t)xp.slices);
                     if (rc) return rc;
                 } else {
-                int rc = launch_gemm(MODE_TN, G, wstream);
+                int rc = launch_gemm(MODE_TN, G, sw, wstream);
                 if (!rc) rc = add_segment(grads + l.weight_off, G.C, l.n_out, l.n_in, (uint32_t)plan.slices);
                 if (!rc && has_bias) rc = add_segment(grads + l.bias_off, G.bias_grad, 1, l.n_out, (uint32_t)plan.slices);
                 if (rc) return rc;
@@ -3542,19 +3460,17 @@ extern "C" int bsvi_amort_fwd_bwd(const bsvi_amort* a, const bsvi_amort_args* ar
                 // (What trying them in round 4 found is why this file is compiled without packed-f32 instructions — Makefile: with
                 //  x6gemm_kernel<true> on this stream the narrow layers' outer_kernel on the other one returned ~50 of 1024 values different
                 //  from call to call, lanes 48-63, beside EVERY bf16-MFMA kernel: tools/r4/coresidency_probe.py, profiles/r4/x6_notes.txt 4.)
-                const int x6_modes = [&] { const char* e = getenv("BSVI_X6_MODES"); return e ? atoi(e) : 3; }();
-                static const int x6_only = [] { const char* e = getenv("BSVI_X6_NN_ONLY"); return e ? atoi(e) : -1; }();     // (diagnostics: 10 * net + layer)
-                if (x6_on && (x6_modes & 2) && (size_t)i < x6.size() && x6[i].nn && (x6_only < 0 || x6_only == 10 * (&net == &a->dec ? 1 : 0) + i)) {
+                if (sel::input_grad_path(x6_on, (size_t)i < x6.size() && x6[i].nn, 10 * (&net == &a->dec ? 1 : 0) + i, sw) == sel::IG_X6) {
                     X6Args X{};
                     X.A = dY; X.lda = ldy;
                     X.Bp = x6[i].nn; X.Kp = x6[i].kp_nn; X.plane_stride = (long)l.n_in * X.Kp;
                     X.C = G.C; X.ldc = G.ldc; X.M = G.M; X.N = G.N; X.K = G.K;
                     X.Y = G.Y; X.ldy = G.ldy; X.act = G.act; X.post_add = G.post_add;
                     X.split = G.split; X.act2 = G.act2; X.post_add2 = G.post_add2; X.accumulate = G.accumulate;
-                    if (int rc = launch_x6(true, X, stream)) return rc;
+                    if (int rc = launch_x6(true, X, sw, stream)) return rc;
                     continue;
                 }
-                int rc = launch_gemm(MODE_NN, G, stream);
+                int rc = launch_gemm(MODE_NN, G, sw, stream);
                 if (rc) return rc;
             }
         }
@@ -3661,6 +3577,7 @@ extern "C" int bsvi_amort_apply(const bsvi_amort* a, int network, const float* p
     const Net& net = network == 0 ? a->enc : a->dec;
     if (value == 0 || value >= net.width.size()) return bsvi_fail(BSVI_ERR_INVALID, "no such network value");
     hipStream_t stream = (hipStream_t)stream_;
+    const sel::Switches sw = read_switches();
     const size_t R = n_rows;
     if (R * a->floats_per_row > bsvi_amort_workspace_bytes(a, (n_rows + a->d.batch_size - 1) / a->d.batch_size) / sizeof(float))
         return bsvi_fail(BSVI_ERR_INVALID, "workspace too small for this many rows");
@@ -3684,7 +3601,7 @@ extern "C" int bsvi_amort_apply(const bsvi_amort* a, int network, const float* p
         G.bias = l.bias_off != 0xFFFFFFFFu ? params_dev + l.bias_off : nullptr;
         G.act = (int)l.activation; G.post_add = l.post_add;
         if (l.split_col > 0 && l.split_col < l.n_out) { G.split = (int)l.split_col; G.act2 = (int)l.activation2; G.post_add2 = l.post_add2; }
-        int rc = launch_gemm(MODE_NT, G, stream);
+        int rc = launch_gemm(MODE_NT, G, sw, stream);
         if (rc) return rc;
     }
     const long total = (long)R * net.width[value];

@@ -255,6 +255,10 @@ EXPORTS.update({
     "bsvi_debug_gemm": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                   C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
                                   C.c_float, C.c_uint32, C.c_void_p]),
+    "bsvi_debug_gemm_kind": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                       C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
+                                       C.c_float, C.c_uint32, C.c_void_p]),
+    "bsvi_amort_kind_name": (C.c_char_p, [C.c_int]),
 })
 
 EXPORTS.update({

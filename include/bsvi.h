@@ -810,6 +810,14 @@ int bsvi_debug_gemm(int mode, const float* a_dev, const float* b_dev, float* c_d
                     uint32_t m, uint32_t n, uint32_t k, uint32_t lda, uint32_t ldb, uint32_t ldc,
                     const float* bias_or_y_dev, uint32_t ldy, uint32_t activation, float post_add,
                     uint32_t accumulate, void* stream);
+/* Which kernel that call would launch for its product, without launching it: bsvi_debug_gemm's own arguments (the pointers too:
+ * their alignment decides), modes 0, 1, 2, 3, 5 and 6.  Returns a kind of brancher_amd/csrc/amort_select.h (>= 0; its name:
+ * bsvi_amort_kind_name) or an error code (< 0). */
+int bsvi_debug_gemm_kind(int mode, const float* a_dev, const float* b_dev, float* c_dev, const int32_t* rows_dev,
+                         uint32_t m, uint32_t n, uint32_t k, uint32_t lda, uint32_t ldb, uint32_t ldc,
+                         const float* bias_or_y_dev, uint32_t ldy, uint32_t activation, float post_add,
+                         uint32_t accumulate, void* stream);
+const char* bsvi_amort_kind_name(int kind);
 
 /* Test hook, not used by the product path: evaluates one special function (fn 0 digamma,
  * 1 trigamma, 2 dirichlet_grad_one(x, alpha=p0, total=p1), 6 lgamma) or one node function of

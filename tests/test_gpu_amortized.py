@@ -872,3 +872,127 @@ def test_the_fused_likelihood_epilogue_equals_the_separate_launch():
         assert not torch.equal(f1, f0)                                  # (another launch sequence: another summation order)
         assert float((f1 - f0).abs().max()) <= 2e-6 * float(f0.abs().max())
         assert float((g1 - g0).abs().max()) <= 2e-5 * float(g0.abs().max())
+
+
+# ---- every kernel the three launchers choose from, where bsvi_debug_gemm reaches it with the default switches -------------------
+# (id, mode, M, N, K, lda, ldb, ldc, ldy, kind): the rows of tests/c_abi/amort_select_table.cpp, which works each kind out by hand
+# (tests/test_amort_select_cpu.py compares the two lists)
+AMORT_KIND_ROWS = [
+    ("outer4", 2, 3, 260, 130, 4, 260, 260, 0, "outer<4>"),
+    ("outer8", 2, 260, 6, 130, 260, 8, 6, 0, "outer<8>"),
+    ("skinny_tn", 2, 257, 3, 130, 257, 3, 3, 0, "skinny_tn"),
+    ("gemm_tn", 2, 70, 50, 300, 70, 50, 50, 0, "gemm<tn,64,2>"),
+    ("rowdot2", 0, 70, 2, 12, 12, 12, 2, 0, "rowdot<2>"),
+    ("rowdot4", 0, 70, 3, 12, 12, 12, 3, 0, "rowdot<4>"),
+    ("rowdot8", 1, 70, 7, 12, 12, 7, 7, 7, "rowdot<8>"),
+    ("skinny_n", 0, 70, 5, 13, 13, 13, 5, 0, "skinny_n"),
+    ("skinny_k4nt1", 0, 257, 12, 1, 1, 1, 12, 0, "skinny_k4nt<1>"),
+    ("skinny_k4nt3", 0, 257, 12, 3, 3, 3, 12, 0, "skinny_k4nt<3>"),
+    ("skinny_k4nt8", 0, 257, 12, 8, 8, 8, 16, 0, "skinny_k4nt<8>"),
+    ("skinny_k4", 1, 257, 12, 5, 5, 12, 12, 12, "skinny_k4"),
+    ("skinny_k", 0, 257, 12, 2, 2, 2, 15, 0, "skinny_k"),
+    ("gemm_nt64", 0, 300, 70, 50, 50, 50, 73, 0, "gemm<nt,64,2>"),
+    ("gemm_nt128", 0, 50, 20, 18, 18, 18, 23, 0, "gemm<nt,128,2>"),
+    ("gemm_nn64", 1, 300, 70, 50, 50, 70, 70, 70, "gemm<nn,64,2>"),
+    ("gemm_nn128", 1, 50, 20, 18, 18, 20, 20, 20, "gemm<nn,128,2>"),
+    ("x6_nt", 5, 300, 72, 100, 100, 100, 76, 0, "x6<nt,var1>"),
+    ("x6_nn", 6, 300, 72, 100, 100, 72, 72, 72, "x6<nn,var1>"),
+    ("x6_r5_nt", 5, 256, 130, 64, 64, 64, 134, 0, "x6_r5<nt>"),
+    ("x6_r5_nn", 6, 256, 130, 64, 64, 130, 130, 130, "x6_r5<nn>"),
+    ("xgemm", 3, 300, 70, 50, 50, 50, 73, 0, "xgemm_glds<128>"),
+]
+
+
+@pytest.mark.parametrize("row", AMORT_KIND_ROWS, ids=[r[0] for r in AMORT_KIND_ROWS])
+def test_every_kind_the_launchers_select_runs_and_matches_torch(row):
+    """One row per kernel that launch_gemm, launch_x6 and launch_xgemm choose from with the default switches, at a small shape with
+    tails (rows that are no multiple of the row block, gathered rows where the mode takes them, accumulation on the input-gradient
+    forms): bsvi_debug_gemm_kind first says that the call launches the kind the row claims, then the product is compared with torch in
+    double precision — the f32-input kernels to 2e-6 of the largest output, the six-piece and exact-data kernels to twice the error
+    of torch's own f32 product (or 2e-6), the bounds of the tests above.  The kinds behind a switch that is read once per process
+    (BSVI_GEMM_PF's depth 1, BSVI_XGEMM_TALL / BSVI_XGEMM_GLDS=0, the BSVI_X6_DEBUG forms, BSVI_X6_VAR=0) and the fused likelihood's
+    (reached by the network tests) stay with the table, tests/c_abi/amort_select_table.cpp."""
+    from brancher_amd import native
+    lib = native.load()
+    dev = torch.device("cuda:0")
+    _, mode, M, N, K, lda, ldb, ldc, ldy, kind = row
+    g = torch.Generator(device="cpu").manual_seed(M + 3 * N + 7 * K + mode)
+    rnd = lambda *s: torch.randn(*s, generator=g).to(dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    yard = None
+    if mode in (0, 5):        # C = relu(A[rows] B^T + bias) + 0.1 (mode 5: no gather, no activation)
+        src = rnd(M + 5, lda)
+        rows = torch.randint(0, M + 5, (M,), generator=g).to(torch.int32).to(dev) if mode == 0 else None
+        Bm, bias = rnd(N, ldb), rnd(N)
+        Cm = torch.full((M, ldc), 7.0, device=dev)
+        args = (mode, ptr(src), ptr(Bm), ptr(Cm), ptr(rows), M, N, K, lda, ldb, ldc, ptr(bias), 0, 1 if mode == 0 else 0, 0.1 if mode == 0 else 0.0, 0, None)
+        Ag = src[rows.long()] if mode == 0 else src[:M]
+        ref = Ag[:, :K].double() @ Bm[:, :K].double().T + bias.double()
+        if mode == 0:
+            ref = torch.relu(ref) + 0.1
+        else:
+            yard = Ag[:, :K] @ Bm[:, :K].T + bias
+    elif mode in (1, 6):      # C += (A B) * relu'(Y)
+        A, Bm, Y, C0 = rnd(M, lda), rnd(K, ldb), rnd(M, ldy), rnd(M, ldc)
+        Cm = C0.clone()
+        args = (mode, ptr(A), ptr(Bm), ptr(Cm), None, M, N, K, lda, ldb, ldc, ptr(Y), ldy, 1, 0.0, 1, None)
+        ref = C0[:, :N].double() + (A[:, :K].double() @ Bm[:, :N].double()) * (Y[:, :N] > 0).double()
+        if mode == 6:
+            yard = C0[:, :N] + (A[:, :K] @ Bm[:, :N]) * (Y[:, :N] > 0).float()
+    elif mode == 2:           # C = A^T B[rows], the column sums of A beside it
+        A, src = rnd(K, lda), rnd(K + 3, ldb)
+        rows = torch.randint(0, K + 3, (K,), generator=g).to(torch.int32).to(dev)
+        Cm, colsum = torch.zeros(M, ldc, device=dev), torch.zeros(M, device=dev)
+        args = (mode, ptr(A), ptr(src), ptr(Cm), ptr(rows), M, N, K, lda, ldb, ldc, ptr(colsum), 0, 0, 0.0, 0, None)
+        ref = A[:, :M].double().T @ src[rows.long()][:, :N].double()
+    else:                     # mode 3: C = relu(X[rows] B^T + bias), X exactly bf16 (pixel counts)
+        n_src = M // 2 + 7
+        src = torch.randint(0, 256, (n_src, K), generator=g).float().to(dev)
+        rows = torch.randint(0, n_src, (M,), generator=g).to(torch.int32).to(dev)
+        Bm, bias = (torch.randn(N, K, generator=g) / 64).to(dev), rnd(N)
+        Cm = torch.full((M, ldc), 7.0, device=dev)
+        args = (mode, ptr(src), ptr(Bm), ptr(Cm), ptr(rows), M, N, K, lda, ldb, ldc, ptr(bias), 0, 1, 0.0, n_src, None)
+        ref = torch.relu(src[rows.long()].double() @ Bm.double().T + bias.double())
+        yard = torch.relu(src[rows.long()] @ Bm.T + bias)
+    got_kind = lib.bsvi_debug_gemm_kind(*args)
+    assert got_kind >= 0, native.check(got_kind)
+    assert lib.bsvi_amort_kind_name(got_kind).decode() == kind
+    native.check(lib.bsvi_debug_gemm(*args))
+    torch.cuda.synchronize()
+    if mode in (0, 3, 5):
+        assert torch.all(Cm[:, N:] == 7.0)
+    scale = ref.abs().max().item() + 1e-12
+    err = (Cm[:, :N].double() - ref).abs().max().item() / scale
+    bound = 2e-6 if yard is None else max(2.0 * (yard.double() - ref).abs().max().item() / scale, 2e-6)
+    print("%s: error %.3g of the largest output, bound %.3g" % (kind, err, bound))
+    assert err < 2e-6 if yard is None else err <= bound, (err, bound)
+    if mode == 2:
+        cs = A[:, :M].double().sum(0)
+        assert ((colsum.double() - cs).abs().max() / cs.abs().max()).item() < 2e-6
+
+
+def test_a_product_that_falls_back_from_the_fused_kernel_launches_the_likelihood(monkeypatch):
+    """The fused likelihood follows the kernel that sel::select_x6 chooses, not the wish alone.  BSVI_X6_V=5 sends every six-piece
+    product to round 5's register-staged kernel, which has no likelihood epilogue: with BSVI_AMORT_FUSE_LIK unset the forward pass
+    must then launch amort_lik exactly as with BSVI_AMORT_FUSE_LIK=0 — the same launch sequence, so the same bits in the output
+    vector and in every row's f, finite and identical call to call; both estimators.  (Before the selection answered `lik`, the unset
+    case skipped amort_lik, read partial log-likelihoods nobody had written and took the raw logits for their gradient.)"""
+    from brancher_amd import engine, workloads as W
+    kw = dict(dataset_size=300, batch_size=64, n_features=784, latent_size=2, hidden1=512, hidden2=256, seed=3)
+    monkeypatch.setenv("BSVI_X6_V", "5")
+    for estimator in ("pathwise", "blackbox"):
+        out = {}
+        for fused in (None, "0"):
+            if fused is None:
+                monkeypatch.delenv("BSVI_AMORT_FUSE_LIK", raising=False)
+            else:
+                monkeypatch.setenv("BSVI_AMORT_FUSE_LIK", fused)
+            c = engine.compile_model(W.build_vae(W.native_api(), **kw), None, estimator)
+            assert c.data_path() == "bf16x3"
+            a = c.evaluate(8, seed=4, offset=2, want_fvalues=True)
+            first, fa = c.out.clone(), a["f"].clone()
+            b = c.evaluate(8, seed=4, offset=2, want_fvalues=True)
+            assert torch.equal(c.out, first) and torch.equal(b["f"], fa)
+            assert bool(torch.isfinite(fa).all()) and bool(torch.isfinite(first).all())
+            out[fused] = (first, fa)
+        assert torch.equal(out[None][0], out["0"][0]) and torch.equal(out[None][1], out["0"][1])
