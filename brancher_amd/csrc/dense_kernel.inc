@@ -26,6 +26,9 @@
 //   dense_epilogue   sum over samples of f, non-finite count, gradients of shared uniform entries
 //   dense_param_kernel  chain rule to theta, finalize, optimizer step
 
+#include "dense_select.h"
+namespace dsel = bsvi_dense_select;      // the tile constants, the launch plan and the workspace layout
+
 namespace bsvi {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -1133,7 +1136,7 @@ __global__ void __launch_bounds__(256) dense_ce(const DParams D) {
 // d f / d s, d f / d mu (likelihood parts) and the row sums of eps, eps^2 from GT[p][(n, c)]: one workgroup per feature
 // quad; thread (sample lane, class) redraws the quad's normals of its samples (the counters dense_wsplit used), reads
 // the four rows of GT along (n, c) and keeps sixteen sums; the sample lanes of a class are joined in lane order.
-constexpr uint32_t kXGroups = 4;     // sample groups of dense_xreduce (dense_rows adds them in order)
+using dsel::kXGroups;       // sample groups of dense_xreduce (dense_rows adds them in order)
 __global__ void __launch_bounds__(256) dense_xreduce(const DParams D) {
     __shared__ float red[16][256];
     const uint32_t tid = threadIdx.x, p = (blockIdx.x / kXGroups) * 4, grp = blockIdx.x % kXGroups;
@@ -1179,6 +1182,8 @@ __global__ void __launch_bounds__(256) dense_xreduce(const DParams D) {
 #include "dense_xfused.inc"
 
 // ---- host side -------------------------------------------------------------------------------
+// Which launches an iteration makes, their grids, LDS and derived arguments, and the workspace: dense_select.h.  Here: the environment
+// (dense_read_switches), the device (bsvi_dense_create) and ONE loop over the plan's launches (dense_iterate).
 struct bsvi_dense {
     bsvi_dense_desc d;
     void* dev_blob = nullptr;
@@ -1188,14 +1193,41 @@ struct bsvi_dense {
     const uint32_t* pu_idx = nullptr;
     const float* dataset = nullptr;
     const float* labels = nullptr;
-    uint32_t P_pad = 0, B_pad = 0, R = 0;
-    bool xpath = false;      // every dataset value is exactly a bf16 number: both products on the bf16 matrix cores (DParams)
-    bool xb9 = false;        // dense_xbwd with feature tiles of nine 16-row blocks (they fit LDS) instead of seven
-    bool fold = true;        // the sample sums inside the parameter kernel when the call allows (BSVI_DENSE_FOLD=0: dense_epilogue as a launch)
-    bool xfused = false;     // ... as the two fused launches of dense_xfused.inc (BSVI_DENSE_FUSED=0: the round-3 sequence of six)
-    uint32_t Kp = 0;
-    uint32_t n_cu = 256;
+    dsel::Switches sw;       // the environment as bsvi_dense_create found it
+    dsel::Model m;           // the shape, the estimator, and what the device granted
+    dsel::ModelPlan mp;      // the path and its paddings
 };
+
+// the one place of the dense-link path that looks at the environment
+static dsel::Switches dense_read_switches() {
+    auto on = [](const char* knob) { const char* e = getenv(knob); return !(e && e[0] == '0'); };
+    auto digit = [](const char* knob, int mask) { const char* e = getenv(knob); return e ? (e[0] - '0') & mask : 0; };
+    auto number = [](const char* knob) { const char* e = getenv(knob); return e ? atoi(e) : 0; };
+    dsel::Switches sw;
+    sw.xgemm = on("BSVI_DENSE_XGEMM");
+    sw.fused = on("BSVI_DENSE_FUSED");
+    sw.fold = on("BSVI_DENSE_FOLD");
+    sw.xf_ns = (uint32_t)number("BSVI_XF_NS");
+    sw.xf_debug = digit("BSVI_XF_DEBUG", 7);
+    sw.xb_debug = digit("BSVI_XB_DEBUG", 3);
+    sw.xb_rb = number("BSVI_XB_RB");
+    sw.xb_groups = (uint32_t)number("BSVI_XB_GROUPS");
+    return sw;
+}
+
+// the templated families, by dsel::Kind minus the family's first: create raises their LDS attribute and dense_iterate launches through
+// the same tables
+typedef void (*dense_plain_fn)(const DParams);
+typedef void (*dense_xfwd_fn)(const DParams, const uint32_t);
+typedef void (*dense_xbwd_fn)(const DParams, const uint32_t, const uint32_t, const uint32_t, const uint32_t);
+static const dense_plain_fn kDenseForward[] = {dense_forward<1>, dense_forward<4>, dense_forward<10>, dense_forward<16>};
+static const dense_xfwd_fn kDenseXfwd[] = {dense_xfwd<0, 1>, dense_xfwd<0, 2>, dense_xfwd<1, 2>, dense_xfwd<2, 2>, dense_xfwd<3, 2>, dense_xfwd<4, 2>,
+                                           dense_xfwd<5, 2>, dense_xfwd<6, 2>, dense_xfwd<0, 1, true>, dense_xfwd<0, 2, true>};
+static const dense_xbwd_fn kDenseXbwd[] = {dense_xbwd<0, 2, 7>, dense_xbwd<0, 4, 7>, dense_xbwd<1, 4, 7>, dense_xbwd<2, 4, 7>, dense_xbwd<3, 4, 7>,
+                                           dense_xbwd<0, 4, 9>, dense_xbwd<0, 2, 7, true>, dense_xbwd<0, 4, 7, true>, dense_xbwd<0, 4, 9, true>};
+static_assert(sizeof(kDenseForward) / sizeof(kDenseForward[0]) == dsel::FORWARD_COUNT && sizeof(kDenseXfwd) / sizeof(kDenseXfwd[0]) == dsel::XFWD_COUNT &&
+              sizeof(kDenseXbwd) / sizeof(kDenseXbwd[0]) == dsel::XBWD_COUNT, "one entry per kind of dense_select.h, in its order");
+static bool dense_is_xfwd(int kind) { return kind >= dsel::XFWD_FIRST && kind < dsel::XFWD_FIRST + dsel::XFWD_COUNT; }
 
 extern "C" int bsvi_dense_create(const bsvi_dense_desc* desc, bsvi_dense** out) {
     if (!desc || !out) return fail(BSVI_ERR_INVALID, "null argument");
@@ -1223,9 +1255,6 @@ extern "C" int bsvi_dense_create(const bsvi_dense_desc* desc, bsvi_dense** out) 
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(BSVI_ERR_NO_DEVICE, "no HIP device visible");
     bsvi_dense* p = new bsvi_dense();
     p->d = *desc;
-    p->R = (uint32_t)R;
-    p->P_pad = (desc->n_features + 63) / 64 * 64;
-    p->B_pad = (desc->batch_size + 63) / 64 * 64;
     const size_t b_uni = align_up((size_t)desc->n_uniform * sizeof(bsvi_uniform_entry), 256);
     const size_t b_con = align_up((size_t)desc->n_consts * 4, 256);
     const size_t b_ptr = align_up(((size_t)desc->n_params + 1) * 4, 256);
@@ -1252,53 +1281,31 @@ extern "C" int bsvi_dense_create(const bsvi_dense_desc* desc, bsvi_dense** out) 
     p->pu_idx = (const uint32_t*)(base + o_idx);
     p->dataset = (const float*)(base + o_dat);
     p->labels = (const float*)(base + o_lab);
-    {   // the exact-data path: all dataset values exactly bf16, features in whole Philox quads; BSVI_DENSE_XGEMM=0 forces the f32 kernels
-        const char* xe = getenv("BSVI_DENSE_XGEMM");
-        bool exact = !(xe && xe[0] == '0') && desc->n_features % 4 == 0 && desc->n_features >= 32;
+    p->sw = dense_read_switches();
+    dsel::Model& m = p->m;
+    m.C = desc->n_classes; m.P = desc->n_features; m.B = desc->batch_size; m.DS = desc->dataset_size;
+    m.n_params = desc->n_params; m.n_uniform_grad = desc->n_uniform_grad;
+    m.blackbox = desc->estimator == BSVI_EST_BLACKBOX; m.entropy_weight = desc->entropy_weight;
+    for (int i = 0; i < 4; ++i) { m.base[i] = bases[i]; m.stride[i] = strides[i]; }
+    if (dsel::wants_exact_scan(m, p->sw)) {      // the exact-data path: all dataset values exactly bf16
         const uint32_t* bits = reinterpret_cast<const uint32_t*>(desc->dataset);
         const size_t n_values = (size_t)desc->dataset_size * desc->n_features;
-        for (size_t i = 0; exact && i < n_values; ++i) exact = (bits[i] & 0xFFFFu) == 0u;
-        p->xpath = exact;
-        p->Kp = (desc->n_features + 31) / 32 * 32;
-        if (exact) {
-            p->B_pad = (desc->batch_size + 127) / 128 * 128;        // dense_xbwd walks the minibatch axis in steps of 128
-            const char* fe = getenv("BSVI_DENSE_FUSED");
-            const char* fo = getenv("BSVI_DENSE_FOLD");
-            p->fold = !(fo && fo[0] == '0');
-            p->xfused = !(fe && fe[0] == '0') && (size_t)XF_MT * (p->B_pad * 2 + 32) <= 150u * 1024u;
-            p->xb9 = (size_t)XF_MT9 * (p->B_pad * 2 + 32) <= 150u * 1024u && p->B_pad % 256u == 0u;      // (+ per launch: the dlog pieces below 4 GB, dense_launch_exact)
-            int dev = 0, n_cu = 0;
-            if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n_cu > 0)
-                p->n_cu = (uint32_t)n_cu;
-            if (p->xfused) {
-                const int lds_b = (int)(XF_MT * (p->B_pad * 2 + 32)), lds_b9 = (int)(XF_MT9 * (p->B_pad * 2 + 32));
-                const void* fk[6] = {(const void*)dense_xfwd<0, 1>, (const void*)dense_xfwd<0, 2>, (const void*)dense_xfwd<1, 2>, (const void*)dense_xfwd<2, 2>,
-                                     (const void*)dense_xfwd<0, 1, true>, (const void*)dense_xfwd<0, 2, true>};
-                const void* bk[6] = {(const void*)dense_xbwd<0, 4, 7>, (const void*)dense_xbwd<1, 4, 7>, (const void*)dense_xbwd<2, 4, 7>, (const void*)dense_xbwd<3, 4, 7>,
-                                     (const void*)dense_xbwd<0, 2, 7>, (const void*)dense_xbwd<0, 2, 7>};
-                for (int i = 0; i < 6 && p->xfused; ++i)
-                    if (hipFuncSetAttribute(fk[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)XF_FWD_LDS) != hipSuccess ||
-                        hipFuncSetAttribute(bk[i], hipFuncAttributeMaxDynamicSharedMemorySize, lds_b) != hipSuccess) {
-                        (void)hipGetLastError();
-                        p->xfused = false;
-                    }
-                {   // (profiling variants, BSVI_XF_DEBUG=3..5)
-                    const void* dk[4] = {(const void*)dense_xfwd<3, 2>, (const void*)dense_xfwd<4, 2>, (const void*)dense_xfwd<5, 2>, (const void*)dense_xfwd<6, 2>};
-                    for (int i = 0; i < 4; ++i) if (hipFuncSetAttribute(dk[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)XF_FWD_LDS) != hipSuccess) (void)hipGetLastError();
-                }
-                if (p->xfused && (hipFuncSetAttribute((const void*)dense_xbwd<0, 4, 7, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b) != hipSuccess ||
-                                  hipFuncSetAttribute((const void*)dense_xbwd<0, 2, 7, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b) != hipSuccess)) {
-                    (void)hipGetLastError();
-                    p->xfused = false;
-                }
-                if (p->xfused && p->xb9 &&
-                    (hipFuncSetAttribute((const void*)dense_xbwd<0, 4, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b9) != hipSuccess ||
-                     hipFuncSetAttribute((const void*)dense_xbwd<0, 4, 9, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b9) != hipSuccess)) {
-                    (void)hipGetLastError();
-                    p->xb9 = false;
-                }
-            }
-        }
+        m.exact_data = true;
+        for (size_t i = 0; m.exact_data && i < n_values; ++i) m.exact_data = (bits[i] & 0xFFFFu) == 0u;
+    }
+    int dev = 0, n_cu = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n_cu > 0)
+        m.n_cu = (uint32_t)n_cu;
+    p->mp = dsel::model_plan(m, p->sw);
+    // the device facts: a refused LDS grant sends the model to the six-launch sequence (regular kinds) or to seven-block tiles (nine-block
+    // kinds); on a profiling kind it changes nothing
+    for (uint32_t i = 0; i < p->mp.n_attr; ++i) {
+        const dsel::Attr& at = p->mp.attr[i];
+        const void* fn = dense_is_xfwd(at.kind) ? (const void*)kDenseXfwd[at.kind - dsel::XFWD_FIRST] : (const void*)kDenseXbwd[at.kind - dsel::XBWD_FIRST];
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)at.lds) == hipSuccess) continue;
+        (void)hipGetLastError();
+        if (at.cls == dsel::ATTR_REGULAR) m.fused_ok = false;
+        if (at.cls == dsel::ATTR_NINE) m.xb9_ok = false;
     }
     p->d.uniform = nullptr; p->d.consts = nullptr; p->d.param_uniform_ptr = nullptr; p->d.param_uniform_idx = nullptr;
     p->d.dataset = nullptr; p->d.labels = nullptr;
@@ -1306,7 +1313,8 @@ extern "C" int bsvi_dense_create(const bsvi_dense_desc* desc, bsvi_dense** out) 
     return BSVI_OK;
 }
 
-extern "C" int bsvi_dense_exact_data(const bsvi_dense* p) { return (p && p->xpath) ? 1 : 0; }
+extern "C" int bsvi_dense_exact_data(const bsvi_dense* p) { return (p && p->mp.path != dsel::F32) ? 1 : 0; }
+extern "C" const char* bsvi_dense_kind_name(int kind) { return dsel::name(kind); }
 
 extern "C" void bsvi_dense_destroy(bsvi_dense* p) {
     if (!p) return;
@@ -1314,100 +1322,66 @@ extern "C" void bsvi_dense_destroy(bsvi_dense* p) {
     delete p;
 }
 
-static const uint32_t kDenseRowChunk = 64;
-static const uint32_t kDenseKSplit = 4;      // upper bound; the workspace is sized for it
-
-struct DenseLayout {
-    size_t rowp, idx, Xb, XbT, lab, eps, pv_part, qv_part, s1, s2, lik_part, dlog, ds_part, dmu_part, rowg, hpart, partial, total;
-    size_t Xb_bf, XbT_bf, Wp, logitsT, dlogp, GT;
-    size_t wsum, ws1, ws2;
-    uint32_t n_pad;
-};
-
-static bool dense_fused_for(const bsvi_dense* p, size_t n_pad) {
-    return p->xfused && 3ull * n_pad * p->d.n_classes * p->B_pad * 2ull < (1ull << 32);
-}
-
-static DenseLayout dense_layout(const bsvi_dense* p, uint32_t n_local) {
-    DenseLayout L;
-    L.n_pad = (n_local + 63) / 64 * 64;
-    const size_t R = p->R, np = L.n_pad, Bp = p->B_pad, Pp = p->P_pad, C = p->d.n_classes;
-    // the fused launches address the dlog pieces with 32-bit buffer offsets: beyond 4 GB of pieces the six-launch sequence serves
-    const bool fused = dense_fused_for(p, L.n_pad);
-    size_t o = 0;
-    auto take = [&](size_t floats) { size_t at = o; o += align_up(floats * 4, 256); return at; };
-    L.rowp = take(6 * R + 64);                 // mu, s, mu0, s0, {mu, s} interleaved (+ slack rows)
-    L.idx = take(Bp);
-    L.Xb = take(Bp * Pp);
-    L.XbT = take(Pp * Bp + 128);               // forward tiles are 128 columns wide: slack is only read
-    L.lab = take(Bp);
-    // (the exact-data path stores neither eps nor the f32 dlog: it has the pieces below instead)
-    L.eps = take(p->xpath ? 64 : (R + 32) * np);                // 32 rows of slack: the last feature chunk reads past P
-    L.pv_part = take(((R + kDenseRowChunk - 1) / kDenseRowChunk) * np);
-    L.qv_part = take(p->d.estimator == BSVI_EST_BLACKBOX ? ((R + kDenseRowChunk - 1) / kDenseRowChunk) * np : 1);
-    const size_t xgroups = fused ? np / 16 : kDenseKSplit;       // sample groups of dense_xbwd's partial sums
-    L.s1 = take(xgroups * R);
-    L.s2 = take(xgroups * R);
-    L.lik_part = take((Bp / 32) * np);
-    L.dlog = take(p->xpath ? 64 : C * np * Bp);
-    if (p->xpath) {
-        const size_t Kp = p->Kp, NC = np * C;
-        L.Xb_bf = take((Bp * Kp + 1) / 2 + 64);
-        L.XbT_bf = take(((size_t)p->d.n_features * Bp + 1) / 2 + 64);
-        L.Wp = take(fused ? 64 : (3 * NC * Kp + 1) / 2 + 64);
-        L.logitsT = take(fused ? 64 : Bp * NC);
-        L.dlogp = take((3 * NC * Bp + 1) / 2 + 64);
-        L.GT = take(fused ? 64 : (size_t)p->d.n_features * NC);
-    } else {
-        L.Xb_bf = L.XbT_bf = L.Wp = L.logitsT = L.dlogp = L.GT = 0;
-    }
-    L.ds_part = take((fused ? xgroups : kDenseKSplit * (Bp / 64)) * R);
-    L.dmu_part = take((fused ? xgroups : kDenseKSplit * (Bp / 64)) * R);
-    L.rowg = take(4 * R);
-    L.hpart = take(3 * ((R + 63) / 64));
-    L.partial = take(2 + (size_t)p->d.n_uniform_grad);
-    L.wsum = take(2);                          // caller-weighted gradients: A, B and the weighted row sums (dense_weighted_sums)
-    L.ws1 = take(R + 4);
-    L.ws2 = take(R + 4);
-    L.total = o + 256;
-    return L;
-}
-
 extern "C" size_t bsvi_dense_workspace_bytes(const bsvi_dense* p, uint32_t n_local) {
     if (!p || !n_local) return 0;
-    return dense_layout(p, n_local).total;
+    dsel::Call c;
+    c.n_local = n_local;      // (the layout follows the sample count alone)
+    return dsel::layout(p->m, dsel::call_plan(p->m, p->sw, c)).total;
 }
 
-static int dense_fill(const bsvi_dense* p, const bsvi_dense_args* a, DParams& D) {
-    if (a) BSVI_CHECK_STRUCT(a, bsvi_dense_args);
-    if (!p || !a) return fail(BSVI_ERR_INVALID, "null argument");
-    if (!a->params_dev || !a->out_dev || !a->workspace_dev) return fail(BSVI_ERR_INVALID, "null device pointer");
+// what the selection needs of a call, behind the checks of the arguments that depend on the estimator
+static int dense_call(const bsvi_dense* p, const bsvi_dense_args* a, dsel::Call& c) {
     if (!a->n_samples_local || !a->n_samples_global) return fail(BSVI_ERR_INVALID, "zero samples");
-    const DenseLayout L = dense_layout(p, a->n_samples_local);
-    char* ws = (char*)a->workspace_dev;
-    memset(&D, 0, sizeof(D));
-    D.uniform = p->uniform; D.consts = p->consts; D.params = a->params_dev; D.dataset = p->dataset; D.labels = p->labels;
-    D.noise_in = a->noise_dev; D.indices_in = a->indices_dev; D.noise_out = a->noise_out_dev; D.indices_out = a->indices_out_dev;
-    D.fvalue_out = a->fvalue_out_dev;
     if (a->q_weight_dev && p->d.estimator != BSVI_EST_BLACKBOX)
         return fail(BSVI_ERR_INVALID, "q_weight_dev needs a model lowered for the BlackBox estimator (its launches accumulate log q)");
     if (a->logq_out_dev && p->d.estimator != BSVI_EST_BLACKBOX)
         return fail(BSVI_ERR_INVALID, "logq_out_dev needs a model lowered for the BlackBox estimator (its launches accumulate log q)");
     if (p->d.estimator == BSVI_EST_BLACKBOX && !a->f_weight_dev != !a->q_weight_dev)
         return fail(BSVI_ERR_INVALID, "a BlackBox model takes f_weight_dev and q_weight_dev together (or neither)");
+    c.n_local = a->n_samples_local;
+    c.fvalue_out = a->fvalue_out_dev != nullptr; c.f_weight = a->f_weight_dev != nullptr; c.q_weight = a->q_weight_dev != nullptr;
+    c.logq_out = a->logq_out_dev != nullptr; c.noise_in = a->noise_dev != nullptr;
+    return BSVI_OK;
+}
+
+extern "C" int bsvi_dense_plan(const bsvi_dense* p, const bsvi_dense_args* a, int32_t* kinds, uint32_t capacity) {
+    if (a) BSVI_CHECK_STRUCT(a, bsvi_dense_args);
+    if (!p || !a || (!kinds && capacity)) return fail(BSVI_ERR_INVALID, "null argument");
+    dsel::Call c;
+    const int rc = dense_call(p, a, c);
+    if (rc) return rc;
+    const dsel::Plan plan = dsel::call_plan(p->m, p->sw, c);
+    for (uint32_t i = 0; i < plan.n && i < capacity; ++i) kinds[i] = (int32_t)plan.launch[i].kind;
+    return (int)plan.n;
+}
+
+static int dense_fill(const bsvi_dense* p, const bsvi_dense_args* a, DParams& D, dsel::Plan& plan) {
+    if (a) BSVI_CHECK_STRUCT(a, bsvi_dense_args);
+    if (!p || !a) return fail(BSVI_ERR_INVALID, "null argument");
+    if (!a->params_dev || !a->out_dev || !a->workspace_dev) return fail(BSVI_ERR_INVALID, "null device pointer");
+    dsel::Call c;
+    const int rc = dense_call(p, a, c);
+    if (rc) return rc;
+    plan = dsel::call_plan(p->m, p->sw, c);
+    const dsel::Layout L = dsel::layout(p->m, plan);
+    char* ws = (char*)a->workspace_dev;
+    memset(&D, 0, sizeof(D));
+    D.uniform = p->uniform; D.consts = p->consts; D.params = a->params_dev; D.dataset = p->dataset; D.labels = p->labels;
+    D.noise_in = a->noise_dev; D.indices_in = a->indices_dev; D.noise_out = a->noise_out_dev; D.indices_out = a->indices_out_dev;
+    D.fvalue_out = a->fvalue_out_dev;
     D.f_weight = a->f_weight_dev; D.q_weight = a->q_weight_dev; D.logq_out = a->logq_out_dev;
     D.wsum = (float*)(ws + L.wsum); D.ws1 = (float*)(ws + L.ws1); D.ws2 = (float*)(ws + L.ws2);
     D.rowp = (float*)(ws + L.rowp); D.idx = (int32_t*)(ws + L.idx); D.Xb = (float*)(ws + L.Xb); D.XbT = (float*)(ws + L.XbT);
     D.lab = (float*)(ws + L.lab); D.eps = (float*)(ws + L.eps); D.pv_part = (float*)(ws + L.pv_part);
     D.qv_part = (float*)(ws + L.qv_part);
     D.estimator = p->d.estimator;
-    D.per_sample = (a->fvalue_out_dev || p->d.estimator == BSVI_EST_BLACKBOX) ? 1u : 0u;
+    D.per_sample = plan.per_sample;
     D.s1 = (float*)(ws + L.s1); D.s2 = (float*)(ws + L.s2); D.lik_part = (float*)(ws + L.lik_part);
     D.dlog = (float*)(ws + L.dlog); D.ds_part = (float*)(ws + L.ds_part); D.dmu_part = (float*)(ws + L.dmu_part);
     D.rowg = (float*)(ws + L.rowg); D.hpart = (float*)(ws + L.hpart); D.partial = (float*)(ws + L.partial);
-    D.C = p->d.n_classes; D.P = p->d.n_features; D.P_pad = p->P_pad; D.DS = p->d.dataset_size; D.B = p->d.batch_size;
-    D.B_pad = p->B_pad; D.R = p->R;
-    D.n_local = a->n_samples_local; D.n_global = a->n_samples_global; D.n_pad = L.n_pad; D.sample_base = a->sample_base;
+    D.C = p->d.n_classes; D.P = p->d.n_features; D.P_pad = plan.P_pad; D.DS = p->d.dataset_size; D.B = p->d.batch_size;
+    D.B_pad = plan.B_pad; D.R = plan.R;
+    D.n_local = a->n_samples_local; D.n_global = a->n_samples_global; D.n_pad = plan.n_pad; D.sample_base = a->sample_base;
     D.likelihood = p->d.likelihood; D.n_uniform_grad = p->d.n_uniform_grad;
     D.q_loc_u = p->d.q_loc_u; D.q_scale_u = p->d.q_scale_u; D.prior_loc_u = p->d.prior_loc_u; D.prior_scale_u = p->d.prior_scale_u;
     D.q_loc_stride = p->d.q_loc_stride; D.q_scale_stride = p->d.q_scale_stride;
@@ -1415,203 +1389,73 @@ static int dense_fill(const bsvi_dense* p, const bsvi_dense_args* a, DParams& D)
     D.lik_weight = p->d.lik_weight; D.prior_weight = p->d.prior_weight; D.entropy_weight = p->d.entropy_weight;
     D.seed_lo = (uint32_t)a->seed; D.seed_hi = (uint32_t)(a->seed >> 32);
     D.offset_lo = (uint32_t)a->offset; D.offset_hi = (uint32_t)(a->offset >> 32);
-    D.row_chunk = kDenseRowChunk;
-    D.xpath = p->xpath ? 1u : 0u; D.Kp = p->Kp;
-    if (p->xpath) {
+    D.row_chunk = dsel::kDenseRowChunk;
+    D.xpath = plan.exact ? 1u : 0u; D.Kp = plan.Kp;
+    if (plan.exact) {
         D.Xb_bf = (uint16_t*)(ws + L.Xb_bf); D.XbT_bf = (uint16_t*)(ws + L.XbT_bf); D.Wp = (uint16_t*)(ws + L.Wp);
         D.logitsT = (float*)(ws + L.logitsT); D.dlogp = (uint16_t*)(ws + L.dlogp); D.GT = (float*)(ws + L.GT);
     }
-    // as many sample splits (<= kDenseKSplit) as keep each a multiple of the 32-sample step, preferring a
-    // unit count that spreads evenly over the 8 XCDs
-    D.ksplit = 1;
-    for (uint32_t k = kDenseKSplit; k >= 1; k >>= 1)
-        if (L.n_pad % (32 * k) == 0) { D.ksplit = k; break; }
-    if (p->xpath) D.ksplit = 4;        // = kXGroups
-    D.lik_parts = D.B_pad / 64;
+    D.ksplit = plan.ksplit; D.lik_parts = plan.lik_parts; D.xfused = plan.xfused ? 1u : 0u;
     D.stamps = g_debug_stamps;
-    if (dense_fused_for(p, L.n_pad)) {
-        D.xfused = 1u;
-        D.ksplit = L.n_pad / 16;       // dense_xbwd: one partial per block of 16 samples (dense_rows adds them in order)
-        D.lik_parts = (D.B_pad + 511) / 512;
-    }
     return BSVI_OK;
 }
 
-// the exact-data iteration: heads (row parameters, minibatch + its bf16 copies) | W pieces | logits product | likelihood and
-// dlog pieces | gradient product | reduction against eps — then the common tail (dense_rows, dense_epilogue)
-// the fused exact-data iteration (dense_xfused.inc): heads | [per-sample prior sums] | draw + logits product + likelihood |
-// gradient product + reduction against eps — then the common tail
-static int dense_launch_fused(const bsvi_dense* p, const DParams& D, hipStream_t s) {
-    {
-        const uint32_t n_tiles = (D.B_pad / 64) * (D.P_pad / 64), n_rowp = (D.R + 255) / 256;
-        hipLaunchKernelGGL(dense_head, dim3(n_tiles + n_rowp), dim3(256), 0, s, D, 0u, n_tiles);
-    }
-    if (D.per_sample) hipLaunchKernelGGL(dense_wsplit, dim3(D.n_pad), dim3(256), 0, s, D);      // (sums only: D.xfused)
-    // samples per workgroup: as many as fill the 64 rows of W, but no fewer workgroups than CUs
-    uint32_t NS = XF_ROWS / D.C;
-    const uint32_t want = D.n_pad / p->n_cu;
-    if (NS > want) NS = want ? want : 1u;
-    // (BSVI_XF_NS: measurements.  cfg 4, C = 10: NS = 3 / 4 / 5 / 6 -> 154.7 / 138.1 / 147.6 / 148.4 us per iteration — one workgroup
-    //  per CU beats fuller 64-row tiles on fewer CUs, and 32-row tiles on 1.33 rounds of workgroups)
-    { static const uint32_t force = [] { const char* e = getenv("BSVI_XF_NS"); return e ? (uint32_t)atoi(e) : 0u; }(); if (force && force * D.C <= XF_ROWS) NS = force; }
-    while (NS > 1u && xf_epilogue_lds(NS, D.C) > XF_FWD_LDS) --NS;
-    static const int dbg_f = [] { const char* e = getenv("BSVI_XF_DEBUG"); return e ? (e[0] - '0') & 7 : 0; }();
-    static const int dbg_b = [] { const char* e = getenv("BSVI_XB_DEBUG"); return e ? (e[0] - '0') & 3 : 0; }();
-    const dim3 fgrid((D.n_pad + NS - 1) / NS, (D.B_pad + 511) / 512);
-    if (D.f_weight) {       // (caller-weighted gradients: the instantiations that read a_n)
-        if (NS * D.C <= 32u) hipLaunchKernelGGL((dense_xfwd<0, 1, true>), fgrid, dim3(512), XF_FWD_LDS, s, D, NS);
-        else hipLaunchKernelGGL((dense_xfwd<0, 2, true>), fgrid, dim3(512), XF_FWD_LDS, s, D, NS);
-    } else if (NS * D.C <= 32u) hipLaunchKernelGGL((dense_xfwd<0, 1>), fgrid, dim3(512), XF_FWD_LDS, s, D, NS);
-    else switch (dbg_f) {
-    case 1: hipLaunchKernelGGL((dense_xfwd<1, 2>), fgrid, dim3(512), XF_FWD_LDS, s, D, NS); break;
-    case 2: hipLaunchKernelGGL((dense_xfwd<2, 2>), fgrid, dim3(512), XF_FWD_LDS, s, D, NS); break;
-    case 3: hipLaunchKernelGGL((dense_xfwd<3, 2>), fgrid, dim3(512), XF_FWD_LDS, s, D, NS); break;
-    case 4: hipLaunchKernelGGL((dense_xfwd<4, 2>), fgrid, dim3(512), XF_FWD_LDS, s, D, NS); break;
-    case 5: hipLaunchKernelGGL((dense_xfwd<5, 2>), fgrid, dim3(512), XF_FWD_LDS, s, D, NS); break;
-    case 6: hipLaunchKernelGGL((dense_xfwd<6, 2>), fgrid, dim3(512), XF_FWD_LDS, s, D, NS); break;
-    default: hipLaunchKernelGGL((dense_xfwd<0, 2>), fgrid, dim3(512), XF_FWD_LDS, s, D, NS);
-    }
-    // feature tiles of RB 16-row blocks of x^T: nine when they fit LDS (BSVI_XB_RB=7: the round-4 tiling), the P / 16 blocks dealt out evenly
-    static const int rb_force = [] { const char* e = getenv("BSVI_XB_RB"); return e ? atoi(e) : 0; }();
-    const uint32_t RB = (p->xb9 && dbg_b == 0 && rb_force != 7) ? 9u : 7u;
-    const uint32_t nrb = (D.P + 15u) / 16u, tiles_m = (nrb + RB - 1u) / RB, rb_base = nrb / tiles_m, rb_extra = nrb % tiles_m;
-    // One workgroup per CU (its x^T tile takes 118 / 152 KB of LDS), and workgroup i runs on XCD i % 8: the column groups of ONE XCD
-    // times the feature tiles must fit that XCD's n_cu / 8 CUs.  (Round 4 sized for the chip — 256 / 7 = 36 groups — which put
-    // 5 groups x 7 tiles = 35 workgroups on the 32 CUs of XCDs 0-3: three of them waited for a whole second round and the kernel
-    // took twice a workgroup's time.  36 -> 32 groups: 66.3 -> 36.9 us, profiles/r5/xbwd_groups.txt.)
-    const uint32_t cu_per_xcd = p->n_cu >= 8u ? p->n_cu / 8u : 1u;
-    uint32_t groups = 8u * (cu_per_xcd / tiles_m);
-    if (!groups) groups = p->n_cu / tiles_m;
-    const uint32_t total_cb = D.C * (D.n_pad / 16);
-    { static const uint32_t force = [] { const char* e = getenv("BSVI_XB_GROUPS"); return e ? (uint32_t)atoi(e) : 0u; }(); if (force) groups = force; }
-    if (groups > total_cb) groups = total_cb;
-    if (!groups) groups = 1;
-    const dim3 bgrid(8 * ((groups + 7) / 8) * tiles_m);
-    const uint32_t blds = 16u * RB * (D.B_pad * 2 + 32);
-    if (D.noise_in) {        // (caller-supplied normals: the instantiations that load them)
-        if (RB == 9u) hipLaunchKernelGGL((dense_xbwd<0, 4, 9, true>), bgrid, dim3(512), blds, s, D, tiles_m, groups, rb_base, rb_extra);
-        else if (D.B_pad % 256u == 0u) hipLaunchKernelGGL((dense_xbwd<0, 4, 7, true>), bgrid, dim3(512), blds, s, D, tiles_m, groups, rb_base, rb_extra);
-        else hipLaunchKernelGGL((dense_xbwd<0, 2, 7, true>), bgrid, dim3(512), blds, s, D, tiles_m, groups, rb_base, rb_extra);
-    } else if (RB == 9u) {
-        hipLaunchKernelGGL((dense_xbwd<0, 4, 9>), bgrid, dim3(512), blds, s, D, tiles_m, groups, rb_base, rb_extra);
-    } else if (D.B_pad % 256u == 0u) {     // (groups of two k steps in a ring of four register sets; B_pad = 128 (mod 256): a ring of two)
-        switch (dbg_b) {
-        case 1: hipLaunchKernelGGL((dense_xbwd<1, 4, 7>), bgrid, dim3(512), blds, s, D, tiles_m, groups, rb_base, rb_extra); break;
-        case 2: hipLaunchKernelGGL((dense_xbwd<2, 4, 7>), bgrid, dim3(512), blds, s, D, tiles_m, groups, rb_base, rb_extra); break;
-        case 3: hipLaunchKernelGGL((dense_xbwd<3, 4, 7>), bgrid, dim3(512), blds, s, D, tiles_m, groups, rb_base, rb_extra); break;
-        default: hipLaunchKernelGGL((dense_xbwd<0, 4, 7>), bgrid, dim3(512), blds, s, D, tiles_m, groups, rb_base, rb_extra);
-        }
-    } else {
-        hipLaunchKernelGGL((dense_xbwd<0, 2, 7>), bgrid, dim3(512), blds, s, D, tiles_m, groups, rb_base, rb_extra);
-    }
-    // (the tail — rows, sample sums, parameters — follows from dense_reduce)
-    HIP_TRY(hipGetLastError());
-    return BSVI_OK;
-}
-
-static int dense_launch_exact(const bsvi_dense* p, const DParams& D, hipStream_t s) {
-    if (D.xfused) return dense_launch_fused(p, D, s);      // (dense_fill cleared the flag if the dlog pieces pass 4 GB: 32-bit buffer offsets)
-    const uint32_t work0 = D.R > D.B_pad ? D.R : D.B_pad, work1 = D.B_pad * D.P_pad;
-    (void)work0; (void)work1;
-    {   // row parameters and the minibatch (with its bf16 copies) in one launch of heterogeneous workgroups, no noise blocks
-        const uint32_t n_tiles = (D.B_pad / 64) * (D.P_pad / 64), n_rowp = (D.R + 255) / 256;
-        hipLaunchKernelGGL(dense_head, dim3(n_tiles + n_rowp), dim3(256), 0, s, D, 0u, n_tiles);
-    }
-    hipLaunchKernelGGL(dense_wsplit, dim3(D.n_pad), dim3(256), 0, s, D);
-    const int NC = (int)(D.n_pad * D.C);
-    int rc = bsvi_xgemm_nt(D.Xb_bf, nullptr, D.Wp, (long)NC * D.Kp, D.logitsT, NC, (int)D.B_pad, NC, (int)D.Kp, s);
+// One iteration: the plan of this call (dense_select.h), then its launches in order.  R arrives zeroed but for what an optimizer step
+// adds to the parameter kernel's block.
+static int dense_iterate(const bsvi_dense* p, const bsvi_dense_args* a, RParams& R) {
+    DParams D;
+    dsel::Plan plan;
+    int rc = dense_fill(p, a, D, plan);
     if (rc) return rc;
-    hipLaunchKernelGGL(dense_ce, dim3((D.B_pad / 64) * (D.n_pad / 8)), dim3(256), 0, s, D);
-    rc = bsvi_xgemm_nt(D.XbT_bf, nullptr, D.dlogp, (long)NC * D.B_pad, D.GT, NC, (int)D.P, NC, (int)D.B_pad, s);
-    if (rc) return rc;
-    hipLaunchKernelGGL(dense_xreduce, dim3((D.P / 4) * kXGroups), dim3(256), 0, s, D);
-    hipLaunchKernelGGL(dense_rows, dim3((D.R + 255) / 256), dim3(256), 0, s, D);
-    DParams E = D;
-    E.sums_folded = 1;          // dense_wsplit wrote the per-sample sums whole
-    hipLaunchKernelGGL(dense_epilogue, dim3(1), dim3(1024), 0, s, E);
-    HIP_TRY(hipGetLastError());
-    return BSVI_OK;
-}
-
-static int dense_launch(const bsvi_dense* p, const DParams& D, hipStream_t s) {
-    // (caller-weighted gradients: the weighted row sums depend on nothing the iteration writes)
-    if (D.f_weight) hipLaunchKernelGGL(dense_weighted_sums, dim3((D.R + 255) / 256), dim3(256), 0, s, D);
-    if (D.xpath) return dense_launch_exact(p, D, s);
-    const uint32_t work0 = D.R > D.B_pad ? D.R : D.B_pad, work1 = D.B_pad * D.P_pad;
-    const dim3 ngrid(D.n_pad / 256 ? (D.n_pad + 255) / 256 : 1, (D.R + D.row_chunk - 1) / D.row_chunk);
-    if (!D.per_sample) {
-        // the three heads are independent: one launch of heterogeneous workgroups (dense_head)
-        const uint32_t n_noise = ngrid.x * ngrid.y, n_tiles = (D.B_pad / 64) * (D.P_pad / 64), n_rowp = (D.R + 255) / 256;
-        hipLaunchKernelGGL(dense_head, dim3(n_noise + n_tiles + n_rowp), dim3(256), 0, s, D, n_noise, n_tiles);
-    } else {
-        // per-sample prior values wanted: the noise kernel reads the row parameters, so the heads run in order
-        hipLaunchKernelGGL(dense_prologue, dim3((work0 + 255) / 256), dim3(256), 0, s, D);
-        hipLaunchKernelGGL(dense_gather, dim3((work1 + 255) / 256 > 2048 ? 2048 : (work1 + 255) / 256), dim3(256), 0, s, D);
-        hipLaunchKernelGGL(dense_noise, ngrid, dim3(256), 0, s, D);
-    }
-    const dim3 fgrid((D.n_pad / 16) * (D.B_pad / 64));
-    if (D.C == 1) hipLaunchKernelGGL((dense_forward<1>), fgrid, dim3(256), 0, s, D);
-    else if (D.C <= 4) hipLaunchKernelGGL((dense_forward<4>), fgrid, dim3(256), 0, s, D);
-    else if (D.C <= 10) hipLaunchKernelGGL((dense_forward<10>), fgrid, dim3(256), 0, s, D);
-    else hipLaunchKernelGGL((dense_forward<16>), fgrid, dim3(256), 0, s, D);
-    hipLaunchKernelGGL(dense_backward, dim3(D.C * ((D.P + 63) / 64) * D.ksplit * (D.B_pad / 64)), dim3(256), 0, s, D);
-    hipLaunchKernelGGL(dense_rows, dim3((D.R + 255) / 256), dim3(256), 0, s, D);
-    if (D.per_sample) {
-        const uint32_t with_q = (D.estimator == BSVI_EST_BLACKBOX && D.entropy_weight != 0.0f) ? 1u : 0u;
-        hipLaunchKernelGGL(dense_sample_sums, dim3(D.n_pad / 64), dim3(256), 0, s, D, with_q);
-        DParams E = D;
-        E.sums_folded = 1;
-        hipLaunchKernelGGL(dense_epilogue, dim3(1), dim3(1024), 0, s, E);
-    } else {
-        hipLaunchKernelGGL(dense_epilogue, dim3(1), dim3(1024), 0, s, D);
-    }
-    HIP_TRY(hipGetLastError());
-    return BSVI_OK;
-}
-
-static void dense_rparams(const bsvi_dense* p, const DParams& D, float* params, float* out, RParams& R) {
-    memset(&R, 0, sizeof(R));
     R.uniform = p->uniform; R.pu_ptr = p->pu_ptr; R.pu_idx = p->pu_idx;
-    R.partials = D.partial; R.params = params; R.out = out;
+    R.partials = D.partial; R.params = (float*)a->params_dev; R.out = a->out_dev;
     R.n_uniform_grad = p->d.n_uniform_grad; R.n_params = p->d.n_params; R.n_blocks = 1; R.n_global = D.n_global;
-}
-
-static int dense_reduce(const bsvi_dense* p, const DParams& D, const RParams& R, hipStream_t s) {
-    if (D.xfused) {
-        DParams E = D;
-        E.sums_folded = 1;      // (the per-sample sums, when asked for, were written whole by dense_wsplit)
-        // (measured and dropped: rows + sample sums as ONE launch whose last workgroup — arrival ticket behind agent-scope
-        //  fences — runs the sums: 18 us against 6.5 + 4.7, the two fences and a 256-thread epilogue cost more than a launch;
-        //  with the parameter kernel folded in as well, 220 us: four dependent loads per parameter walked by one workgroup)
-        hipLaunchKernelGGL(dense_rows, dim3((D.R + 63) / 64), dim3(256), 0, s, D);      // (sliced form: 64 rows per workgroup)
-        // the epilogue's sums inside the parameter kernel when nothing but the plain value is asked of it (BSVI_DENSE_FOLD=0: two launches)
-        const uint32_t nug = D.n_uniform_grad;
-        const bool own_entries = (D.q_loc_stride || D.q_loc_u >= nug) && (D.q_scale_stride || D.q_scale_u >= nug) &&
-                                 (D.prior_loc_stride || D.prior_loc_u >= nug) && (D.prior_scale_stride || D.prior_scale_u >= nug);
-        const bool blackbox = D.estimator == BSVI_EST_BLACKBOX && D.entropy_weight != 0.0f;
-        if (p->fold && own_entries && !blackbox && !D.per_sample && !D.f_weight && !D.fvalue_out && !D.logq_out) {
-            const uint32_t n = p->d.n_params ? p->d.n_params : 1;
-            hipLaunchKernelGGL(dense_param_fold_kernel, dim3((n + 255) / 256), dim3(256), 0, s, R, E, (D.R + 63) / 64);
-            HIP_TRY(hipGetLastError());
-            return BSVI_OK;
+    DParams E = D;      // what dense_epilogue and dense_param_fold_kernel read: the per-sample sums may already be whole
+    E.sums_folded = plan.sums_folded ? 1u : 0u;
+    const hipStream_t s = (hipStream_t)a->stream;
+    const int NC = (int)(D.n_pad * D.C);
+    for (uint32_t i = 0; i < plan.n; ++i) {
+        const dsel::Launch& l = plan.launch[i];
+        const dim3 grid(l.grid_x, l.grid_y), block(l.block);
+        dense_plain_fn plain = nullptr;      // the kernels that take the parameter block alone, without dynamic LDS
+        switch (l.kind) {
+        case dsel::WEIGHTED_SUMS: plain = dense_weighted_sums; break;
+        case dsel::PROLOGUE: plain = dense_prologue; break;
+        case dsel::GATHER: plain = dense_gather; break;
+        case dsel::NOISE: plain = dense_noise; break;
+        case dsel::FORWARD_1: case dsel::FORWARD_4: case dsel::FORWARD_10: case dsel::FORWARD_16: plain = kDenseForward[l.kind - dsel::FORWARD_FIRST]; break;
+        case dsel::BACKWARD: plain = dense_backward; break;
+        case dsel::WSPLIT: plain = dense_wsplit; break;
+        case dsel::CE: plain = dense_ce; break;
+        case dsel::XREDUCE: plain = dense_xreduce; break;
+        case dsel::ROWS: case dsel::ROWS_SLICED: plain = dense_rows; break;
+        case dsel::HEAD: hipLaunchKernelGGL(dense_head, grid, block, 0, s, D, l.arg[0], l.arg[1]); break;
+        case dsel::XGEMM_LOGITS:
+            rc = bsvi_xgemm_nt(D.Xb_bf, nullptr, D.Wp, (long)NC * D.Kp, D.logitsT, NC, (int)D.B_pad, NC, (int)D.Kp, s);
+            if (rc) return rc;
+            break;
+        case dsel::XGEMM_GRAD:
+            rc = bsvi_xgemm_nt(D.XbT_bf, nullptr, D.dlogp, (long)NC * D.B_pad, D.GT, NC, (int)D.P, NC, (int)D.B_pad, s);
+            if (rc) return rc;
+            break;
+        case dsel::SAMPLE_SUMS: hipLaunchKernelGGL(dense_sample_sums, grid, block, 0, s, D, l.arg[0]); break;
+        case dsel::EPILOGUE: hipLaunchKernelGGL(dense_epilogue, grid, block, 0, s, E); break;
+        case dsel::PARAM: hipLaunchKernelGGL(dense_param_kernel, grid, block, 0, s, R); break;
+        case dsel::PARAM_FOLD: hipLaunchKernelGGL(dense_param_fold_kernel, grid, block, 0, s, R, E, l.arg[0]); break;
+        default:
+            if (dense_is_xfwd(l.kind)) hipLaunchKernelGGL(kDenseXfwd[l.kind - dsel::XFWD_FIRST], grid, block, l.lds, s, D, l.arg[0]);
+            else hipLaunchKernelGGL(kDenseXbwd[l.kind - dsel::XBWD_FIRST], grid, block, l.lds, s, D, l.arg[0], l.arg[1], l.arg[2], l.arg[3]);
         }
-        hipLaunchKernelGGL(dense_epilogue, dim3(1), dim3(1024), 0, s, E);
+        if (plain) hipLaunchKernelGGL(plain, grid, block, 0, s, D);
     }
-    const uint32_t n = p->d.n_params ? p->d.n_params : 1;
-    hipLaunchKernelGGL(dense_param_kernel, dim3((n + 255) / 256), dim3(256), 0, s, R);
     HIP_TRY(hipGetLastError());
     return BSVI_OK;
 }
 
 extern "C" int bsvi_dense_fwd_bwd(const bsvi_dense* p, const bsvi_dense_args* a) {
-    DParams D;
-    int rc = dense_fill(p, a, D);
-    if (rc) return rc;
-    rc = dense_launch(p, D, (hipStream_t)a->stream);
-    if (rc) return rc;
     RParams R;
-    dense_rparams(p, D, (float*)a->params_dev, a->out_dev, R);
-    return dense_reduce(p, D, R, (hipStream_t)a->stream);
+    memset(&R, 0, sizeof(R));
+    return dense_iterate(p, a, R);
 }
 
 extern "C" int bsvi_dense_step(const bsvi_dense* p, const bsvi_dense_args* a, const bsvi_opt_cfg* cfg, float* params_dev,
@@ -1624,16 +1468,11 @@ extern "C" int bsvi_dense_step(const bsvi_dense* p, const bsvi_dense_args* a, co
         return fail(BSVI_ERR_INVALID, "caller-weighted gradients are an evaluation (bsvi_dense_fwd_bwd), not an optimizer step");
     bsvi_dense_args aa = *a;
     aa.params_dev = params_dev;
-    DParams D;
-    rc = dense_fill(p, &aa, D);
-    if (rc) return rc;
-    rc = dense_launch(p, D, (hipStream_t)a->stream);
-    if (rc) return rc;
     RParams R;
-    dense_rparams(p, D, params_dev, a->out_dev, R);
+    memset(&R, 0, sizeof(R));
     R.state = state_dev; R.active_mask = active_mask_dev; R.loss_slot = loss_slot_dev; R.finite_slot = finite_slot_dev;
     R.do_finalize = 1; R.do_step = 1; R.cfg = *cfg;
-    return dense_reduce(p, D, R, (hipStream_t)a->stream);
+    return dense_iterate(p, &aa, R);
 }
 
 extern "C" int bsvi_dense_finalize(const bsvi_dense* p, float* out_dev, uint32_t n_global, void* stream) {

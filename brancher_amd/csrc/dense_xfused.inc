@@ -22,6 +22,12 @@
 // HBM traffic per iteration at config 4: the dlog pieces once out and (through L2) once in, 2 x 31 MB, plus 8 MB of partial
 // sums — against 300-500 MB in round 3.  No atomics on floats; every sum has a fixed order.
 
+#include "dense_select.h"
+// the tile constants the launch plan shares with the kernels live there: XF_ROWS (sample, class) rows of a dense_xfwd workgroup and
+// its XF_FWD_LDS bytes (the epilogue's share: xf_epilogue_lds), XF_MT / XF_MT9 rows of x^T resident in dense_xbwd
+using bsvi_dense_select::XF_ROWS;
+using bsvi_dense_select::XF_FWD_LDS;
+
 typedef __bf16 xf_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float xf_f32x16 __attribute__((ext_vector_type(16)));
 typedef float xf_f32x4 __attribute__((ext_vector_type(4)));
@@ -30,19 +36,13 @@ typedef uint32_t xf_u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr uint32_t XF_KC = 64;                       // features per chunk of W in LDS (two k steps of 32)
 constexpr uint32_t XF_WS = 2 * XF_KC + 16;           // row stride in bytes: 9 x 16, so 16 rows sit on 16 different bank quads
-constexpr uint32_t XF_ROWS = 64;                     // (sample, class) rows of a workgroup: two 32-column MFMA blocks
 constexpr uint32_t XF_PLANE = XF_ROWS * XF_WS;
 constexpr uint32_t XF_BUF = 3 * XF_PLANE;
 constexpr uint32_t XF_DRAW_LDS = 2 * XF_BUF;         // two chunks of W: one being drawn, one being multiplied (55 296 B)
 constexpr uint32_t XF_XSLOT = 8192;                  // the A fragments of one k step of one product wave: 2 k chunks x 4 row blocks x 1 KB
 constexpr uint32_t XF_XRING = 3;                     // ... three steps deep per wave (two steps = 64 KB per CU in flight)
 constexpr uint32_t XF_LOOP_LDS = XF_DRAW_LDS + 4 * XF_XRING * XF_XSLOT;      // 153 600 B
-// after the loop: the 512-row logits tile (row stride NS C | 1 words) + per-quad likelihoods [NS][128] + their partial sums [NS][8]
-constexpr uint32_t xf_epilogue_lds(uint32_t NS, uint32_t C) { return (512u * ((NS * C) | 1u) + NS * 136u) * 4u; }
-constexpr uint32_t XF_FWD_LDS = 160u * 1024u;              // (the samples per workgroup are capped so that the epilogue fits: dense_launch_fused)
-static_assert(XF_LOOP_LDS <= XF_FWD_LDS, "the product loop's LDS");
-constexpr uint32_t XF_MT = 112;                      // rows of x^T resident in dense_xbwd with 7 MFMA blocks of 16 per tile (784 = 7 x 112)
-constexpr uint32_t XF_MT9 = 144;                     // ... with 9: 49 row blocks as tiles of 9, 8, 8, 8, 8, 8 (152 KB of LDS at B_pad = 512)
+static_assert(XF_LOOP_LDS <= XF_FWD_LDS, "the product loop's LDS");      // (after the loop: xf_epilogue_lds, dense_select.h)
 
 __device__ __forceinline__ xf_u32x2 xf_pack4(const uint16_t v[4]) {
     return xf_u32x2{(uint32_t)v[0] | ((uint32_t)v[1] << 16), (uint32_t)v[2] | ((uint32_t)v[3] << 16)};
@@ -591,7 +591,7 @@ __global__ void __launch_bounds__(512) dense_xbwd(const DParams D, const uint32_
             }
         }
     };
-    const uint32_t n_groups = D.B_pad / 64u;            // (a multiple of NR: dense_launch_fused picks the instantiation)
+    const uint32_t n_groups = D.B_pad / 64u;            // (a multiple of NR: call_plan, dense_select.h, picks the instantiation)
     // x^T rows p0 .. p0 + 111 -> LDS by DMA (global_load_lds, 16 bytes per lane: one instruction = 1 KB = one row at
     // B_pad = 512), wave w takes rows w, w + 8, ...: all of a wave's rows in flight at once, no registers.  (Round 4 staged
     // through registers, seven loads in flight per lane: 9 500 cycles before the first MFMA.)  Rows beyond P are zeros.

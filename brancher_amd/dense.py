@@ -192,6 +192,24 @@ class CompiledDense:
         bf16 number (three bf16 MFMAs on the exact pieces of the f32 operand, bsvi_dense_exact_data), else "f32" """
         return "bf16x3" if self._exact_data else "f32"
 
+    def launch_plan(self, number_samples, noise=False, want_fvalues=False, weighted=False):
+        """the kernels an evaluation of `number_samples` samples launches, by name and in order, without launching them
+        (bsvi_dense_plan; csrc/dense_select.h): `noise` — the caller supplies the normals; `want_fvalues` — per-sample values
+        (and log q under the BlackBox estimator) are asked for, as `evaluate` does; `weighted` — `evaluate_weighted`"""
+        from brancher_amd import engine
+        rank, world = engine.dist_info()
+        _, n_local = engine.shard(number_samples, rank, world)
+        some = lambda present: C.c_void_p(16) if present else None      # only the presence of an optional pointer matters
+        blackbox = getattr(self.program, "estimator", "pathwise") == "blackbox"
+        args = DenseArgs(n_samples_local=n_local, n_samples_global=number_samples, noise_dev=some(noise),
+                         fvalue_out_dev=some(want_fvalues), logq_out_dev=some(want_fvalues and blackbox),
+                         f_weight_dev=some(weighted), q_weight_dev=some(weighted))
+        kinds = (C.c_int32 * 16)()
+        n = self.lib.bsvi_dense_plan(self.handle, C.byref(args), kinds, 16)
+        if n < 0:
+            native.check(n)
+        return [self.lib.bsvi_dense_kind_name(kinds[i]).decode() for i in range(n)]
+
     def __init__(self, joint_model, posterior_model, estimator="pathwise", device=None, program=None):
         from brancher_amd import engine
         self.device = device or engine._device()

@@ -93,6 +93,8 @@ DENSE_EXPORTS = {
     "bsvi_dense_destroy": (None, [C.c_void_p]),
     "bsvi_dense_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_uint32]),
     "bsvi_dense_exact_data": (C.c_int, [C.c_void_p]),
+    "bsvi_dense_plan": (C.c_int, [C.c_void_p, C.POINTER(DenseArgs), C.POINTER(C.c_int32), C.c_uint32]),
+    "bsvi_dense_kind_name": (C.c_char_p, [C.c_int]),
     "bsvi_dense_fwd_bwd": (C.c_int, [C.c_void_p, C.POINTER(DenseArgs)]),
     "bsvi_dense_finalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "bsvi_dense_step": (C.c_int, [C.c_void_p, C.POINTER(DenseArgs), C.POINTER(OptCfg), C.c_void_p, C.c_void_p,

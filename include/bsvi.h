@@ -513,6 +513,12 @@ size_t bsvi_dense_workspace_bytes(const bsvi_dense* d, uint32_t n_samples_local)
  * f32 accumulation; the noise is never stored (both consumers draw it from the same Philox counters).  0: the f32-input MFMA
  * kernels serve the model (also with BSVI_DENSE_XGEMM=0 at create time). */
 int bsvi_dense_exact_data(const bsvi_dense* d);
+/* Which launches bsvi_dense_fwd_bwd would make for these arguments, in order, without launching anything: writes up to `capacity`
+ * kinds (brancher_amd/csrc/dense_select.h; bsvi_dense_kind_name names one, "?" for an unknown value) and returns how many there are,
+ * or a negative bsvi_status.  Only n_samples_local / n_samples_global and WHICH of the optional pointers are set matter: the plan is
+ * a function of the model, of the BSVI_DENSE_* / BSVI_XF_* / BSVI_XB_* switches as bsvi_dense_create found them, and of those. */
+int bsvi_dense_plan(const bsvi_dense* d, const bsvi_dense_args* args, int32_t* kinds, uint32_t capacity);
+const char* bsvi_dense_kind_name(int kind);
 /* ELBO forward+backward of the dense model over this GPU's sample shard; leaves sums in out_dev
  * (then bsvi_finalize / all-reduce / bsvi_optimizer_step as for bsvi_elbo_fwd_bwd). */
 int bsvi_dense_fwd_bwd(const bsvi_dense* d, const bsvi_dense_args* args);

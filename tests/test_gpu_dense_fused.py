@@ -72,6 +72,62 @@ def test_fused_launches_equal_the_six_launch_sequence_and_the_f32_kernels(shape,
     assert np.abs(replay["grads"].cpu().numpy() - a["grads"]).max() <= 2e-6 * gscale
 
 
+_HEAD, _TAIL = ("dense_head", "dense_wsplit"), ("dense_rows<sliced>", "dense_epilogue", "dense_param_kernel")
+_F32 = ("dense_backward", "dense_rows", "dense_sample_sums", "dense_epilogue", "dense_param_kernel")
+DENSE_PLAN_ROWS = [
+    # (shape, environment at create, call, the launches in order): every branch of the launch plan (csrc/dense_select.h) that a small
+    # shape reaches on 256 CUs; tests/c_abi/dense_select_table.cpp holds the same rows (tests/test_dense_select_cpu.py compares them)
+    ((64, 32, 32, 1, 50), {}, "fvalues", _HEAD + ("dense_xfwd<0,1>", "dense_xbwd<0,2,7>") + _TAIL),                   # B_pad = 128
+    ((256, 200, 32, 3, 24), {}, "fvalues", _HEAD + ("dense_xfwd<0,1>", "dense_xbwd<0,4,9>") + _TAIL),                 # B_pad = 256: nine-block tiles
+    ((256, 200, 32, 3, 24), {"BSVI_XB_RB": "7"}, "fvalues", _HEAD + ("dense_xfwd<0,1>", "dense_xbwd<0,4,7>") + _TAIL),
+    ((256, 200, 32, 3, 24), {}, "fvalues+noise", _HEAD + ("dense_xfwd<0,1>", "dense_xbwd<0,4,9,noise>") + _TAIL),
+    ((96, 40, 784, 10, 24), {"BSVI_XF_NS": "4"}, "fvalues", _HEAD + ("dense_xfwd<0,2>", "dense_xbwd<0,2,7>") + _TAIL),   # config 4's forward kernel
+    ((700, 650, 32, 1, 20), {}, "fvalues",                                                                             # B_pad = 768: x^T does not fit LDS
+     _HEAD + ("xgemm_nt<logits>", "dense_ce", "xgemm_nt<grad>", "dense_xreduce", "dense_rows", "dense_epilogue", "dense_param_kernel")),
+    ((64, 32, 30, 3, 20), {}, "fvalues", ("dense_prologue", "dense_gather", "dense_noise", "dense_forward<4>") + _F32),
+    ((64, 32, 30, 3, 20), {}, "plain", ("dense_head", "dense_forward<4>", "dense_backward", "dense_rows", "dense_epilogue", "dense_param_kernel")),
+    ((64, 32, 32, 16, 20), {"BSVI_DENSE_XGEMM": "0"}, "fvalues", ("dense_prologue", "dense_gather", "dense_noise", "dense_forward<16>") + _F32),
+    ((96, 40, 784, 10, 24), {}, "plain", ("dense_head", "dense_xfwd<0,1>", "dense_xbwd<0,2,7>", "dense_rows<sliced>", "dense_param_fold_kernel")),
+    ((96, 40, 784, 10, 24), {"BSVI_DENSE_FOLD": "0"}, "plain", ("dense_head", "dense_xfwd<0,1>", "dense_xbwd<0,2,7>") + _TAIL),
+]
+_f32_reference = {}
+
+
+@pytest.mark.parametrize("row", DENSE_PLAN_ROWS, ids=lambda r: "DS%d_B%d_P%d_C%d_N%d" % r[0] + "".join("-%s=%s" % kv for kv in r[1].items()) + "-" + r[2])
+def test_every_launch_plan_runs_what_it_says_and_equals_the_f32_kernels(row, monkeypatch):
+    """The launches of each row are the ones the library reports (bsvi_dense_plan; the switches are read when the model is created),
+    and loss, per-sample values and gradients equal those of the same model on the f32 kernels (BSVI_DENSE_XGEMM=0), within the
+    tolerances of test_fused_launches_equal_the_six_launch_sequence_and_the_f32_kernels."""
+    shape, env, call, names = row
+    api = W.native_api()
+    n, fvalues, supplied = shape[4], "fvalues" in call, "noise" in call
+    for knob, value in env.items():
+        monkeypatch.setenv(knob, value)
+    model = engine.compile_model(build(api, shape), None, "pathwise")
+    assert tuple(model.launch_plan(n, noise=supplied, want_fvalues=fvalues)) == names
+    kw = {}
+    if supplied:
+        kw["noise"] = {"weights": np.random.RandomState(7).standard_normal((n, 1, shape[3], shape[2])).astype(np.float32)}
+    if (shape, supplied) not in _f32_reference:
+        monkeypatch.setenv("BSVI_DENSE_XGEMM", "0")
+        plain = engine.compile_model(build(api, shape), None, "pathwise")
+        assert plain.data_path() == "f32"
+        _f32_reference[(shape, supplied)] = outputs(plain, n, **kw)
+    ref = _f32_reference[(shape, supplied)]
+    if fvalues:
+        got = outputs(model, n, **kw)
+    else:
+        res = model.evaluate(n, seed=13, offset=2, want_indices=True, **kw)
+        torch.cuda.synchronize()
+        got = dict(loss=float(res["loss"].item()), grads=res["grads"].cpu().numpy().astype(np.float64), idx=res["indices"].cpu().numpy())
+    assert np.array_equal(got["idx"], ref["idx"])
+    fscale, gscale = np.abs(ref["f"]).max(), max(np.abs(ref["grads"]).max(), 1e-3)
+    if fvalues:
+        assert np.abs(got["f"] - ref["f"]).max() <= 2e-5 * fscale
+    assert abs(got["loss"] - ref["loss"]) <= 2e-5 * abs(ref["loss"])
+    assert np.abs(got["grads"] - ref["grads"]).max() <= 5e-5 * gscale + 1e-6
+
+
 def test_fused_training_walks_the_trajectory_of_the_six_launch_sequence(monkeypatch):
     api = W.native_api()
     shape = (256, 64, 64, 10, 128)
