@@ -36,6 +36,7 @@ NO_BIAS = 0xFFFFFFFF
 MAX_LAYERS = 8                                                         # BNN_MAX_LAYERS (csrc/bnn_kernel.inc)
 MIDDLE_PATHS = ("mid_gen", "upper_gen", "upper_lds", "upper_mem")      # bsvi_bnn_select::BnnMiddle (csrc/bnn_select.h)
 PREDICT_PATHS = ("global", "lds")                                      # bsvi_bnn_predict_lds
+PRIOR_KINDS = {D.DIST_NORMAL: "normal", D.DIST_LAPLACE: "laplace", D.DIST_CAUCHY: "cauchy"}      # bsvi_bnn_set_row_priors (BSVI_DIST_*)
 
 
 class BnnProgram:
@@ -49,6 +50,7 @@ class BnnProgram:
                  likelihood=("categorical", "bernoulli", "normal")[self.likelihood], latents=[t["name"] for t in self.tensors])
         if self.likelihood == LIK_NORMAL:
             s["scale"] = "learnable" if self.scale_learnable else "constant"
+        s["priors"] = {t["name"]: t.get("prior", "normal") for t in self.tensors}
         return s
 
 
@@ -184,8 +186,10 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     if others or sorted(names) != sorted(v.name for v in q_random):
         raise LoweringError("bnn path: every latent of the network needs a Normal posterior of the same name, and nothing else may be latent")
     for v in latents:
-        if not _is_random(v) or v.distribution.kind != D.DIST_NORMAL:
-            raise LoweringError("bnn path: weights and biases must be Normal variables")
+        # (loc / scale families on the whole real line: a Normal posterior covers their support — LogNormal, Beta and the rest do not)
+        if not _is_random(v) or v.distribution.kind not in PRIOR_KINDS:
+            raise LoweringError("bnn path: weights and biases must be Normal, Laplace or Cauchy variables: the prior of %r is %s"
+                                % (v.name, type(getattr(v, "distribution", None)).__name__.replace("Distribution", "") or "no distribution"))
     labels_var = k.dataset
 
     def minibatch_source(v, what):
@@ -243,7 +247,7 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
         for ent in (ql, qs, pl, ps):
             if ent[2] not in (1, size):
                 raise LoweringError("bnn path: a parameter of %r has an unsupported shape" % v.name)
-        tensors.append(dict(name=v.name, row0=row0, rows=shape[1], cols=shape[2], size=size))
+        tensors.append(dict(name=v.name, row0=row0, rows=shape[1], cols=shape[2], size=size, prior=PRIOR_KINDS[v.distribution.kind]))
         entries.append((ql, qs, pl, ps))
         row0 += size
     R = row0
@@ -288,6 +292,9 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     prog.uniform = uni
     prog.consts = np.concatenate(L.consts) if L.consts else np.zeros(0, np.float32)
     prog.row_uniform = row_uniform
+    # the prior of every row (bsvi_bnn_set_row_priors): one kind per tensor
+    kind_of = {name: kind for kind, name in PRIOR_KINDS.items()}
+    prog.row_prior = np.concatenate([np.full(t["size"], kind_of[t["prior"]], dtype=np.uint8) for t in tensors])
     prog.layers, prog.tensors, prog.n_rows = layers, tensors, R
     prog.n_features, prog.n_classes, prog.dataset_size, prog.batch_size = P, width, DS, int(ind_x.batch_size)
     prog.likelihood = lik
@@ -382,6 +389,9 @@ class CompiledBnn:
         else:
             native.check(lib.bsvi_bnn_create(C.byref(d), C.byref(handle)))
         self.handle = handle
+        row_prior = np.ascontiguousarray(getattr(p, "row_prior", np.zeros(0)), dtype=np.uint8)
+        if (row_prior != D.DIST_NORMAL).any():             # (without the call every row is Normal)
+            native.check(lib.bsvi_bnn_set_row_priors(handle, row_prior.ctypes.data_as(C.c_void_p), row_prior.size))
         self._exact_data = bool(lib.bsvi_bnn_exact_data(handle))
         dev = self.device
         self.n_params = p.n_params

@@ -32,6 +32,8 @@
 //   bnn_row_sums (its last part) / bnn_epilogue / bnn_uniform_grads / dense_param_kernel      closed-form prior and entropy terms, the value, chain rule
 // The two products carry the flops (2 x 2 N H_1 P B); everything else is elementwise or tiny and written for clarity.
 
+#include <atomic>
+
 #include "bnn_select.h"
 
 constexpr uint32_t BNN_MAX_LAYERS = 8;
@@ -74,6 +76,9 @@ struct BParams {
     float* sigt;            // [C][B_pad][n_pad]
     float* gsig;            // [C][n_pad]
     double* gsd;            // [C]
+    // the prior of every row (bsvi_bnn_set_row_priors): BSVI_DIST_NORMAL | _LAPLACE | _CAUCHY, one byte per row, padded with Normal to
+    // a whole quad.  Read by the MIXED instantiations of bnn_draw and bnn_row_sums alone: a model whose rows are all Normal never looks
+    const uint8_t* row_kind;
 };
 
 __device__ __forceinline__ float bnn_act(uint32_t act, float v) {
@@ -118,6 +123,15 @@ __device__ __forceinline__ double bnn_uniform_value_d(const BParams& Q, uint32_t
     default: break;
     }
     return (double)e.a + (double)e.b * g;
+}
+
+// the per-sample part of log p(w) of a row in u = (w - mu0) / s0, by select (the kinds differ across the lanes of bnn_draw); the
+// sample-independent part is bnn_row_terms' / bnn_row_terms_mixed's
+// (log(1 + u^2) by the hardware logarithm: every lane evaluates all three, and log1pf's polynomial alone doubled the kernel's time at
+//  784-20-10; the sum 1 + u^2 rounds to 6e-8 absolute, the size of the rounding of the Normal's -u^2 / 2 at u ~ 1)
+__device__ __forceinline__ float bnn_prior_value(const uint32_t kind, const float u) {
+    const float vn = -0.5f * u * u, vl = -fabsf(u), vc = -__logf(1.0f + u * u);
+    return kind == BSVI_DIST_LAPLACE ? vl : (kind == BSVI_DIST_CAUCHY ? vc : vn);
 }
 
 // the normals of rows 4g .. 4g+3 of sample n: the dense path's definition (dense_eps4), or the caller's
@@ -186,6 +200,9 @@ __global__ void __launch_bounds__(256) bnn_head_gather(const BParams Q, const ui
 // 8-byte stores along p, the small tensors as consecutive floats; the per-sample prior and log q sums of the chunk by a wave sum.
 // grid: row_chunks x ceil(n_pad / 4), block 256 (round 6: four samples per workgroup instead of 64 k one-wave workgroups, and the row
 // parameters of a quad by 16- / 8-byte loads where their arrays' offsets allow)
+// MIXED: some row's prior is Laplace or Cauchy.  The lanes run along the rows, and a quad of the small tensors can straddle two
+// tensors, so the kind is per row and the value is picked by select; MIXED = false is the kernel of the all-Normal models as it was.
+template <bool MIXED>
 __global__ void __launch_bounds__(256) bnn_draw(const BParams Q) {
     const uint32_t chunk = blockIdx.x, lane = threadIdx.x & 63u, n = blockIdx.y * 4u + (threadIdx.x >> 6), g = chunk * 64u + lane;
     if (n >= Q.n_pad) return;
@@ -201,6 +218,7 @@ __global__ void __launch_bounds__(256) bnn_draw(const BParams Q) {
         float rp[4][4];
         // (array a starts a * R floats into rowp: 16-byte loads where that is a multiple of four floats, 8-byte loads where of two)
         const bool whole = 4u * g + 3u < Q.R, base16 = ((uintptr_t)Q.rowp & 15u) == 0u;
+        const uint32_t kinds = MIXED ? *reinterpret_cast<const uint32_t*>(Q.row_kind + 4u * (size_t)g) : 0u;      // (a byte per row)
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
             const size_t at = (size_t)a * Q.R + 4u * g;
@@ -225,7 +243,8 @@ __global__ void __launch_bounds__(256) bnn_draw(const BParams Q) {
             w4[j] = live ? w : 0.0f;
             if (live) {
                 const float u = (w - mu0) / s0;
-                pv += -0.5f * u * u;
+                if (MIXED) pv += bnn_prior_value((kinds >> (8 * j)) & 0xFFu, u);
+                else pv += -0.5f * u * u;
                 qv += -0.5f * e[j] * e[j];
                 if (Q.noise_out) Q.noise_out[(size_t)r * Q.n_local + n] = e[j];
             }
@@ -477,8 +496,32 @@ __device__ __forceinline__ void bnn_row_terms(const BParams& Q, const uint32_t r
     qconst = -log(sd) - 0.91893853320467274178;
 }
 
+// ... of a row whose prior is Laplace or Cauchy: no closed form in sum eps, sum eps^2 — the per-sample sums of bnn_row_sums<true>,
+//     T0 = sum_n a_n t_n,  T1 = sum_n a_n eps_n t_n,      t = d log p / d w
+// and T2 = sum_n a_n d log p / d s0 from the two: log p = g(u) - log s0 with u = (w - mu0) / s0 for either family, so
+// d log p / d s0 = -u t - 1 / s0, and with w - mu0 = (mu - mu0) + s eps:   T2 = -((mu - mu0) T0 + s T1 + N) / s0
+// (the same summands regrouped: no accumulators and no per-sample arithmetic of its own)
+__device__ __forceinline__ void bnn_row_terms_mixed(const BParams& Q, const uint32_t r, const uint32_t kind, const float ds_lik, const float dmu_lik,
+                                                    const float T0, const float T1, const float N, double& hconst, double& qconst) {
+    const float mu = Q.rowp[r], s = Q.rowp[Q.R + r], mu0 = Q.rowp[2 * (size_t)Q.R + r], s0 = Q.rowp[3 * (size_t)Q.R + r];
+    const float T2 = -((mu - mu0) * T0 + s * T1 + N) / s0;
+    Q.rowg[r] = dmu_lik + Q.prior_weight * T0;
+    Q.rowg[Q.R + r] = ds_lik + Q.prior_weight * T1 + Q.entropy_weight * N / s;
+    Q.rowg[2 * (size_t)Q.R + r] = -Q.prior_weight * T0;
+    Q.rowg[3 * (size_t)Q.R + r] = Q.prior_weight * T2;
+    // (double precision, for bnn_row_terms' reason)  Laplace: -log(2 s0); Cauchy: -log(pi) - log(s0)
+    const double sd = bnn_uniform_value_d(Q, Q.row_uniform[Q.R + r]), s0d = bnn_uniform_value_d(Q, Q.row_uniform[3 * (size_t)Q.R + r]);
+    const double pconst = kind == BSVI_DIST_LAPLACE ? -log(2.0 * s0d) : -1.14472988584940017414 - log(s0d);
+    hconst = (double)Q.prior_weight * pconst + (double)Q.entropy_weight * (1.41893853320467274178 + log(sd));
+    qconst = -log(sd) - 0.91893853320467274178;
+}
+
 // per row quad (one wave, lanes = samples): sum_n eps G, sum_n G, sum_n eps, sum_n eps^2, then the rows' gradients and constants.  grid: ceil(quads / 4), block 256: a wave per quad
 // (round 6: four quads per workgroup, as bnn_draw)
+// MIXED: eight more accumulators, T0 and T1 of bnn_row_terms_mixed for each of the four rows, from w and u recomputed as bnn_draw
+// computed them on the eps redrawn here anyway — no pass over memory of their own, the same wave_sum order; a Normal row of such a model
+// keeps its closed form.  MIXED = false is the kernel of the all-Normal models as it was.
+template <bool MIXED>
 __global__ void __launch_bounds__(256) bnn_row_sums(const BParams Q) {
     const uint32_t quads = (Q.R + 3u) / 4u, g = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u, r0 = 4u * g;
     if (g >= quads) return;
@@ -486,6 +529,19 @@ __global__ void __launch_bounds__(256) bnn_row_sums(const BParams Q) {
 #pragma unroll
     for (int k = 0; k < 16; ++k) acc[k] = 0.0f;
     float asum = 0.0f;
+    float tacc[8], rp[4][4], is0[4];
+    uint32_t kinds = 0u;
+    if (MIXED) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) tacc[k] = 0.0f;
+        kinds = *reinterpret_cast<const uint32_t*>(Q.row_kind + (size_t)r0);
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) rp[a][j] = (r0 + j < Q.R) ? Q.rowp[(size_t)a * Q.R + r0 + j] : 1.0f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) is0[j] = 1.0f / rp[3][j];          // (once per row: the loop below multiplies)
+    }
     for (uint32_t n = lane; n < Q.n_local; n += 64u) {
         float e[4];
         bnn_eps4(Q, n, g, e);
@@ -503,10 +559,22 @@ __global__ void __launch_bounds__(256) bnn_row_sums(const BParams Q) {
                 G = Q.gsm[(size_t)n * Q.Rs + (r - Q.R1)];
             }
             acc[j] += e[j] * G; acc[4 + j] += G; acc[8 + j] += aw * e[j]; acc[12 + j] += aw * (e[j] * e[j]);
+            if (MIXED) {
+                const uint32_t kind = (kinds >> (8 * j)) & 0xFFu;
+                const float w = rp[0][j] + rp[1][j] * e[j], dw = w - rp[2][j], u = dw * is0[j];
+                // Laplace: t = -sign(u) / s0 (sign(0) = 0, as torch's abs backward);  Cauchy: t = -2 u / ((1 + u^2) s0)
+                const float sg = dw > 0.0f ? 1.0f : (dw < 0.0f ? -1.0f : 0.0f);
+                const float t = (kind == BSVI_DIST_LAPLACE ? -sg : (kind == BSVI_DIST_CAUCHY ? -2.0f * u / (1.0f + u * u) : 0.0f)) * is0[j];
+                tacc[j] += aw * t; tacc[4 + j] += aw * (e[j] * t);
+            }
         }
     }
 #pragma unroll
     for (int k = 0; k < 16; ++k) acc[k] = wave_sum(acc[k]);
+    if (MIXED) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) tacc[k] = wave_sum(tacc[k]);
+    }
     const float Nw = Q.f_weight ? wave_sum(asum) : (float)Q.n_local;
     if (lane < 16u) {
         const uint32_t q = lane >> 2, j = lane & 3u;
@@ -528,7 +596,15 @@ __global__ void __launch_bounds__(256) bnn_row_sums(const BParams Q) {
             ds_lik = (lane == (uint32_t)j) ? acc[j] : ds_lik; dmu_lik = (lane == (uint32_t)j) ? acc[4 + j] : dmu_lik;
             S1 = (lane == (uint32_t)j) ? acc[8 + j] : S1; S2 = (lane == (uint32_t)j) ? acc[12 + j] : S2;
         }
-        bnn_row_terms(Q, r, ds_lik, dmu_lik, S1, S2, Nw, hconst, qconst);
+        uint32_t kind = BSVI_DIST_NORMAL;
+        float T0 = 0.0f, T1 = 0.0f;
+        if (MIXED) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { T0 = (lane == (uint32_t)j) ? tacc[j] : T0; T1 = (lane == (uint32_t)j) ? tacc[4 + j] : T1; }
+            kind = (kinds >> (8u * lane)) & 0xFFu;
+        }
+        if (MIXED && kind != BSVI_DIST_NORMAL) bnn_row_terms_mixed(Q, r, kind, ds_lik, dmu_lik, T0, T1, Nw, hconst, qconst);
+        else bnn_row_terms(Q, r, ds_lik, dmu_lik, S1, S2, Nw, hconst, qconst);
     }
     double h4 = 0.0, q4 = 0.0;
 #pragma unroll
@@ -626,6 +702,9 @@ struct bsvi_bnn {
     uint32_t LC = 1;             // targets per dataset row: one label, or C for the Normal likelihood
     uint32_t scale_u = 0, scale_stride = 0;      // Normal likelihood: sigma of output c is uniform entry scale_u + c * scale_stride
     bool scale_learn = false;    // ... parameter entries (bsvi_bnn_create_normal_learnable), else constants
+    uint8_t* row_kind = nullptr; // the prior of every row, in the blob (all Normal until bsvi_bnn_set_row_priors)
+    bool mixed = false;          // some row is Laplace or Cauchy: the MIXED instantiations of bnn_draw / bnn_row_sums
+    mutable std::atomic<bool> launched{false};      // a launch was made: the priors stay as they are
     uint64_t act_floats = 0, delta_floats = 0;      // per (sample, minibatch row)
     uint32_t act_off[BNN_MAX_LAYERS] = {};
     bool exact = false;
@@ -1151,15 +1230,17 @@ static int bnn_create(const bsvi_bnn_desc* desc, const bool normal, const uint32
         std::vector<uint32_t> at(ur_ptr.begin(), ur_ptr.end() - 1);
         for (size_t i = 0; i < 4 * (size_t)R; ++i) if (desc->row_uniform[i] < desc->n_uniform_grad) ur_item[at[desc->row_uniform[i]]++] = (uint32_t)i;
     }
-    const size_t sizes[9] = {(size_t)desc->n_uniform * sizeof(bsvi_uniform_entry), (size_t)desc->n_consts * 4, ((size_t)desc->n_params + 1) * 4,
+    // (the rows' prior kinds, a byte each padded to a whole quad, behind everything else: all Normal until bsvi_bnn_set_row_priors)
+    const std::vector<uint8_t> kinds(((size_t)R + 3) / 4 * 4, (uint8_t)BSVI_DIST_NORMAL);
+    const size_t sizes[10] = {(size_t)desc->n_uniform * sizeof(bsvi_uniform_entry), (size_t)desc->n_consts * 4, ((size_t)desc->n_params + 1) * 4,
                              (size_t)desc->n_uniform_grad * 4, 4 * (size_t)R * 4, ur_ptr.size() * 4, ur_item.size() * 4,
-                             (size_t)desc->dataset_size * desc->n_features * 4, (size_t)desc->dataset_size * p->LC * 4};
-    const void* srcs[9] = {desc->uniform, desc->consts, desc->param_uniform_ptr, desc->param_uniform_idx, desc->row_uniform, ur_ptr.data(),
-                           ur_item.data(), desc->dataset, desc->labels};
-    size_t offs[9], total = 0;
-    for (int i = 0; i < 9; ++i) { offs[i] = total; total += align_up(sizes[i], 256); }
+                             (size_t)desc->dataset_size * desc->n_features * 4, (size_t)desc->dataset_size * p->LC * 4, kinds.size()};
+    const void* srcs[10] = {desc->uniform, desc->consts, desc->param_uniform_ptr, desc->param_uniform_idx, desc->row_uniform, ur_ptr.data(),
+                           ur_item.data(), desc->dataset, desc->labels, kinds.data()};
+    size_t offs[10], total = 0;
+    for (int i = 0; i < 10; ++i) { offs[i] = total; total += align_up(sizes[i], 256); }
     std::vector<char> host(total + 256, 0);
-    for (int i = 0; i < 9; ++i) if (sizes[i] && srcs[i]) memcpy(&host[offs[i]], srcs[i], sizes[i]);
+    for (int i = 0; i < 10; ++i) if (sizes[i] && srcs[i]) memcpy(&host[offs[i]], srcs[i], sizes[i]);
     hipError_t e = hipMalloc(&p->dev_blob, host.size());
     if (e == hipSuccess) e = hipMemcpy(p->dev_blob, host.data(), host.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) { if (p->dev_blob) (void)hipFree(p->dev_blob); delete p; return fail(BSVI_ERR_HIP, std::string("bsvi_bnn_create: ") + hipGetErrorString(e)); }
@@ -1167,7 +1248,7 @@ static int bnn_create(const bsvi_bnn_desc* desc, const bool normal, const uint32
     p->uniform = (const bsvi_uniform_entry*)(base + offs[0]); p->consts = (const float*)(base + offs[1]);
     p->pu_ptr = (const uint32_t*)(base + offs[2]); p->pu_idx = (const uint32_t*)(base + offs[3]);
     p->row_uniform = (const uint32_t*)(base + offs[4]); p->ur_ptr = (const uint32_t*)(base + offs[5]); p->ur_item = (const uint32_t*)(base + offs[6]);
-    p->dataset = (const float*)(base + offs[7]); p->labels = (const float*)(base + offs[8]);
+    p->dataset = (const float*)(base + offs[7]); p->labels = (const float*)(base + offs[8]); p->row_kind = (uint8_t*)(base + offs[9]);
     {
         const size_t wl_bytes = bsvi_bnn_select::upper_lds_bytes(p->Rs, p->act_floats);
         int dev = 0, n_cu = 0;
@@ -1190,6 +1271,23 @@ extern "C" int bsvi_bnn_create_normal(const bsvi_bnn_desc* desc, uint32_t scale_
 
 extern "C" int bsvi_bnn_create_normal_learnable(const bsvi_bnn_desc* desc, uint32_t scale_uniform, uint32_t scale_stride, bsvi_bnn** out) {
     return bnn_create(desc, true, scale_uniform, scale_stride, out, true);
+}
+
+// the prior of every row: Normal (what every row is without this call), Laplace or Cauchy.  Before the first launch only — the
+// launches choose their instantiations of bnn_draw / bnn_row_sums from what stands here
+extern "C" int bsvi_bnn_set_row_priors(bsvi_bnn* p, const uint8_t* kinds, uint32_t n_rows) {
+    if (!p || !kinds) return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_row_priors: null argument");
+    if (n_rows != p->R) return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_row_priors: n_rows is not the model's number of rows");
+    if (p->launched.load()) return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_row_priors: the model was launched already (set the priors before the first launch)");
+    bool mixed = false;
+    for (uint32_t r = 0; r < n_rows; ++r) {
+        if (kinds[r] != BSVI_DIST_NORMAL && kinds[r] != BSVI_DIST_LAPLACE && kinds[r] != BSVI_DIST_CAUCHY)
+            return fail(BSVI_ERR_UNSUPPORTED, "bsvi_bnn_set_row_priors: the prior of a row is Normal, Laplace or Cauchy");
+        mixed = mixed || kinds[r] != BSVI_DIST_NORMAL;
+    }
+    HIP_TRY(hipMemcpy(p->row_kind, kinds, n_rows, hipMemcpyHostToDevice));      // (the pad bytes of the last quad stay Normal)
+    p->mixed = mixed;
+    return BSVI_OK;
 }
 
 extern "C" void bsvi_bnn_destroy(bsvi_bnn* p) {
@@ -1297,14 +1395,17 @@ static int bnn_fill(const bsvi_bnn* p, const bsvi_bnn_args* a, BParams& Q, BnnLa
     Q.sums = (float*)(ws + L.sums); Q.rowg = (float*)(ws + L.rowg); Q.hpart = (double*)(ws + L.hpart); Q.partial = (float*)(ws + L.partial);
     Q.fs = (float*)(ws + L.fs); Q.row_chunks = L.row_chunks;
     if (p->scale_learn) { Q.sigt = (float*)(ws + L.sigt); Q.gsig = (float*)(ws + L.gsig); Q.gsd = (double*)(ws + L.gsd); }
+    Q.row_kind = p->row_kind;
     return BSVI_OK;
 }
 
 static int bnn_launch(const bsvi_bnn* p, const BParams& Q, const BnnLayout& L, hipStream_t s) {
     const uint32_t head_n = std::max(Q.R, Q.B_pad);
     const uint32_t head_blocks = (head_n + 255) / 256, gy = (std::max(Q.Kp, Q.P_ld) + 255) / 256;
+    p->launched.store(true);
     hipLaunchKernelGGL(bnn_head_gather, dim3(Q.B_pad * gy + head_blocks), dim3(256), 0, s, Q, gy, head_blocks);
-    hipLaunchKernelGGL(bnn_draw, dim3(L.row_chunks, (Q.n_pad + 3u) / 4u), dim3(256), 0, s, Q);
+    if (p->mixed) hipLaunchKernelGGL(bnn_draw<true>, dim3(L.row_chunks, (Q.n_pad + 3u) / 4u), dim3(256), 0, s, Q);
+    else hipLaunchKernelGGL(bnn_draw<false>, dim3(L.row_chunks, (Q.n_pad + 3u) / 4u), dim3(256), 0, s, Q);
     int rc;
     const bool mid = bnn_mid_ready(p);
     if (mid) rc = bsvi_xgemm_nt_t(Q.Xb_bf, nullptr, Q.Wp, (long)Q.NC * Q.Kp, Q.a1T, (int)Q.B_pad, (int)Q.B_pad, (int)Q.NC, (int)Q.Kp, s);      // a1 as [(h, n)][b]
@@ -1345,7 +1446,8 @@ static int bnn_launch(const bsvi_bnn* p, const BParams& Q, const BnnLayout& L, h
     if (Q.exact) rc = bsvi_xgemm_nt(Q.XbT_bf, nullptr, Q.dlogp, (long)Q.NC * Q.B_pad, Q.GT, (int)Q.NC, (int)Q.P, (int)Q.NC, (int)Q.B_pad, s);
     else rc = bsvi_gemm_f32(1, Q.da1T, (int)Q.B_pad, Q.Xb, (int)Q.P_ld, Q.GT, (int)Q.P_ld, (int)Q.NC, (int)Q.P, (int)Q.B_pad, s);
     if (rc) return rc;
-    hipLaunchKernelGGL(bnn_row_sums, dim3(((Q.R + 3) / 4 + 3) / 4), dim3(256), 0, s, Q);
+    if (p->mixed) hipLaunchKernelGGL(bnn_row_sums<true>, dim3(((Q.R + 3) / 4 + 3) / 4), dim3(256), 0, s, Q);
+    else hipLaunchKernelGGL(bnn_row_sums<false>, dim3(((Q.R + 3) / 4 + 3) / 4), dim3(256), 0, s, Q);
     hipLaunchKernelGGL(bnn_epilogue, dim3(1), dim3(1024), 0, s, Q, L.row_blocks);
     if (Q.n_uniform_grad) hipLaunchKernelGGL(bnn_uniform_grads, dim3((Q.n_uniform_grad + 255) / 256), dim3(256), 0, s, Q);
     HIP_TRY(hipGetLastError());
@@ -1653,6 +1755,8 @@ extern "C" int bsvi_bnn_predict(const bsvi_bnn* p, const bsvi_bnn_predict_args* 
     Q.pv_part = (float*)(ws + L.part); Q.qv_part = Q.pv_part + (size_t)L.row_chunks * L.n_pad;
     Q.Xb = (float*)(ws + L.X); Q.Xb_bf = (uint16_t*)(ws + L.X);
     Q.row_chunks = L.row_chunks;
+    Q.row_kind = p->row_kind;
+    p->launched.store(true);
 
     BnnPredict V;
     memset(&V, 0, sizeof V);
@@ -1690,7 +1794,9 @@ extern "C" int bsvi_bnn_predict(const bsvi_bnn* p, const bsvi_bnn_predict_args* 
     }
     const uint32_t head_n = std::max(Q.R, Q.C);
     hipLaunchKernelGGL(bnn_predict_head, dim3((head_n + 255) / 256), dim3(256), 0, s, Q, V);
-    hipLaunchKernelGGL(bnn_draw, dim3(L.row_chunks, (Q.n_pad + 3u) / 4u), dim3(256), 0, s, Q);
+    // (the prior partials of the draw are written and never read: the MIXED instantiation all the same, so that the two stay one kernel each)
+    if (p->mixed) hipLaunchKernelGGL(bnn_draw<true>, dim3(L.row_chunks, (Q.n_pad + 3u) / 4u), dim3(256), 0, s, Q);
+    else hipLaunchKernelGGL(bnn_draw<false>, dim3(L.row_chunks, (Q.n_pad + 3u) / 4u), dim3(256), 0, s, Q);
     HIP_TRY(hipGetLastError());
     const uint32_t gy = (std::max(Q.Kp, Q.P_ld) + 255) / 256;
     for (uint32_t m0 = 0; m0 < a->n_rows; m0 += L.rows_pass) {

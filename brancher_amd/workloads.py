@@ -781,6 +781,28 @@ def _bnn_activations(activations, activation, n_hidden_layers):
     return list(activations)
 
 
+def _bnn_prior(api, prior, prior_loc, prior_scale):
+    """the prior of the two Bayesian-neural-network builders' tensors: one of "normal" / "laplace" / "cauchy" for every tensor, or a
+    dict by tensor name ("weights1", "b1", ...; tensors it does not name are Normal) -> (name, shape) -> the prior variable.
+    Without the builders' new keywords that is `NormalVariable(zeros, prior_scale * ones, name)` as it always was — whose auto-created
+    roots `<name>_loc` / `<name>_scale` are, by the reference's name-collision rule, the POSTERIOR's parameters of the same names.  With
+    them the prior's loc and scale are roots of their own names, `<name>_prior_loc` / `<name>_prior_scale`: constants of the model,
+    so that the prior asked for is the prior scored."""
+    classes = {"normal": api.NormalVariable, "laplace": api.LaplaceVariable, "cauchy": api.CauchyVariable}
+    kinds = list(prior.values()) if isinstance(prior, dict) else [prior]
+    if any(k not in classes for k in kinds):
+        raise ValueError("prior is 'normal', 'laplace' or 'cauchy', or a dict of them by tensor name")
+    as_before = all(k == "normal" for k in kinds) and float(prior_loc) == 0.0
+
+    def make(name, shape):
+        if as_before:
+            return api.NormalVariable(np.zeros(shape), prior_scale * np.ones(shape), name)
+        cls = classes[prior.get(name, "normal") if isinstance(prior, dict) else prior]
+        return cls(api.RootVariable(prior_loc + np.zeros(shape), name + "_prior_loc"),
+                   api.RootVariable(prior_scale * np.ones(shape), name + "_prior_scale"), name)
+    return make
+
+
 def _bnn_features(rng, data, dataset_size, n_features):
     if data == "integers":
         return rng.randint(-3, 4, size=(dataset_size, n_features, 1)).astype(np.float32)
@@ -791,7 +813,7 @@ def _bnn_features(rng, data, dataset_size, n_features):
 
 def build_bayesian_neural_network(api, dataset_size=48, batch_size=30, n_features=784, n_hidden=20, n_classes=10, seed=0,
                                   prior_scale=10., q_scale=0.2, q_scale1=None, q_loc_scale=0.0, pixels="uint8",
-                                  activation="tanh", hidden2=0, widths=None, activations=None, teacher=None):
+                                  activation="tanh", hidden2=0, widths=None, activations=None, teacher=None, prior="normal", prior_loc=0.):
     """`tests/test_MNIST_bayesian_neural_network.py:20-60` of the reference: a one-hidden-layer network whose weight matrices AND
     biases are latent — weights1 [H, P], b1 [H, 1], weights2 [C, H], b2 [C, 1], priors N(0, 10), a mean-field Normal posterior
     over all four (scale 0.2) — `tanh(matmul(weights1, x) + b1)`, `matmul(weights2, hidden) + b2` as the logits of an observed
@@ -804,8 +826,12 @@ def build_bayesian_neural_network(api, dataset_size=48, batch_size=30, n_feature
     depth); activations: one name per hidden layer (default: `activation` everywhere).  pixels="integers" / "normal": the features of
     `build_bnn_regression` (-3 .. 3, exactly bf16 | standard normal).  teacher: an integer — the labels are what a fixed random linear
     map of the centred features (drawn from that seed, whatever `seed` is) ranks highest, so that there is something to learn and a
-    second build with another `seed` is held-out data of the same task (examples/bnn_predict.py); None: uniformly random labels."""
+    second build with another `seed` is held-out data of the same task (examples/bnn_predict.py); None: uniformly random labels.
+    prior: "normal" | "laplace" | "cauchy" — the family of every weight's and bias's prior (loc prior_loc, scale prior_scale), or a dict
+    by tensor name ("weights1", "b1", ...: the tensors it leaves out are Normal); its parameters are then constants of the model under
+    names of their own (`_bnn_prior`).  Without the two keywords every model is built draw for draw as before."""
     BF = api.BF
+    prior_of = _bnn_prior(api, prior, prior_loc, prior_scale)
     n_features, n_classes, widths = _bnn_widths(widths, n_features, [n_hidden] + ([hidden2] if hidden2 else []), n_classes)
     if pixels in ("integers", "normal"):
         rng = np.random.RandomState(seed)
@@ -826,8 +852,8 @@ def build_bayesian_neural_network(api, dataset_size=48, batch_size=30, n_feature
     layer, q_vars = x, []
     for l in range(1, len(widths)):
         rows, cols = widths[l], widths[l - 1]
-        b = api.NormalVariable(np.zeros((rows, 1)), prior_scale * np.ones((rows, 1)), "b%d" % l)
-        w = api.NormalVariable(np.zeros((rows, cols)), prior_scale * np.ones((rows, cols)), "weights%d" % l)
+        b = prior_of("b%d" % l, (rows, 1))
+        w = prior_of("weights%d" % l, (rows, cols))
         pre = BF.matmul(w, layer) + b
         layer = getattr(BF, acts[l - 1])(pre) if l + 1 < len(widths) else pre
         sw = q_scale1 if (l == 1 and q_scale1 is not None) else q_scale
@@ -846,7 +872,7 @@ def build_bayesian_neural_network(api, dataset_size=48, batch_size=30, n_feature
 
 def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_hidden=9, n_outputs=1, hidden2=0, activation="tanh",
                          sigma=0.5, data="integers", bias=True, seed=0, prior_scale=2., q_scale=0.1, q_scale1=None, q_loc_scale=0.5,
-                         widths=None, activations=None, learnable_sigma=False, sigma_init=None):
+                         widths=None, activations=None, learnable_sigma=False, sigma_init=None, prior="normal", prior_loc=0.):
     """The regression model of the Bayesian-neural-network family: the network of `build_bayesian_neural_network` (latent weight
     matrices and biases under a mean-field Normal posterior) as the loc of an observed Normal,
     `y ~ NormalVariable(matmul(weights2, act(matmul(weights1, x) + b1)) + b2, sigma)`, the targets [DS, C, 1] an EmpiricalVariable that
@@ -859,8 +885,10 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
     depth); activations: one name per hidden layer (default: `activation` everywhere).  learnable_sigma: True — the reference's idiom,
     `NormalVariable(chain, sigma, "y", learnable=True)`: a learnable root `y_scale` behind a softplus in the joint model's parameter
     group; "exp" — `BF.exp` of a learnable root `y_log_scale`; the model's sigma then starts at sigma_init (one number or one per
-    output; default: the teacher's sigma).  Without the keyword every model is built draw for draw as before."""
+    output; default: the teacher's sigma).  prior / prior_loc: as for `build_bayesian_neural_network` (the Bayesian lasso is
+    prior="laplace").  Without these keywords every model is built draw for draw as before."""
     BF = api.BF
+    prior_of = _bnn_prior(api, prior, prior_loc, prior_scale)
     if learnable_sigma not in (False, True, "exp"):
         raise ValueError("learnable_sigma is False, True (the reference's flag) or \"exp\"")
     if sigma_init is not None and not learnable_sigma:
@@ -893,10 +921,10 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
     for l in range(1, len(widths)):
         rows, cols = widths[l], widths[l - 1]
         sw = q_scale1 if l == 1 else q_scale
-        w = api.NormalVariable(np.zeros((rows, cols)), prior_scale * np.ones((rows, cols)), "weights%d" % l)
+        w = prior_of("weights%d" % l, (rows, cols))
         pre = BF.matmul(w, layer)
         if bias:
-            pre = pre + api.NormalVariable(np.zeros((rows, 1)), prior_scale * np.ones((rows, 1)), "b%d" % l)
+            pre = pre + prior_of("b%d" % l, (rows, 1))
             q_vars.append(api.NormalVariable(q_loc_scale * q_scale * rng.normal(0., 1., (rows, 1)), q_scale * np.ones((rows, 1)),
                                              "b%d" % l, learnable=True))
         layer = getattr(BF, acts[l - 1])(pre) if l + 1 < len(widths) else pre

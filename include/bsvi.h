@@ -612,6 +612,14 @@ int bsvi_bnn_create_normal(const bsvi_bnn_desc* desc, uint32_t scale_uniform, ui
  * order and on top of what the entry's rows contribute — one entry may be a prior scale and sigma; the chain rule through the
  * transform, finalize and the optimizer step are those of every other entry.  No struct changes, the ABI version stays. */
 int bsvi_bnn_create_normal_learnable(const bsvi_bnn_desc* desc, uint32_t scale_uniform, uint32_t scale_stride, bsvi_bnn** out);
+/* The PRIOR of every latent row: kinds[r] is BSVI_DIST_NORMAL, BSVI_DIST_LAPLACE or BSVI_DIST_CAUCHY (the reference's LaplaceVariable /
+ * CauchyVariable weights and biases; another kind is BSVI_ERR_UNSUPPORTED), its loc and scale the row's prior loc / prior scale entries
+ * as for the Normal.  Valid after any of the three create calls and before the first launch (bsvi_bnn_fwd_bwd, bsvi_bnn_step,
+ * bsvi_bnn_predict): a wrong n_rows, a null pointer or a call after a launch is BSVI_ERR_INVALID.  Without the call every row is Normal,
+ * and such a model runs the kernels it ran.  With u = (w - mu0) / s0 a Laplace row adds  prior_weight (-|u| - log(2 s0))  to f per sample,
+ * a Cauchy row  prior_weight (-log1p(u^2) - log(pi) - log(s0));  their gradients are per-sample sums taken in a fixed order inside the
+ * launches that walk every (row, sample) anyway.  The posterior stays mean-field Normal.  No struct changes, the ABI version stays. */
+int bsvi_bnn_set_row_priors(bsvi_bnn* b, const uint8_t* kinds, uint32_t n_rows);
 void bsvi_bnn_destroy(bsvi_bnn* b);
 size_t bsvi_bnn_workspace_bytes(const bsvi_bnn* b, uint32_t n_samples_local);
 int bsvi_bnn_exact_data(const bsvi_bnn* b);
