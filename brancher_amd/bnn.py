@@ -14,7 +14,14 @@ between the layers, biases optional) — and the regression model of the same fa
 
 with sigma (one value, or [C, 1]) a constant of the model (`bsvi_bnn_create_normal`) or learnable — the reference's
 `NormalVariable(chain, 0.5, "y", learnable=True)`, or any a + b g(root) of a learnable root with g softplus / exp / sigmoid
-(`bsvi_bnn_create_normal_learnable`) —, from one layer (minibatched Bayesian linear regression) to eight.
+(`bsvi_bnn_create_normal_learnable`) —, or computed from the input by a second head on the trunk of the first (heteroscedastic regression),
+
+    loc   = BF.matmul(weights_loc, hidden) + b_loc
+    scale = a + b * g(BF.matmul(weights_scale, hidden) + b_scale)          # g softplus / exp / sigmoid, a >= 0, b > 0
+    y     = NormalVariable(loc, scale, name="y");  y.observe(targets)
+
+whose four head tensors are latents like the rest and, to the library, ONE last layer of 2 C rows (`bsvi_bnn_create_normal_heads`); from
+one layer (minibatched Bayesian linear regression) to eight.
 `dense.lower_dense` serves ONE latent matrix without a bias; this module serves the rest of the family through `bsvi_bnn_*` (include/bsvi.h, csrc/bnn_kernel.inc).  The reference's semantics are kept as on the
 dense path: priors and posteriors are matched by NAME, auto-created roots `<var>_<arg>` collide by name, no
 minibatch rescaling of the likelihood (`variables.py:849` TODO).
@@ -43,13 +50,14 @@ class BnnProgram:
     """What `lower_bnn` extracts from the graph."""
     estimator = "pathwise"
     scale_learnable = False
+    scale_head = None          # (transform, a, b) of a scale head: sigma = a + b g(second head); the last layer then has 2 C rows
 
     def summary(self):
         s = dict(kind="bnn", layers=[(l["rows"], l["cols"], l["activation"]) for l in self.layers], n_rows=self.n_rows,
                  dataset_size=self.dataset_size, batch_size=self.batch_size, n_params=self.n_params,
                  likelihood=("categorical", "bernoulli", "normal")[self.likelihood], latents=[t["name"] for t in self.tensors])
         if self.likelihood == LIK_NORMAL:
-            s["scale"] = "learnable" if self.scale_learnable else "constant"
+            s["scale"] = "head" if self.scale_head else "learnable" if self.scale_learnable else "constant"
         s["priors"] = {t["name"]: t.get("prior", "normal") for t in self.tensors}
         return s
 
@@ -125,6 +133,46 @@ def _normal_scale(L, k, links, n_outputs, joint_roots=()):
     return k0, (1 if size > 1 else 0), bool(is_param)
 
 
+def _has_matmul(e):
+    return (e.op == "call" and e.attr[0] == "matmul") or any(_has_matmul(a) for a in e.args if hasattr(a, "op"))
+
+
+def _scale_head(k, e):
+    """the scale of a Normal likelihood computed from a matmul: a + b g(second head) -> (g, a, b, the head's chain, its x), or the cause"""
+    def number(x):
+        return float(np.asarray(x.attr).reshape(-1)[0]) if x.op == "const" and np.size(x.attr) == 1 else None
+
+    def peel(x):      # x == a + b * core with numbers a, b -> (core, a, b)
+        if x.op in ("add", "sub", "mul", "truediv"):
+            l, r = x.args
+            cl, cr = number(l), number(r)
+            if cl is not None and cr is None and x.op != "truediv":
+                core, a, b = peel(r)
+                return dict(add=(core, cl + a, b), sub=(core, cl - a, -b), mul=(core, cl * a, cl * b))[x.op]
+            if cr is not None and cl is None and (x.op != "truediv" or cr != 0.0):
+                core, a, b = peel(l)
+                return dict(add=(core, a + cr, b), sub=(core, a - cr, b), mul=(core, a * cr, b * cr), truediv=(core, a / (cr or 1.), b / (cr or 1.)))[x.op]
+        return x, 0.0, 1.0
+
+    form = "a + b * g(BF.matmul(weights, hidden) [+ bias]) with g one of %s, a >= 0 and b > 0" % " / ".join(LEARNABLE_SCALE_TRANSFORMS)
+    core, a, b = peel(e)
+    if core.op != "call" or core.attr[0] not in LEARNABLE_SCALE_TRANSFORMS or len(core.args) != 1 or core.attr[1]:
+        what = "BF.%s" % core.attr[0] if core.op == "call" and isinstance(core.attr[0], str) else "the operation %r" % core.op
+        try:      # (the bare head)
+            _chain(core)
+            what = "missing"
+        except LoweringError:
+            pass
+        raise LoweringError("bnn path: the transform of the scale head of the Normal likelihood %r is %s (the scale must be %s)" % (k.name, what, form))
+    if not (a >= 0 and b > 0):
+        raise LoweringError("bnn path: the scale head of the Normal likelihood %r has a = %g, b = %g (the scale must be %s)" % (k.name, a, b, form))
+    try:
+        chain, x_var = _chain(core.args[0])
+    except LoweringError as err:
+        raise LoweringError("bnn path: the scale head of the Normal likelihood %r is not a chain of matmul layers (%s)" % (k.name, err)) from None
+    return core.attr[0], float(a), float(b), chain, x_var
+
+
 def lower_bnn(joint, posterior, estimator="pathwise"):
     # "taylor1" (gradient_estimators.py:47-56): f at the posterior's analytic means — every latent of the network is a mean-field Normal,
     # whose mean is its loc (distributions.py:137 through torch), so the program is the Pathwise one evaluated on the draw eps = 0
@@ -147,7 +195,8 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     # (a regression model whose noise scale is a latent is named as such, before the posterior of that latent is looked at)
     for v in joint._flatten():
         if _is_random(v) and v.distribution.kind == D.DIST_NORMAL and v.is_observed and getattr(v, "has_random_dataset", False) \
-                and _depends_on_latent(v.link.expressions()["scale"].expr):
+                and _depends_on_latent(v.link.expressions()["scale"].expr) and not _has_matmul(v.link.expressions()["scale"].expr):
+            # (a scale computed from a matmul is a scale head, or refused below with its own cause)
             raise LoweringError("bnn path: the scale of the Normal likelihood %r is a latent variable or computed from one "
                                 "(it must be a constant of the model)" % v.name)
     if not q_random or any(v.distribution.kind != D.DIST_NORMAL for v in q_random):
@@ -174,11 +223,32 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
         chain, x_var = _chain(links["logits"].expr)
     if len(chain) > MAX_LAYERS:
         raise LoweringError("bnn path: the network has %d layers, the kernels serve at most %d" % (len(chain), MAX_LAYERS))
+    # a scale head: sigma = a + b g(BF.matmul(weights_scale, H) [+ b_scale]) on the trunk H of the loc head
+    head = None
+    if normal and _depends_on_latent(links["scale"].expr):
+        g, ha, hb, chain_s, x_s = _scale_head(k, links["scale"].expr)
+        same = len(chain_s) == len(chain) and x_s is x_var and all(
+            ls[0] is ll[0] and ls[1] is ll[1] and ls[2] == ll[2] for ls, ll in zip(chain_s[:-1], chain[:-1]))
+        if not same:
+            raise LoweringError("bnn path: the two heads of the Normal likelihood %r stand on different trunks (both must be "
+                                "BF.matmul(weights, H) [+ bias] on the same H: the same x, the same latent variables and activations)" % k.name)
+        Ws, bs = chain_s[-1][0], chain_s[-1][1]
+        if (bs is None) != (chain[-1][1] is None):
+            raise LoweringError("bnn path: one head of the Normal likelihood %r has a bias and the other has none (either both or neither)" % k.name)
+        head = (g, ha, hb, Ws, bs)
     latents = []
     for W, b, _ in chain:
         latents.append(W)
         if b is not None:
             latents.append(b)
+    if head:
+        head_vars = [v for v in (chain[-1][0], chain[-1][1], head[3], head[4]) if v is not None]
+        trunk_names = [v.name for v in latents[:len(latents) - (2 if chain[-1][1] is not None else 1)]]
+        for v in head_vars:
+            if v.name in trunk_names or sum(1 for o in head_vars if o.name == v.name) > 1:
+                raise LoweringError("bnn path: the head tensor %r of the Normal likelihood %r is used twice (in the trunk, or by both heads)"
+                                    % (v.name, k.name))
+        latents += [v for v in (head[3], head[4]) if v is not None]
     names = [v.name for v in latents]
     if len(set(names)) != len(names):
         raise LoweringError("bnn path: a latent tensor is used by two layers")
@@ -235,6 +305,11 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     order = [chain[0][0]] + ([chain[0][1]] if chain[0][1] is not None else [])
     for W, b, _ in chain[1:]:
         order += [W] + ([b] if b is not None else [])
+    if head:
+        # to the library the two heads are ONE last layer of 2 C rows: weights_loc | weights_scale a row-major [2 C, cols] block of the
+        # latent vector, b_loc | b_scale the column behind it
+        Wl, bl = chain[-1][0], chain[-1][1]
+        order = [v for v in order if v is not Wl and v is not bl] + [Wl, head[3]] + ([bl, head[4]] if bl is not None else [])
     tensors, row0, entries = [], 0, []
     for v in order:
         q = L.q_by_name[v.name]
@@ -266,12 +341,25 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
         layers.append(dict(rows=t["rows"], cols=t["cols"], weight_row0=t["row0"], bias_row0=bias0,
                            activation=ACTIVATIONS[act] if act else 0, weights=W.name, bias=b.name if b is not None else None))
         width = t["rows"]
+    if head:
+        ts, last = by_name[head[3].name], layers[-1]
+        if ts["cols"] != last["cols"]:
+            raise LoweringError("bnn path: %r is [%d, %d] but its input has %d rows" % (ts["name"], ts["rows"], ts["cols"], last["cols"]))
+        if head[4] is not None and (by_name[head[4].name]["rows"], by_name[head[4].name]["cols"]) != (ts["rows"], 1):
+            raise LoweringError("bnn path: bias %r must be a column [%d, 1]" % (head[4].name, ts["rows"]))
+        if Ym.shape[1] != width or ts["rows"] != width:
+            raise LoweringError("bnn path: the targets have %d columns but the heads of the Normal likelihood %r have %d (loc) and %d (scale) "
+                                "rows" % (Ym.shape[1], k.name, width, ts["rows"]))
+        last.update(weights_scale=ts["name"], bias_scale=head[4].name if head[4] is not None else None)
     lik = LIK_NORMAL if normal else LIK_CATEGORICAL if k.distribution.kind == D.DIST_CATEGORICAL else LIK_BERNOULLI
     scale_entries = None
     if normal:
         if Ym.shape[1] != width:
             raise LoweringError("bnn path: the targets have %d columns but the last layer has %d rows" % (Ym.shape[1], width))
-        scale_entries = _normal_scale(L, k, links, width, joint_roots)
+        if head:
+            layers[-1]["rows"] = 2 * width
+        else:
+            scale_entries = _normal_scale(L, k, links, width, joint_roots)
     if lik == LIK_BERNOULLI:
         if width != 1:
             raise LoweringError("bnn path: a Bernoulli/Binomial likelihood needs a single output")
@@ -298,7 +386,9 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     prog.layers, prog.tensors, prog.n_rows = layers, tensors, R
     prog.n_features, prog.n_classes, prog.dataset_size, prog.batch_size = P, width, DS, int(ind_x.batch_size)
     prog.likelihood = lik
-    if normal:
+    if head:
+        prog.scale_head = head[:3]
+    elif normal:
         # (constants stand behind the entries with a gradient in the uniform table; a learnable scale is one of those)
         prog.scale_learnable = scale_entries[2]
         prog.scale_uniform, prog.scale_stride = (0 if prog.scale_learnable else n_up) + scale_entries[0], scale_entries[1]
@@ -383,7 +473,10 @@ class CompiledBnn:
         self.lib = lib
         d, self._keep = make_desc(p)
         handle = C.c_void_p()
-        if p.likelihood == LIK_NORMAL:
+        if p.likelihood == LIK_NORMAL and getattr(p, "scale_head", None):
+            g, a, b = p.scale_head
+            native.check(lib.bsvi_bnn_create_normal_heads(C.byref(d), lowering.UT[g], a, b, C.byref(handle)))
+        elif p.likelihood == LIK_NORMAL:
             create = lib.bsvi_bnn_create_normal_learnable if getattr(p, "scale_learnable", False) else lib.bsvi_bnn_create_normal
             native.check(create(C.byref(d), p.scale_uniform, p.scale_stride, C.byref(handle)))
         else:
@@ -565,7 +658,8 @@ class CompiledBnn:
         — the draw of a training launch at the same (seed, offset, sample_base), or `noise` ([n_rows, N], or named as the oracle
         takes it) — and the chain forward on every row of `x`.  Device tensors: "probs" [N, M, C] (softmax probabilities | sigmoid of
         the logit | the Normal's loc), "mean" [M, C] (their mean over the samples, fixed order), "var" [M, C] (Normal likelihood only:
-        population variance of the loc over the samples + sigma^2), and on request "outputs" [N, M, C] (logits | loc), "draws"
+        population variance of the loc over the samples + sigma^2; with a scale head + the mean over the samples of sigma^2), and on request
+        "outputs" [N, M, C] (logits | loc; a scale head adds "scale" [N, M, C], sigma of every sample and row), "draws"
         [N, M, C] (one draw of the likelihood per sample and row: one-hot | 0 / 1 | real) and "noise" [n_rows, N] (the eps drawn).
         offset=None draws from the sampling range (1 << 62) + tick, as the samplers of the engine do; `self.iteration`, `self.out` and
         the gradients are left alone.  Not sharded: every rank computes all N samples, no collective.  rows_per_pass (a multiple of
@@ -596,7 +690,8 @@ class CompiledBnn:
         new = lambda *shape: torch.empty(shape, device=dev)
         probs, mean = new(N, M, Cn), new(M, Cn)
         var = new(M, Cn) if p.likelihood == LIK_NORMAL else None
-        outputs = new(N, M, Cn) if want_outputs else None
+        heads = bool(getattr(p, "scale_head", None))        # (z_out is then [N, M, 2 C]: the loc, then sigma itself)
+        outputs = new(N, M, 2 * Cn if heads else Cn) if want_outputs else None
         draws = new(N, M, Cn) if want_draws else None
         noise_o = new(p.n_noise, N) if want_noise else None
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
@@ -608,6 +703,8 @@ class CompiledBnn:
         res = dict(probs=probs, mean=mean, n_rows=M, seed=int(seed), offset=int(offset),
                    rows_per_pass=int(self.lib.bsvi_bnn_predict_rows_per_pass(self.handle, N, M, rpp)),
                    data_path="bf16x3" if self.lib.bsvi_bnn_predict_last_exact() == 1 else "f32")
+        if heads and outputs is not None:
+            outputs, res["scale"] = outputs[..., :Cn], outputs[..., Cn:]      # (views of the one buffer: no copy on the device)
         for k, t in (("var", var), ("outputs", outputs), ("draws", draws), ("noise", noise_o)):
             if t is not None:
                 res[k] = t

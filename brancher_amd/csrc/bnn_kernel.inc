@@ -13,6 +13,12 @@
 // into the gradient of its entry: per (c, b, n) beside liknb at the two bnn_upper sites and summed over b by bnn_sig_rows (bnn_lik's
 // order), per (c, n) out of the tile in bnn_mid_gen; then over n in double precision (bnn_epilogue) and into the entry (bnn_uniform_grads).
 // All of it behind BParams::scale_learn / a generator switch: a constant sigma and the classifiers run what they ran.
+// A scale head (bsvi_bnn_create_normal_heads: heteroscedastic regression) makes sigma a function of the input: the last layer has 2 C
+// rows, z_c the loc and z_(C + c) the raw scale of output c, sigma_c = a + b g(z_(C + c)) with g softplus / exp / sigmoid, and the
+// epilogue of every site seeds BOTH halves,
+//     delta_c = wgt u_c / sigma_c,      delta_(C + c) = wgt (u_c^2 - 1) / sigma_c * b g'(z_(C + c))
+// so that the reverse sweep, bnn_small, the second product and the row sums carry the gradient to the four head tensors as they carry
+// any delta (no sigma table behind the targets, none of the scale_learn machinery).  BParams::C stays the number of TARGETS per row.
 // All latent scalars form ONE vector of R rows (weights1 first: H_1 x P
 // rows r = h * P + p, then the other tensors); row r draws eps from the dense path's Philox counters (sample, r >> 2), so the
 // noise of a model is one [R][N] matrix as on the dense path, and reads its four parameters (q loc, q scale, prior loc, prior
@@ -50,6 +56,10 @@ struct BParams {
     uint32_t n_uniform_grad, likelihood, estimator, exact, act_width;
     uint32_t LC, scale_u, scale_stride;       // targets per minibatch row (1 label; C for the Normal likelihood) and sigma's uniform entries
     uint32_t scale_learn;                     // sigma's entries are parameters: its gradient is accumulated (launch-uniform)
+    // a scale head (bsvi_bnn_create_normal_heads; 0: none): the last layer has 2 C rows, the loc in row c and the raw scale in row C + c,
+    // sigma_c = head_a + head_b g(raw) with g the BSVI_UT_* transform `heads`.  C, LC and the targets stay C per row: where a kernel
+    // means "rows of the last layer" it reads layer[n_layers - 1].rows, never C
+    uint32_t heads; float head_a, head_b;
     float lik_weight, prior_weight, entropy_weight;
     uint32_t seed_lo, seed_hi, offset_lo, offset_hi;
     const float* noise_in; float* noise_out; const int32_t* indices_in; int32_t* indices_out; float* fvalue_out; float* logq_out;
@@ -99,6 +109,17 @@ __device__ __forceinline__ float bnn_act_grad(uint32_t act, float y) {
     case BSVI_BNN_ACT_SOFTPLUS: return y > 20.0f ? 1.0f : -expm1f(-y);
     default: return 1.0f;
     }
+}
+
+// a scale head's sigma = a + b g(raw) and d sigma / d raw = b g'(raw): g softplus (as bnn_act writes it; torch's backward is 1 above the
+// threshold), exp or sigmoid
+__device__ __forceinline__ float bnn_head_sigma(const uint32_t t, const float a, const float b, const float raw, float& dsigma) {
+    float g, dg;
+    if (t == BSVI_UT_EXP) { g = expf(raw); dg = g; }
+    else if (t == BSVI_UT_SIGMOID) { g = sigmoidf_(raw); dg = g * (1.0f - g); }
+    else { g = raw > 20.0f ? raw : log1pf(expf(raw)); dg = raw > 20.0f ? 1.0f : sigmoidf_(raw); }
+    dsigma = b * dg;
+    return a + b * g;
 }
 
 __device__ __forceinline__ float bnn_uniform_value(const BParams& Q, uint32_t k) {
@@ -167,7 +188,7 @@ __device__ __forceinline__ void bnn_head_body(const BParams& Q, const uint32_t i
         Q.idx[i] = row;
         for (uint32_t c = 0; c < Q.LC; ++c) Q.lab[(size_t)i * Q.LC + c] = row >= 0 ? Q.labels[(size_t)row * Q.LC + c] : 0.0f;
     }
-    if (Q.likelihood == BSVI_LIK_NORMAL && i < Q.C) {      // (R >= C: the last layer alone has C rows of weights)
+    if (Q.likelihood == BSVI_LIK_NORMAL && !Q.heads && i < Q.C) {      // (R >= C: the last layer alone has C rows of weights)
         const float sigma = bnn_uniform_value(Q, Q.scale_u + i * Q.scale_stride);
         float* const sg = Q.lab + (size_t)Q.B_pad * Q.LC;
         sg[i] = sigma;
@@ -328,7 +349,21 @@ __global__ void __launch_bounds__(256) bnn_upper(const BParams Q) {
         // ---- likelihood and d f / d logits (distributions.py:294-311 / 561-592 through torch: log_softmax, BCE with logits)
         const float wgt = live ? Q.lik_weight * (Q.f_weight ? Q.f_weight[n] : 1.0f) : 0.0f, label = Q.lab[(size_t)b * Q.LC];
         float lik = 0.0f;
-        if (Q.likelihood == BSVI_LIK_NORMAL) {
+        if (Q.likelihood == BSVI_LIK_NORMAL && Q.heads) {
+            // y_c ~ Normal(z_c, a + b g(z_(C + c))): the second half of the last layer is the raw scale, and its delta carries
+            // d f / d sigma through the transform — the reverse sweep takes both halves down like any delta
+            const float* const yb = Q.lab + (size_t)b * Q.LC;
+            const uint32_t Ct = LL.rows / 2u;
+            float s = 0.0f;
+            for (uint32_t c = 0; c < Ct; ++c) {
+                float ds;
+                const float sigma = bnn_head_sigma(Q.heads, Q.head_a, Q.head_b, Y(LL, Ct + c), ds), u = (yb[c] - Y(LL, c)) / sigma;
+                s += -0.5f * u * u - logf(sigma) - 0.91893853320467274178f;
+                Dl(LL, c) = wgt * u / sigma;
+                Dl(LL, Ct + c) = wgt * (u * u - 1.0f) / sigma * ds;
+            }
+            lik = wgt * s;
+        } else if (Q.likelihood == BSVI_LIK_NORMAL) {
             // y_c ~ Normal(z_c, sigma_c), sigma a constant of the model (distributions.py:137 through torch): the targets of row b,
             // then sigma and -log sigma - 1/2 log 2 pi per output behind the targets (bnn_head_body)
             const float* const yb = Q.lab + (size_t)b * Q.LC;
@@ -702,6 +737,8 @@ struct bsvi_bnn {
     uint32_t LC = 1;             // targets per dataset row: one label, or C for the Normal likelihood
     uint32_t scale_u = 0, scale_stride = 0;      // Normal likelihood: sigma of output c is uniform entry scale_u + c * scale_stride
     bool scale_learn = false;    // ... parameter entries (bsvi_bnn_create_normal_learnable), else constants
+    uint32_t heads = 0;          // a scale head (bsvi_bnn_create_normal_heads): its BSVI_UT_* transform; the last layer has 2 C rows
+    float head_a = 0.0f, head_b = 1.0f;
     uint8_t* row_kind = nullptr; // the prior of every row, in the blob (all Normal until bsvi_bnn_set_row_priors)
     bool mixed = false;          // some row is Laplace or Cauchy: the MIXED instantiations of bnn_draw / bnn_row_sums
     mutable std::atomic<bool> launched{false};      // a launch was made: the priors stay as they are
@@ -750,6 +787,34 @@ static std::string bnn_normal_source(uint32_t C, uint32_t yl, bool sig_terms = f
              "            lik = wgt * sn;\n"
              "        }\n", C, C, C, yl, C, yl,
              sig_terms ? "                A.sigt[((size_t)c * A.B_pad + b) * A.n_pad + n] = wgt * (u * u - 1.0f) / sigma;\n" : "");
+    return std::string(buf);
+}
+
+// ... of a network with a scale head (bsvi_bnn_create_normal_heads): y[yl + c] the loc, y[yl + C + c] the raw scale, the transform and its
+// two constants as literals (their bits: no decimal round trip); the text bnn_upper runs through bnn_head_sigma
+static std::string bnn_heads_source(const bsvi_bnn* p, uint32_t yl) {
+    uint32_t abits, bbits;
+    memcpy(&abits, &p->head_a, 4); memcpy(&bbits, &p->head_b, 4);
+    const char* g = p->heads == BSVI_UT_EXP ? "const float g = expf(raw), dg = g;"
+                  : p->heads == BSVI_UT_SIGMOID ? "const float g = sigmoidf_(raw), dg = g * (1.0f - g);"
+                  : "const float g = raw > 20.0f ? raw : log1pf(expf(raw)), dg = raw > 20.0f ? 1.0f : sigmoidf_(raw);";
+    char buf[1536];
+    snprintf(buf, sizeof buf,
+             "        {\n"
+             "            const float* const yb = A.lab + (size_t)b * %uu;\n"
+             "            const float ha = __uint_as_float(0x%08xu), hb = __uint_as_float(0x%08xu);\n"
+             "            float sn = 0.0f;\n"
+             "#pragma unroll\n"
+             "            for (uint32_t c = 0; c < %uu; ++c) {\n"
+             "                const float raw = y[%uu + c];\n"
+             "                %s\n"
+             "                const float sigma = ha + hb * g, u = (yb[c] - y[%uu + c]) / sigma;\n"
+             "                sn += -0.5f * u * u - logf(sigma) - 0.91893853320467274178f;\n"
+             "                d[%uu + c] = wgt * u / sigma;\n"
+             "                d[%uu + c] = wgt * (u * u - 1.0f) / sigma * (hb * dg);\n"
+             "            }\n"
+             "            lik = wgt * sn;\n"
+             "        }\n", p->C, abits, bbits, p->C, yl + p->C, g, yl, yl, yl + p->C);
     return std::string(buf);
 }
 
@@ -825,7 +890,7 @@ static std::string bnn_upper_source(const bsvi_bnn* p) {
     s += std::string("        const float wgt = live ? A.lik_weight * (A.f_weight ? A.f_weight[n] : 1.0f) : 0.0f") +
          (p->d.likelihood == BSVI_LIK_NORMAL ? ";\n" : ", label = A.lab[b];\n") + "        float lik = 0.0f;\n";
     if (p->d.likelihood == BSVI_LIK_NORMAL) {
-        s += bnn_normal_source(LL.rows, yl, p->scale_learn);
+        s += p->heads ? bnn_heads_source(p, yl) : bnn_normal_source(LL.rows, yl, p->scale_learn);
     } else if (p->d.likelihood == BSVI_LIK_CATEGORICAL) {
         s += "        {\n            float m = -INFINITY;\n#pragma unroll\n";
         s += fmt("            for (uint32_t c = 0; c < %uu; ++c) m = fmaxf(m, y[%uu + c]);\n", LL.rows, yl);
@@ -980,7 +1045,7 @@ static std::string bnn_mid_source(const bsvi_bnn* p) {
     s += std::string("        const float wgt = live ? A.lik_weight * (A.f_weight ? A.f_weight[n] : 1.0f) : 0.0f") +
          (p->d.likelihood == BSVI_LIK_NORMAL ? ";\n" : ", label = A.lab[b];\n") + "        float lik = 0.0f;\n";
     if (p->d.likelihood == BSVI_LIK_NORMAL) {
-        s += bnn_normal_source(LL.rows, yl);
+        s += p->heads ? bnn_heads_source(p, yl) : bnn_normal_source(LL.rows, yl);
     } else if (p->d.likelihood == BSVI_LIK_CATEGORICAL) {
         s += "        {\n            float m = -INFINITY;\n#pragma unroll\n";
         s += fmt("            for (uint32_t c = 0; c < %uu; ++c) m = fmaxf(m, y[%uu + c]);\n", LL.rows, yl);
@@ -1141,8 +1206,10 @@ static bool bnn_upper_ready(const bsvi_bnn* p) {
 
 // the three entry points' common body; normal: bsvi_bnn_create_normal (the scale entries are its plain arguments: constants), learn:
 // bsvi_bnn_create_normal_learnable (parameter entries)
+// heads: bsvi_bnn_create_normal_heads (no scale entries: sigma is a transform of the last layer's second half)
+struct BnnHeads { uint32_t transform; float a, b; };
 static int bnn_create(const bsvi_bnn_desc* desc, const bool normal, const uint32_t scale_uniform, const uint32_t scale_stride, bsvi_bnn** out,
-                      const bool learn = false) {
+                      const bool learn = false, const BnnHeads* heads = nullptr) {
     if (!desc || !out) return fail(BSVI_ERR_INVALID, "null argument");
     *out = nullptr;
     BSVI_CHECK_STRUCT(desc, bsvi_bnn_desc);
@@ -1153,7 +1220,8 @@ static int bnn_create(const bsvi_bnn_desc* desc, const bool normal, const uint32
     if (!normal && desc->likelihood == BSVI_LIK_NORMAL)
         return fail(BSVI_ERR_UNSUPPORTED, "the Normal likelihood needs its scale entries: create the model with bsvi_bnn_create_normal");
     if (normal && desc->likelihood != BSVI_LIK_NORMAL)
-        return fail(BSVI_ERR_INVALID, learn ? "bsvi_bnn_create_normal_learnable takes likelihood BSVI_LIK_NORMAL" : "bsvi_bnn_create_normal takes likelihood BSVI_LIK_NORMAL");
+        return fail(BSVI_ERR_INVALID, heads ? "bsvi_bnn_create_normal_heads takes likelihood BSVI_LIK_NORMAL"
+                                      : learn ? "bsvi_bnn_create_normal_learnable takes likelihood BSVI_LIK_NORMAL" : "bsvi_bnn_create_normal takes likelihood BSVI_LIK_NORMAL");
     if (desc->likelihood > BSVI_LIK_NORMAL) return fail(BSVI_ERR_UNSUPPORTED, "unknown likelihood");
     if (desc->estimator > BSVI_EST_BLACKBOX) return fail(BSVI_ERR_INVALID, "unknown estimator");
     for (uint32_t k = 0; k < desc->n_uniform; ++k) {
@@ -1178,7 +1246,14 @@ static int bnn_create(const bsvi_bnn_desc* desc, const bool normal, const uint32
     }
     if (desc->layers[desc->n_layers - 1].activation != BSVI_BNN_ACT_NONE) return fail(BSVI_ERR_INVALID, "the last layer yields the logits");
     if (desc->likelihood == BSVI_LIK_BERNOULLI && width != 1) return fail(BSVI_ERR_INVALID, "Bernoulli likelihood needs one output");
-    if (normal) {
+    if (heads) {
+        if (heads->transform != BSVI_UT_SOFTPLUS && heads->transform != BSVI_UT_EXP && heads->transform != BSVI_UT_SIGMOID)
+            return fail(BSVI_ERR_UNSUPPORTED, "bsvi_bnn_create_normal_heads: the transform of the scale head is softplus, exp or sigmoid");
+        if (!std::isfinite(heads->a) || !std::isfinite(heads->b) || heads->a < 0.0f || !(heads->b > 0.0f))
+            return fail(BSVI_ERR_INVALID, "bsvi_bnn_create_normal_heads: sigma = a + b g(raw) needs finite a >= 0 and b > 0");
+        if (width % 2u)
+            return fail(BSVI_ERR_INVALID, "bsvi_bnn_create_normal_heads: the last layer has an odd number of rows (C rows of the loc, then C of the raw scale)");
+    } else if (normal) {
         // sigma of output c: entry scale_uniform + c * scale_stride, every one of them a constant of the model
         if (scale_stride > 1u) return fail(BSVI_ERR_INVALID, "scale_stride is 0 (one scale for every output) or 1 (one per output)");
         const uint64_t last = (uint64_t)scale_uniform + (uint64_t)scale_stride * (width - 1u);
@@ -1210,6 +1285,7 @@ static int bnn_create(const bsvi_bnn_desc* desc, const bool normal, const uint32
     p->Kp = (p->P + 31) / 32 * 32; p->P_ld = (p->P + 3) / 4 * 4;
     p->B_pad = (desc->batch_size + 31) / 32 * 32;
     if (normal) { p->LC = width; p->scale_u = scale_uniform; p->scale_stride = scale_stride; p->scale_learn = learn; }
+    if (heads) { p->C = p->LC = width / 2u; p->heads = heads->transform; p->head_a = heads->a; p->head_b = heads->b; }
     for (uint32_t l = 0; l < desc->n_layers; ++l) { p->act_off[l] = (uint32_t)p->act_floats; p->act_floats += p->layers[l].rows; }
     p->delta_floats = p->act_floats;
     {   // exact data: both products on the bf16 matrix cores (three MFMAs on the exact pieces of the other operand); BSVI_DENSE_XGEMM=0: f32
@@ -1271,6 +1347,11 @@ extern "C" int bsvi_bnn_create_normal(const bsvi_bnn_desc* desc, uint32_t scale_
 
 extern "C" int bsvi_bnn_create_normal_learnable(const bsvi_bnn_desc* desc, uint32_t scale_uniform, uint32_t scale_stride, bsvi_bnn** out) {
     return bnn_create(desc, true, scale_uniform, scale_stride, out, true);
+}
+
+extern "C" int bsvi_bnn_create_normal_heads(const bsvi_bnn_desc* desc, uint32_t transform, float a, float b, bsvi_bnn** out) {
+    const BnnHeads heads{transform, a, b};
+    return bnn_create(desc, true, 0u, 0u, out, false, &heads);
 }
 
 // the prior of every row: Normal (what every row is without this call), Laplace or Cauchy.  Before the first launch only — the
@@ -1377,6 +1458,7 @@ static int bnn_fill(const bsvi_bnn* p, const bsvi_bnn_args* a, BParams& Q, BnnLa
     Q.sample_base = a->sample_base; Q.NC = L.NC; Q.n_uniform_grad = p->d.n_uniform_grad; Q.likelihood = p->d.likelihood;
     Q.estimator = p->d.estimator; Q.exact = p->exact ? 1u : 0u; Q.act_width = (uint32_t)p->act_floats;
     Q.LC = p->LC; Q.scale_u = p->scale_u; Q.scale_stride = p->scale_stride; Q.scale_learn = p->scale_learn ? 1u : 0u;
+    Q.heads = p->heads; Q.head_a = p->head_a; Q.head_b = p->head_b;
     Q.lik_weight = p->d.lik_weight; Q.prior_weight = p->d.prior_weight; Q.entropy_weight = p->d.entropy_weight;
     Q.seed_lo = (uint32_t)a->seed; Q.seed_hi = (uint32_t)(a->seed >> 32); Q.offset_lo = (uint32_t)a->offset; Q.offset_hi = (uint32_t)(a->offset >> 32);
     Q.noise_in = a->noise_dev; Q.noise_out = a->noise_out_dev; Q.indices_in = a->indices_dev; Q.indices_out = a->indices_out_dev;
@@ -1540,6 +1622,8 @@ struct BnnPredict {
     float* p;                    // the pass's p: element (n, j, c) of the pass at p[n * p_stride + j * C + c]
     size_t p_stride;
     float* mean_out; float* var_out;      // [M][C] or null
+    // a scale head only: sigma of the pass, element (n, j, c) at sig[n * sig_stride + j * C + c] (what the reduce reads; z_out holds a copy)
+    float* sig; size_t sig_stride;
 };
 
 // grid: any, block 256.  flag must hold 1; a value with low mantissa bits clears it (every writer writes the same 0)
@@ -1557,7 +1641,7 @@ __global__ void __launch_bounds__(256) bnn_predict_head(const BParams Q, const B
 #pragma unroll
         for (uint32_t q = 0; q < 4u; ++q) Q.rowp[(size_t)q * Q.R + i] = bnn_uniform_value(Q, Q.row_uniform[(size_t)q * Q.R + i]);
     }
-    if (Q.likelihood == BSVI_LIK_NORMAL && i < Q.C) const_cast<float*>(V.sg)[i] = bnn_uniform_value(Q, Q.scale_u + i * Q.scale_stride);
+    if (Q.likelihood == BSVI_LIK_NORMAL && !Q.heads && i < Q.C) const_cast<float*>(V.sg)[i] = bnn_uniform_value(Q, Q.scale_u + i * Q.scale_stride);
 }
 
 // row m0 + j of x_new as row j of the pass's operand, as bnn_gather_body writes the minibatch's (no transpose: there is no second
@@ -1592,7 +1676,7 @@ __global__ void __launch_bounds__(256) bnn_predict_fwd(const BParams Q, const Bn
     const float* const wsm = Q.Wsm + (size_t)n * Q.Rs;
     auto W = [&](uint32_t r) { return LDSW ? wl[r * 65u + lane] : wsm[r]; };
     const BnnLayerDev L1 = Q.layer[0], LL = Q.layer[Q.n_layers - 1];
-    const uint32_t C = LL.rows;
+    const uint32_t C = Q.heads ? LL.rows / 2u : LL.rows;      // targets per row; a scale head's last layer has 2 C rows
     for (uint32_t bi = 0; bi < 2u; ++bi) {
         const uint32_t j = blockIdx.y * 8u + wave * 2u + bi;
         if (j >= V.rows_pass) continue;
@@ -1622,7 +1706,15 @@ __global__ void __launch_bounds__(256) bnn_predict_fwd(const BParams Q, const Bn
         if (!live) continue;
         const size_t at = ((size_t)n * V.M + m) * C;
         float* const pp = V.p + (size_t)n * V.p_stride + (size_t)j * C;
-        if (V.z_out) for (uint32_t c = 0; c < C; ++c) V.z_out[at + c] = Y(cur, c);
+        // (a scale head: z_out is [n][M][2 C], the loc and then sigma itself; sigma of the pass stays in V.sig for the draw and the reduce)
+        float* const sp = Q.heads ? V.sig + (size_t)n * V.sig_stride + (size_t)j * C : nullptr;
+        if (Q.heads) {
+            for (uint32_t c = 0; c < C; ++c) {
+                float ds;
+                sp[c] = bnn_head_sigma(Q.heads, Q.head_a, Q.head_b, Y(cur, C + c), ds);
+                if (V.z_out) { V.z_out[2u * at + c] = Y(cur, c); V.z_out[2u * at + C + c] = sp[c]; }
+            }
+        } else if (V.z_out) for (uint32_t c = 0; c < C; ++c) V.z_out[at + c] = Y(cur, c);
         u32x4 x = {0u, 0u, 0u, 0u};
         if (V.draw_out && Q.likelihood != BSVI_LIK_NORMAL)
             x = philox4x32(Q.sample_base + n, m, Q.offset_lo, Q.offset_hi, Q.seed_lo ^ BNN_KEY_PREDICT, Q.seed_hi);
@@ -1634,7 +1726,7 @@ __global__ void __launch_bounds__(256) bnn_predict_fwd(const BParams Q, const Bn
                     float e[4];
                     box_muller_fast(w.x, w.y, e[0], e[1]);
                     box_muller_fast(w.z, w.w, e[2], e[3]);
-                    for (uint32_t c = c0; c < C && c < c0 + 4u; ++c) V.draw_out[at + c] = Y(cur, c) + V.sg[c] * e[c - c0];
+                    for (uint32_t c = c0; c < C && c < c0 + 4u; ++c) V.draw_out[at + c] = Y(cur, c) + (Q.heads ? sp[c] : V.sg[c]) * e[c - c0];
                 }
             }
         } else if (Q.likelihood == BSVI_LIK_CATEGORICAL) {
@@ -1675,7 +1767,18 @@ __global__ void __launch_bounds__(256) bnn_predict_reduce(const BParams Q, const
     const double mean = s / (double)Q.n_local;
     const size_t at = (size_t)V.m0 * C + i;
     if (V.mean_out) V.mean_out[at] = (float)mean;
-    if (V.var_out) {
+    if (V.var_out && Q.heads) {
+        // the law of total variance: + the mean over the samples of sigma^2 — a second sum in sample order, inside the loop of the first
+        // (784-20-(1+1), 512 rows, 1 024 samples, us per call: a loop of its own for sigma 840, this 722, the constant-sigma network of
+        // the same widths 565; the loads of eight samples issued in front of their additions 864 — profiles/r19/bnn_heads.txt)
+        const float* const sg = V.sig + i;
+        double q = 0.0, s2 = 0.0;
+        for (uint32_t n = 0; n < Q.n_local; ++n) {
+            const double d = (double)src[(size_t)n * V.p_stride] - mean, sn = (double)sg[(size_t)n * V.sig_stride];
+            q += d * d; s2 += sn * sn;
+        }
+        V.var_out[at] = (float)(q / (double)Q.n_local + s2 / (double)Q.n_local);
+    } else if (V.var_out) {
         double q = 0.0;
         for (uint32_t n = 0; n < Q.n_local; ++n) { const double d = (double)src[(size_t)n * V.p_stride] - mean; q += d * d; }
         const double sigma = (double)V.sg[c];
@@ -1690,7 +1793,8 @@ static uint32_t bnn_max_width(const bsvi_bnn* p) {
 }
 
 static bsvi_bnn_select::PredictLayout bnn_predict_layout(const bsvi_bnn* p, uint32_t n_local, uint32_t n_rows, uint32_t rows_per_pass) {
-    return bsvi_bnn_select::predict_layout(p->R, p->Rs, p->P, p->C, p->H1, bnn_max_width(p), n_local, n_rows, rows_per_pass);
+    // (a scale head: the p region is twice as large — p of a pass [n][rows][C] as ever, then sigma of the pass [n][rows][C])
+    return bsvi_bnn_select::predict_layout(p->R, p->Rs, p->P, p->heads ? 2u * p->C : p->C, p->H1, bnn_max_width(p), n_local, n_rows, rows_per_pass);
 }
 
 extern "C" size_t bsvi_bnn_predict_args_size(void) { return sizeof(bsvi_bnn_predict_args); }
@@ -1748,6 +1852,7 @@ extern "C" int bsvi_bnn_predict(const bsvi_bnn* p, const bsvi_bnn_predict_args* 
     Q.Kp = p->Kp; Q.P_ld = p->P_ld; Q.n_local = a->n_samples_local; Q.n_pad = L.n_pad; Q.n_global = a->n_samples_local;
     Q.sample_base = a->sample_base; Q.NC = L.NC; Q.likelihood = p->d.likelihood;
     Q.LC = p->LC; Q.scale_u = p->scale_u; Q.scale_stride = p->scale_stride;
+    Q.heads = p->heads; Q.head_a = p->head_a; Q.head_b = p->head_b;
     Q.seed_lo = (uint32_t)a->seed; Q.seed_hi = (uint32_t)(a->seed >> 32); Q.offset_lo = (uint32_t)a->offset; Q.offset_hi = (uint32_t)(a->offset >> 32);
     Q.noise_in = a->noise_dev; Q.noise_out = a->noise_out;
     Q.rowp = (float*)(ws + L.rowp); Q.Wsm = (float*)(ws + L.Wsm);
@@ -1804,6 +1909,7 @@ extern "C" int bsvi_bnn_predict(const bsvi_bnn* p, const bsvi_bnn_predict_args* 
         V.m0 = m0;
         if (a->p_out) { V.p = a->p_out + (size_t)m0 * p->C; V.p_stride = (size_t)a->n_rows * p->C; }
         else { V.p = (float*)(ws + L.p); V.p_stride = (size_t)L.rows_pass * p->C; }
+        if (p->heads) { V.sig_stride = (size_t)L.rows_pass * p->C; V.sig = (float*)(ws + L.p) + (size_t)a->n_samples_local * V.sig_stride; }
         hipLaunchKernelGGL(bnn_predict_gather, dim3(L.rows_pass * gy), dim3(256), 0, s, Q, V, gy);
         int rc;
         if (exact) rc = bsvi_xgemm_nt(Q.Xb_bf, nullptr, Q.Wp, (long)Q.NC * Q.Kp, const_cast<float*>(V.a1), (int)Q.NC, (int)L.rows_pass, (int)Q.NC, (int)Q.Kp, s);

@@ -872,7 +872,8 @@ def build_bayesian_neural_network(api, dataset_size=48, batch_size=30, n_feature
 
 def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_hidden=9, n_outputs=1, hidden2=0, activation="tanh",
                          sigma=0.5, data="integers", bias=True, seed=0, prior_scale=2., q_scale=0.1, q_scale1=None, q_loc_scale=0.5,
-                         widths=None, activations=None, learnable_sigma=False, sigma_init=None, prior="normal", prior_loc=0.):
+                         widths=None, activations=None, learnable_sigma=False, sigma_init=None, prior="normal", prior_loc=0.,
+                         scale_head=None, scale_floor=0.05):
     """The regression model of the Bayesian-neural-network family: the network of `build_bayesian_neural_network` (latent weight
     matrices and biases under a mean-field Normal posterior) as the loc of an observed Normal,
     `y ~ NormalVariable(matmul(weights2, act(matmul(weights1, x) + b1)) + b2, sigma)`, the targets [DS, C, 1] an EmpiricalVariable that
@@ -886,9 +887,16 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
     `NormalVariable(chain, sigma, "y", learnable=True)`: a learnable root `y_scale` behind a softplus in the joint model's parameter
     group; "exp" — `BF.exp` of a learnable root `y_log_scale`; the model's sigma then starts at sigma_init (one number or one per
     output; default: the teacher's sigma).  prior / prior_loc: as for `build_bayesian_neural_network` (the Bayesian lasso is
-    prior="laplace").  Without these keywords every model is built draw for draw as before."""
+    prior="laplace").  scale_head: "softplus" / "exp" / "sigmoid" — heteroscedastic regression: a second head `weights_scale` (and
+    `b_scale`) on the trunk of the last layer, `y ~ Normal(loc head, scale_floor + g(scale head))`, latents like the rest (prior may
+    be a dict that names them); the teacher's noise scale then depends on the input through a head of its own, and sigma / learnable_sigma
+    are not used.  Without these keywords every model is built draw for draw as before."""
     BF = api.BF
     prior_of = _bnn_prior(api, prior, prior_loc, prior_scale)
+    if scale_head not in (None, "softplus", "exp", "sigmoid"):
+        raise ValueError("scale_head is None, \"softplus\", \"exp\" or \"sigmoid\"")
+    if scale_head and (learnable_sigma or sigma_init is not None):
+        raise ValueError("a scale head replaces sigma: learnable_sigma and sigma_init do not apply")
     if learnable_sigma not in (False, True, "exp"):
         raise ValueError("learnable_sigma is False, True (the reference's flag) or \"exp\"")
     if sigma_init is not None and not learnable_sigma:
@@ -907,9 +915,15 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
     h = X[:, :, 0].astype(np.float64)
     for l in range(1, len(widths)):
         wt = rng.normal(0., 1., (widths[l], widths[l - 1])) / np.sqrt(max((h ** 2).mean(axis=0).sum(), 1e-6))
+        trunk = h
         h = h @ wt.T + (0.3 * rng.normal(0., 1., widths[l]) if bias else 0.)
         if l + 1 < len(widths):
             h = np_acts[acts[l - 1]](h)
+    if scale_head:
+        # the teacher's noise scale: a head of its own on the teacher's trunk, half-unit pre-activations about -1
+        g = dict(softplus=np_acts["softplus"], exp=np.exp, sigmoid=np_acts["sigmoid"])[scale_head]
+        ws = 0.5 * rng.normal(0., 1., (n_outputs, trunk.shape[1])) / np.sqrt(max((trunk ** 2).mean(axis=0).sum(), 1e-6))
+        sig = scale_floor + g(trunk @ ws.T - 1.)
     Y = (h + sig * rng.normal(0., 1., h.shape)).astype(np.float32).reshape(dataset_size, n_outputs, 1)
     if q_scale1 is None:
         q_scale1 = 0.4 / np.sqrt(float((X.astype(np.float64) ** 2).mean(axis=0).sum()))
@@ -927,9 +941,24 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
             pre = pre + prior_of("b%d" % l, (rows, 1))
             q_vars.append(api.NormalVariable(q_loc_scale * q_scale * rng.normal(0., 1., (rows, 1)), q_scale * np.ones((rows, 1)),
                                              "b%d" % l, learnable=True))
-        layer = getattr(BF, acts[l - 1])(pre) if l + 1 < len(widths) else pre
+        trunk, layer = layer, (getattr(BF, acts[l - 1])(pre) if l + 1 < len(widths) else pre)
         q_vars.append(api.NormalVariable(q_loc_scale * sw * rng.normal(0., 1., (rows, cols)), sw * np.ones((rows, cols)),
                                          "weights%d" % l, learnable=True))
+    if scale_head:
+        rows, cols = n_outputs, widths[-2]
+        sw = q_scale1 if len(widths) == 2 else q_scale
+        raw = BF.matmul(prior_of("weights_scale", (rows, cols)), trunk)
+        if bias:
+            raw = raw + prior_of("b_scale", (rows, 1))
+            q_vars.append(api.NormalVariable(q_loc_scale * q_scale * rng.normal(0., 1., (rows, 1)), q_scale * np.ones((rows, 1)),
+                                             "b_scale", learnable=True))
+        q_vars.append(api.NormalVariable(q_loc_scale * sw * rng.normal(0., 1., (rows, cols)), sw * np.ones((rows, cols)),
+                                         "weights_scale", learnable=True))
+        y = api.NormalVariable(layer, scale_floor + getattr(BF, scale_head)(raw), "y")
+        model = api.ProbabilisticModel([y])
+        y.observe(targets)
+        model.set_posterior_model(api.ProbabilisticModel(q_vars))
+        return model
     if sigma_init is not None:
         sig = np.asarray(sigma_init, dtype=np.float64).reshape(-1)
         if sig.size not in (1, n_outputs):

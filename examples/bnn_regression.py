@@ -12,6 +12,7 @@ MI355X:
     python examples/bnn_regression.py --learn-sigma      # sigma learnable: NormalVariable(chain, 1.0, "y", learnable=True)
     python examples/bnn_regression.py --prior laplace    # LaplaceVariable(0, 0.5) on every weight and bias (the Bayesian lasso)
     python examples/bnn_regression.py --prior cauchy     # CauchyVariable(0, 0.5): heavy tails
+    python examples/bnn_regression.py --scale-head       # input-dependent noise: a second head, sigma(x) = 0.05 + softplus(raw(x))
 
 With --learn-sigma the model starts from a guess of 1.0 and learns the noise scale with the posterior (a learnable root `y_scale`
 behind a softplus in the joint model's parameter group, stepped from the second iteration on, as the reference steps it); the learned
@@ -19,7 +20,9 @@ value is printed beside the teacher's.  With --prior the weights and biases carr
 prior of scale 0.5, parameters of the model in their own right, and the posterior stays mean-field Normal.  The likelihood is not
 rescaled from the minibatch to the dataset (as in the reference), so such a prior weighs as much as one minibatch of targets: the
 run with --prior is a 64-8-1 network on minibatches of 512 rows, where the data have the say — at 784-20-1 and 30 rows the 15 729
-weights would return to their prior.
+weights would return to their prior.  With --scale-head the noise level depends on the input: a second head `weights_scale`, `b_scale`
+on the hidden layer gives the scale of the Normal, `0.05 + BF.softplus(BF.matmul(weights_scale, hidden) + b_scale)`, latent like the
+rest; the teacher's noise varies from row to row, and the run prints how well the predicted scale follows the size of the residuals.
 """
 import os
 import sys
@@ -35,6 +38,12 @@ LEARN_SIGMA = "--learn-sigma" in sys.argv[1:]
 KW = dict(dataset_size=512, batch_size=30, n_features=784, n_hidden=20, n_outputs=1, sigma=0.5)
 if LEARN_SIGMA:
     KW.update(learnable_sigma=True, sigma_init=1.0)
+SCALE_HEAD = "--scale-head" in sys.argv[1:]
+if SCALE_HEAD:
+    if LEARN_SIGMA:
+        sys.exit("--scale-head replaces sigma: not with --learn-sigma")
+    KW.update(scale_head="softplus", scale_floor=0.05, dataset_size=2048, batch_size=512, n_features=64, n_hidden=8)
+    del KW["sigma"]
 PRIOR = None
 if "--prior" in sys.argv[1:]:
     PRIOR = (sys.argv[sys.argv.index("--prior") + 1:] or [""])[0]
@@ -63,7 +72,8 @@ model = W.build_bnn_regression(W.native_api(), **KW)
 print("engine: %s, data path %s" % (type(engine.compile_model(model)).__name__, engine.compile_model(model).data_path()))
 if PRIOR:
     print("priors:", engine.compile_model(model).program.summary()["priors"])
-print("RMSE of the posterior-mean prediction before training: %.3f (noise scale %.2f)" % (posterior_mean_rmse(model), KW["sigma"]))
+print("RMSE of the posterior-mean prediction before training: %.3f (noise scale %s)"
+      % (posterior_mean_rmse(model), "from the scale head" if SCALE_HEAD else "%.2f" % KW["sigma"]))
 t0 = time.time()
 inference.perform_inference(model, number_iterations=1500, number_samples=50, optimizer="Adam", lr=0.005)
 seconds = time.time() - t0
@@ -74,3 +84,15 @@ if LEARN_SIGMA:
     theta = float(engine.compile_model(model).named_params()["y_scale"].reshape(-1)[0])
     print("learned noise scale sigma = softplus(y_scale) = %.3f (started at %.2f; the teacher's noise: %.2f)"
           % (np.log1p(np.exp(theta)), KW["sigma_init"], KW["sigma"]))
+if SCALE_HEAD:
+    # the posterior predictive on the dataset's own rows: "scale" is sigma per sample and row, "var" the total variance
+    c = engine.compile_model(model)
+    y = next(v for v in model.flatten() if v.name == "y")
+    X, Y = dataset_of(next(v for v in model.flatten() if v.name == "x")), dataset_of(y.dataset)
+    res = c.predict(X.astype(np.float32), 64, seed=1, offset=0, want_outputs=True)
+    sigma = res["scale"].mean(dim=0).cpu().numpy().reshape(-1)
+    resid = np.abs(res["mean"].cpu().numpy().reshape(-1) - Y.reshape(-1))
+    order = np.argsort(sigma)
+    quarter = len(order) // 4
+    print("predicted noise scale: %.3f .. %.3f over the rows; mean |residual| in the quarter of the rows with the smallest predicted "
+          "scale %.3f, with the largest %.3f" % (sigma.min(), sigma.max(), resid[order[:quarter]].mean(), resid[order[-quarter:]].mean()))

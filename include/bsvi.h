@@ -454,7 +454,7 @@ int bsvi_query_geometry(const bsvi_program* prog, uint32_t n_samples_local, uint
 typedef enum bsvi_dense_likelihood {
     BSVI_LIK_CATEGORICAL = 0,   /* CategoricalVariable(logits=...)            distributions.py:294-311 */
     BSVI_LIK_BERNOULLI = 1,     /* Binomial(1, logits=...) / Bernulli(logits) distributions.py:561-592 */
-    BSVI_LIK_NORMAL = 2         /* NormalVariable(loc, scale) with a constant scale: regression; bsvi_bnn_create_normal only */
+    BSVI_LIK_NORMAL = 2         /* NormalVariable(loc, scale): regression; bsvi_bnn_create_normal and its _learnable / _heads siblings only */
 } bsvi_dense_likelihood;
 
 typedef struct bsvi_dense_desc {
@@ -612,9 +612,21 @@ int bsvi_bnn_create_normal(const bsvi_bnn_desc* desc, uint32_t scale_uniform, ui
  * order and on top of what the entry's rows contribute — one entry may be a prior scale and sigma; the chain rule through the
  * transform, finalize and the optimizer step are those of every other entry.  No struct changes, the ABI version stays. */
 int bsvi_bnn_create_normal_learnable(const bsvi_bnn_desc* desc, uint32_t scale_uniform, uint32_t scale_stride, bsvi_bnn** out);
+/* The same model with a SCALE HEAD (heteroscedastic regression): the last layer has 2 C rows — the loc of output c in row c, the raw
+ * scale in row C + c, both heads of one trunk and latents like every other row — and desc->labels is [dataset_size][C].  Per minibatch
+ * row, sample and output, with z the last layer's 2 C pre-activations:
+ *     sigma_c = a + b g(z[C + c]),  u = (y_c - z[c]) / sigma_c,  f += lik_weight * (-1/2 u^2 - log sigma_c - 1/2 log 2 pi)
+ *     d f / d z[c] = lik_weight u / sigma_c,    d f / d z[C + c] = lik_weight (u^2 - 1) / sigma_c * b g'(z[C + c])
+ * g is `transform`: BSVI_UT_SOFTPLUS (x > 20: x itself), BSVI_UT_EXP or BSVI_UT_SIGMOID, another one BSVI_ERR_UNSUPPORTED; an odd
+ * number of rows in the last layer, a < 0, b <= 0 or a value that is not finite is BSVI_ERR_INVALID (all checked in front of the device
+ * query).  Behind the two deltas everything is bsvi_bnn_create's; the uniform table holds no scale entry.  bsvi_bnn_predict: p_out /
+ * mean_out are the loc [..][C], var_out the variance of the loc over the samples plus the mean over the samples of sigma^2, draw_out
+ * loc + sigma e, and z_out is [n_samples_local][n_rows][2 C]: the loc, then SIGMA (not the raw value).  No struct changes, the ABI
+ * version stays. */
+int bsvi_bnn_create_normal_heads(const bsvi_bnn_desc* desc, uint32_t transform, float a, float b, bsvi_bnn** out);
 /* The PRIOR of every latent row: kinds[r] is BSVI_DIST_NORMAL, BSVI_DIST_LAPLACE or BSVI_DIST_CAUCHY (the reference's LaplaceVariable /
  * CauchyVariable weights and biases; another kind is BSVI_ERR_UNSUPPORTED), its loc and scale the row's prior loc / prior scale entries
- * as for the Normal.  Valid after any of the three create calls and before the first launch (bsvi_bnn_fwd_bwd, bsvi_bnn_step,
+ * as for the Normal.  Valid after any of the create calls and before the first launch (bsvi_bnn_fwd_bwd, bsvi_bnn_step,
  * bsvi_bnn_predict): a wrong n_rows, a null pointer or a call after a launch is BSVI_ERR_INVALID.  Without the call every row is Normal,
  * and such a model runs the kernels it ran.  With u = (w - mu0) / s0 a Laplace row adds  prior_weight (-|u| - log(2 s0))  to f per sample,
  * a Cauchy row  prior_weight (-log1p(u^2) - log(pi) - log(s0));  their gradients are per-sample sums taken in a fixed order inside the
