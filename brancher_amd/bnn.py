@@ -12,7 +12,8 @@ between the layers, biases optional) — and the regression model of the same fa
 
     y = NormalVariable(BF.matmul(weights2, hidden) + b2, sigma, name="y");  y.observe(targets)        # targets [DS, C, 1]
 
-with sigma (one value, or [C, 1]) a constant of the model (`bsvi_bnn_create_normal`) or learnable — the reference's
+(or a `LaplaceVariable` / `CauchyVariable` in its place: median regression, the heavy-tailed fit — `program.family`,
+`bsvi_bnn_set_likelihood_family`), with sigma (one value, or [C, 1]) a constant of the model (`bsvi_bnn_create_normal`) or learnable — the reference's
 `NormalVariable(chain, 0.5, "y", learnable=True)`, or any a + b g(root) of a learnable root with g softplus / exp / sigmoid
 (`bsvi_bnn_create_normal_learnable`) —, or computed from the input by a second head on the trunk of the first (heteroscedastic regression),
 
@@ -43,12 +44,15 @@ NO_BIAS = 0xFFFFFFFF
 MAX_LAYERS = 8                                                         # BNN_MAX_LAYERS (csrc/bnn_kernel.inc)
 MIDDLE_PATHS = ("mid_gen", "upper_gen", "upper_lds", "upper_mem")      # bsvi_bnn_select::BnnMiddle (csrc/bnn_select.h)
 PREDICT_PATHS = ("global", "lds")                                      # bsvi_bnn_predict_lds
+# the families of the loc-scale regression likelihood (bsvi_bnn_set_likelihood_family): the name a refusal gives the observed variable
+LIKELIHOOD_FAMILIES = {D.DIST_NORMAL: "Normal", D.DIST_LAPLACE: "Laplace", D.DIST_CAUCHY: "Cauchy"}
 PRIOR_KINDS = {D.DIST_NORMAL: "normal", D.DIST_LAPLACE: "laplace", D.DIST_CAUCHY: "cauchy"}      # bsvi_bnn_set_row_priors (BSVI_DIST_*)
 
 
 class BnnProgram:
     """What `lower_bnn` extracts from the graph."""
     estimator = "pathwise"
+    family = D.DIST_NORMAL     # of a LIK_NORMAL program: D.DIST_NORMAL | DIST_LAPLACE | DIST_CAUCHY (the observed variable's distribution)
     scale_learnable = False
     scale_head = None          # (transform, a, b) of a scale head: sigma = a + b g(second head); the last layer then has 2 C rows
 
@@ -58,6 +62,8 @@ class BnnProgram:
                  likelihood=("categorical", "bernoulli", "normal")[self.likelihood], latents=[t["name"] for t in self.tensors])
         if self.likelihood == LIK_NORMAL:
             s["scale"] = "head" if self.scale_head else "learnable" if self.scale_learnable else "constant"
+            if self.family != D.DIST_NORMAL:
+                s["family"] = LIKELIHOOD_FAMILIES[self.family].lower()
         s["priors"] = {t["name"]: t.get("prior", "normal") for t in self.tensors}
         return s
 
@@ -109,26 +115,26 @@ def _depends_on_latent(e):
 LEARNABLE_SCALE_TRANSFORMS = ("softplus", "exp", "sigmoid")          # what keeps sigma off zero whatever a step does to its root
 
 
-def _normal_scale(L, k, links, n_outputs, joint_roots=()):
+def _normal_scale(L, k, links, n_outputs, joint_roots=(), family="Normal"):
     """the scale of the Normal likelihood -> (first entry of the uniform table, stride, learnable): one for every output (stride 0) or
     one per output (stride 1); a constant (an entry among the table's constants), or a + b g(root) of a learnable root of the joint
     model with g one of softplus / exp / sigmoid, a >= 0, b > 0 (an entry with a gradient: bsvi_bnn_create_normal_learnable)"""
     e = links["scale"].expr
     m = L.match_uniform(L.from_expr(e, L.p_value))
     if m is None:
-        raise LoweringError("bnn path: the scale of the Normal likelihood %r must be a constant or a transform of one" % k.name)
+        raise LoweringError("bnn path: the scale of the %s likelihood %r must be a constant or a transform of one" % (family, k.name))
     leaf, g, a, b = m
     learnable = leaf.op == "root" and leaf.attr.learnable
     if learnable and (g not in LEARNABLE_SCALE_TRANSFORMS or not (a >= 0 and b > 0) or leaf.attr not in joint_roots):
         # (a bare root: a step can carry it through zero)
-        raise LoweringError("bnn path: the scale of the Normal likelihood %r is learnable (it must be a constant of the model, or "
+        raise LoweringError("bnn path: the scale of the %s likelihood %r is learnable (it must be a constant of the model, or "
                             "a + b * g(root) of a learnable root of the joint model with g one of %s, a >= 0 and b > 0)"
-                            % (k.name, " / ".join(LEARNABLE_SCALE_TRANSFORMS)))
+                            % (family, k.name, " / ".join(LEARNABLE_SCALE_TRANSFORMS)))
     size = int(np.prod(leaf.shape))
     shape = tuple(int(d) for d in leaf.shape)
     if size != 1 and (size != n_outputs or shape[-1] != 1):
-        raise LoweringError("bnn path: the scale of the Normal likelihood %r has shape %r: neither one value nor one per output [%d, 1]"
-                            % (k.name, shape[1:], n_outputs))
+        raise LoweringError("bnn path: the scale of the %s likelihood %r has shape %r: neither one value nor one per output [%d, 1]"
+                            % (family, k.name, shape[1:], n_outputs))
     is_param, k0 = L.uniform_entries(leaf, g, a, b)
     return k0, (1 if size > 1 else 0), bool(is_param)
 
@@ -137,7 +143,7 @@ def _has_matmul(e):
     return (e.op == "call" and e.attr[0] == "matmul") or any(_has_matmul(a) for a in e.args if hasattr(a, "op"))
 
 
-def _scale_head(k, e):
+def _scale_head(k, e, family="Normal"):
     """the scale of a Normal likelihood computed from a matmul: a + b g(second head) -> (g, a, b, the head's chain, its x), or the cause"""
     def number(x):
         return float(np.asarray(x.attr).reshape(-1)[0]) if x.op == "const" and np.size(x.attr) == 1 else None
@@ -163,13 +169,13 @@ def _scale_head(k, e):
             what = "missing"
         except LoweringError:
             pass
-        raise LoweringError("bnn path: the transform of the scale head of the Normal likelihood %r is %s (the scale must be %s)" % (k.name, what, form))
+        raise LoweringError("bnn path: the transform of the scale head of the %s likelihood %r is %s (the scale must be %s)" % (family, k.name, what, form))
     if not (a >= 0 and b > 0):
-        raise LoweringError("bnn path: the scale head of the Normal likelihood %r has a = %g, b = %g (the scale must be %s)" % (k.name, a, b, form))
+        raise LoweringError("bnn path: the scale head of the %s likelihood %r has a = %g, b = %g (the scale must be %s)" % (family, k.name, a, b, form))
     try:
         chain, x_var = _chain(core.args[0])
     except LoweringError as err:
-        raise LoweringError("bnn path: the scale head of the Normal likelihood %r is not a chain of matmul layers (%s)" % (k.name, err)) from None
+        raise LoweringError("bnn path: the scale head of the %s likelihood %r is not a chain of matmul layers (%s)" % (family, k.name, err)) from None
     return core.attr[0], float(a), float(b), chain, x_var
 
 
@@ -194,21 +200,22 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     q_random = [v for v in q_flat if _is_random(v)]
     # (a regression model whose noise scale is a latent is named as such, before the posterior of that latent is looked at)
     for v in joint._flatten():
-        if _is_random(v) and v.distribution.kind == D.DIST_NORMAL and v.is_observed and getattr(v, "has_random_dataset", False) \
+        if _is_random(v) and v.distribution.kind in LIKELIHOOD_FAMILIES and v.is_observed and getattr(v, "has_random_dataset", False) \
                 and _depends_on_latent(v.link.expressions()["scale"].expr) and not _has_matmul(v.link.expressions()["scale"].expr):
             # (a scale computed from a matmul is a scale head, or refused below with its own cause)
-            raise LoweringError("bnn path: the scale of the Normal likelihood %r is a latent variable or computed from one "
-                                "(it must be a constant of the model)" % v.name)
+            raise LoweringError("bnn path: the scale of the %s likelihood %r is a latent variable or computed from one "
+                                "(it must be a constant of the model)" % (LIKELIHOOD_FAMILIES[v.distribution.kind], v.name))
     if not q_random or any(v.distribution.kind != D.DIST_NORMAL for v in q_random):
         raise LoweringError("bnn path: the posterior must be mean-field Normal variables")
     p_random = [v for v in joint._flatten() if _is_random(v)]
-    # the likelihood: a Categorical / Binomial(1) over logits, or — regression — an OBSERVED Normal whose loc is the chain
+    # the likelihood: a Categorical / Binomial(1) over logits, or — regression — an OBSERVED Normal, Laplace or Cauchy whose loc is the chain
     liks = [v for v in p_random if v.distribution.kind in (D.DIST_CATEGORICAL, D.DIST_BINOMIAL, D.DIST_BERNOULLI)
-            or (v.distribution.kind == D.DIST_NORMAL and v.is_observed)]
+            or (v.distribution.kind in LIKELIHOOD_FAMILIES and v.is_observed)]
     if len(liks) != 1:
         raise LoweringError("bnn path: expected one matmul likelihood")
     k = liks[0]
-    normal = k.distribution.kind == D.DIST_NORMAL
+    normal = k.distribution.kind in LIKELIHOOD_FAMILIES      # (LIK_NORMAL: the loc-scale regression likelihood, whatever its family)
+    family = LIKELIHOOD_FAMILIES.get(k.distribution.kind)
     if not k.is_observed or not k.has_random_dataset:
         raise LoweringError("bnn path: the likelihood must be observed through an EmpiricalVariable of labels")
     links = k.link.expressions()
@@ -216,7 +223,7 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
         try:
             chain, x_var = _chain(links["loc"].expr)
         except LoweringError as err:
-            raise LoweringError("bnn path: the loc of the Normal likelihood %r is not a chain of matmul layers (%s)" % (k.name, err)) from None
+            raise LoweringError("bnn path: the loc of the %s likelihood %r is not a chain of matmul layers (%s)" % (family, k.name, err)) from None
     else:
         if "logits" not in links:
             raise LoweringError("bnn path: the likelihood must be parameterised by logits")
@@ -226,15 +233,15 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     # a scale head: sigma = a + b g(BF.matmul(weights_scale, H) [+ b_scale]) on the trunk H of the loc head
     head = None
     if normal and _depends_on_latent(links["scale"].expr):
-        g, ha, hb, chain_s, x_s = _scale_head(k, links["scale"].expr)
+        g, ha, hb, chain_s, x_s = _scale_head(k, links["scale"].expr, family)
         same = len(chain_s) == len(chain) and x_s is x_var and all(
             ls[0] is ll[0] and ls[1] is ll[1] and ls[2] == ll[2] for ls, ll in zip(chain_s[:-1], chain[:-1]))
         if not same:
-            raise LoweringError("bnn path: the two heads of the Normal likelihood %r stand on different trunks (both must be "
-                                "BF.matmul(weights, H) [+ bias] on the same H: the same x, the same latent variables and activations)" % k.name)
+            raise LoweringError("bnn path: the two heads of the %s likelihood %r stand on different trunks (both must be "
+                                "BF.matmul(weights, H) [+ bias] on the same H: the same x, the same latent variables and activations)" % (family, k.name))
         Ws, bs = chain_s[-1][0], chain_s[-1][1]
         if (bs is None) != (chain[-1][1] is None):
-            raise LoweringError("bnn path: one head of the Normal likelihood %r has a bias and the other has none (either both or neither)" % k.name)
+            raise LoweringError("bnn path: one head of the %s likelihood %r has a bias and the other has none (either both or neither)" % (family, k.name))
         head = (g, ha, hb, Ws, bs)
     latents = []
     for W, b, _ in chain:
@@ -246,8 +253,8 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
         trunk_names = [v.name for v in latents[:len(latents) - (2 if chain[-1][1] is not None else 1)]]
         for v in head_vars:
             if v.name in trunk_names or sum(1 for o in head_vars if o.name == v.name) > 1:
-                raise LoweringError("bnn path: the head tensor %r of the Normal likelihood %r is used twice (in the trunk, or by both heads)"
-                                    % (v.name, k.name))
+                raise LoweringError("bnn path: the head tensor %r of the %s likelihood %r is used twice (in the trunk, or by both heads)"
+                                    % (v.name, family, k.name))
         latents += [v for v in (head[3], head[4]) if v is not None]
     names = [v.name for v in latents]
     if len(set(names)) != len(names):
@@ -348,8 +355,8 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
         if head[4] is not None and (by_name[head[4].name]["rows"], by_name[head[4].name]["cols"]) != (ts["rows"], 1):
             raise LoweringError("bnn path: bias %r must be a column [%d, 1]" % (head[4].name, ts["rows"]))
         if Ym.shape[1] != width or ts["rows"] != width:
-            raise LoweringError("bnn path: the targets have %d columns but the heads of the Normal likelihood %r have %d (loc) and %d (scale) "
-                                "rows" % (Ym.shape[1], k.name, width, ts["rows"]))
+            raise LoweringError("bnn path: the targets have %d columns but the heads of the %s likelihood %r have %d (loc) and %d (scale) "
+                                "rows" % (Ym.shape[1], family, k.name, width, ts["rows"]))
         last.update(weights_scale=ts["name"], bias_scale=head[4].name if head[4] is not None else None)
     lik = LIK_NORMAL if normal else LIK_CATEGORICAL if k.distribution.kind == D.DIST_CATEGORICAL else LIK_BERNOULLI
     scale_entries = None
@@ -359,7 +366,7 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
         if head:
             layers[-1]["rows"] = 2 * width
         else:
-            scale_entries = _normal_scale(L, k, links, width, joint_roots)
+            scale_entries = _normal_scale(L, k, links, width, joint_roots, family)
     if lik == LIK_BERNOULLI:
         if width != 1:
             raise LoweringError("bnn path: a Bernoulli/Binomial likelihood needs a single output")
@@ -386,6 +393,8 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     prog.layers, prog.tensors, prog.n_rows = layers, tensors, R
     prog.n_features, prog.n_classes, prog.dataset_size, prog.batch_size = P, width, DS, int(ind_x.batch_size)
     prog.likelihood = lik
+    if normal:
+        prog.family = k.distribution.kind
     if head:
         prog.scale_head = head[:3]
     elif normal:
@@ -482,6 +491,8 @@ class CompiledBnn:
         else:
             native.check(lib.bsvi_bnn_create(C.byref(d), C.byref(handle)))
         self.handle = handle
+        if p.likelihood == LIK_NORMAL and getattr(p, "family", D.DIST_NORMAL) != D.DIST_NORMAL:      # (without the call the family is Normal)
+            native.check(lib.bsvi_bnn_set_likelihood_family(handle, int(p.family)))
         row_prior = np.ascontiguousarray(getattr(p, "row_prior", np.zeros(0)), dtype=np.uint8)
         if (row_prior != D.DIST_NORMAL).any():             # (without the call every row is Normal)
             native.check(lib.bsvi_bnn_set_row_priors(handle, row_prior.ctypes.data_as(C.c_void_p), row_prior.size))
@@ -658,7 +669,8 @@ class CompiledBnn:
         — the draw of a training launch at the same (seed, offset, sample_base), or `noise` ([n_rows, N], or named as the oracle
         takes it) — and the chain forward on every row of `x`.  Device tensors: "probs" [N, M, C] (softmax probabilities | sigmoid of
         the logit | the Normal's loc), "mean" [M, C] (their mean over the samples, fixed order), "var" [M, C] (Normal likelihood only:
-        population variance of the loc over the samples + sigma^2; with a scale head + the mean over the samples of sigma^2), and on request
+        population variance of the loc over the samples + sigma^2; with a scale head + the mean over the samples of sigma^2; a Laplace
+        likelihood adds 2 sigma^2, a Cauchy likelihood has no variance and no "var" key), and on request
         "outputs" [N, M, C] (logits | loc; a scale head adds "scale" [N, M, C], sigma of every sample and row), "draws"
         [N, M, C] (one draw of the likelihood per sample and row: one-hot | 0 / 1 | real) and "noise" [n_rows, N] (the eps drawn).
         offset=None draws from the sampling range (1 << 62) + tick, as the samplers of the engine do; `self.iteration`, `self.out` and
@@ -689,7 +701,8 @@ class CompiledBnn:
                                                       dtype=torch.uint8, device=dev))
         new = lambda *shape: torch.empty(shape, device=dev)
         probs, mean = new(N, M, Cn), new(M, Cn)
-        var = new(M, Cn) if p.likelihood == LIK_NORMAL else None
+        # (a Cauchy likelihood has no variance: no "var" key)
+        var = new(M, Cn) if p.likelihood == LIK_NORMAL and getattr(p, "family", D.DIST_NORMAL) != D.DIST_CAUCHY else None
         heads = bool(getattr(p, "scale_head", None))        # (z_out is then [N, M, 2 C]: the loc, then sigma itself)
         outputs = new(N, M, 2 * Cn if heads else Cn) if want_outputs else None
         draws = new(N, M, Cn) if want_draws else None

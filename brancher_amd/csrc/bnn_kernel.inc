@@ -19,6 +19,11 @@
 //     delta_c = wgt u_c / sigma_c,      delta_(C + c) = wgt (u_c^2 - 1) / sigma_c * b g'(z_(C + c))
 // so that the reverse sweep, bnn_small, the second product and the row sums carry the gradient to the four head tensors as they carry
 // any delta (no sigma table behind the targets, none of the scale_learn machinery).  BParams::C stays the number of TARGETS per row.
+// The observed variable may be a Laplace or a Cauchy variable in the place of the Normal (bsvi_bnn_set_likelihood_family; BParams::family,
+// a literal in the generated kernels): with psi the family's score, -|u| - log(2 sigma) and psi = sign(u), or -log(1 + u^2) - log(pi sigma)
+// and psi = 2 u / (1 + u^2), and at every site  delta_c = wgt psi / sigma_c,  d f / d sigma_c = wgt (u psi - 1) / sigma_c  (the Normal:
+// psi = u) — so a learnable sigma's sums and a scale head's second delta are what they were with u psi in the place of u^2, and
+// bnn_mid_gen's sigma elements, which sum delta_c (y_c - z_c) = wgt u psi, need nothing.  The Normal arms keep their text.
 // All latent scalars form ONE vector of R rows (weights1 first: H_1 x P
 // rows r = h * P + p, then the other tensors); row r draws eps from the dense path's Philox counters (sample, r >> 2), so the
 // noise of a model is one [R][N] matrix as on the dense path, and reads its four parameters (q loc, q scale, prior loc, prior
@@ -89,6 +94,9 @@ struct BParams {
     // the prior of every row (bsvi_bnn_set_row_priors): BSVI_DIST_NORMAL | _LAPLACE | _CAUCHY, one byte per row, padded with Normal to
     // a whole quad.  Read by the MIXED instantiations of bnn_draw and bnn_row_sums alone: a model whose rows are all Normal never looks
     const uint8_t* row_kind;
+    // the family of the loc-scale likelihood (bsvi_bnn_set_likelihood_family): BSVI_DIST_NORMAL | _LAPLACE | _CAUCHY, launch-uniform.
+    // Behind every other member, so that no field the kernels of the models without it read has moved
+    uint32_t family;
 };
 
 __device__ __forceinline__ float bnn_act(uint32_t act, float v) {
@@ -120,6 +128,21 @@ __device__ __forceinline__ float bnn_head_sigma(const uint32_t t, const float a,
     else { g = raw > 20.0f ? raw : log1pf(expf(raw)); dg = raw > 20.0f ? 1.0f : sigmoidf_(raw); }
     dsigma = b * dg;
     return a + b * g;
+}
+
+// the Laplace and Cauchy likelihoods in u = (y - z) / sigma: the value without its constant and the score psi(u) = -d value / d u, so that
+// every site seeds d f / d z = wgt psi / sigma and d f / d sigma = wgt (u psi - 1) / sigma as the Normal does with psi = u
+//     Laplace  -|u|,  psi = sign(u) with sign(0) = 0 (torch's abs backward);      Cauchy  -log(1 + u^2),  psi = 2 u / (1 + u^2)
+// (the hardware logarithm, as bnn_prior_value: the sum 1 + u^2 rounds to 6e-8 absolute, what any term of O(1) of the sample's sum does)
+__device__ __forceinline__ float bnn_family_value(const uint32_t family, const float u, float& psi) {
+    if (family == BSVI_DIST_LAPLACE) { psi = u > 0.0f ? 1.0f : (u < 0.0f ? -1.0f : 0.0f); return -fabsf(u); }
+    const float q = 1.0f + u * u;
+    psi = 2.0f * u / q;
+    return -__logf(q);
+}
+// ... and the constant of either beside -log sigma: -log 2 | -log pi
+__device__ __forceinline__ float bnn_family_const(const uint32_t family) {
+    return family == BSVI_DIST_LAPLACE ? -0.69314718055994530942f : -1.14472988584940017414f;
 }
 
 __device__ __forceinline__ float bnn_uniform_value(const BParams& Q, uint32_t k) {
@@ -192,7 +215,8 @@ __device__ __forceinline__ void bnn_head_body(const BParams& Q, const uint32_t i
         const float sigma = bnn_uniform_value(Q, Q.scale_u + i * Q.scale_stride);
         float* const sg = Q.lab + (size_t)Q.B_pad * Q.LC;
         sg[i] = sigma;
-        sg[Q.C + i] = -logf(sigma) - 0.91893853320467274178f;
+        if (Q.family == BSVI_DIST_NORMAL) sg[Q.C + i] = -logf(sigma) - 0.91893853320467274178f;
+        else sg[Q.C + i] = -logf(sigma) + bnn_family_const(Q.family);      // -log(2 sigma) | -log(pi sigma)
     }
     for (uint32_t k = i; k < 2u + Q.n_uniform_grad; k += n_threads) Q.partial[k] = 0.0f;
 }
@@ -355,12 +379,23 @@ __global__ void __launch_bounds__(256) bnn_upper(const BParams Q) {
             const float* const yb = Q.lab + (size_t)b * Q.LC;
             const uint32_t Ct = LL.rows / 2u;
             float s = 0.0f;
-            for (uint32_t c = 0; c < Ct; ++c) {
-                float ds;
-                const float sigma = bnn_head_sigma(Q.heads, Q.head_a, Q.head_b, Y(LL, Ct + c), ds), u = (yb[c] - Y(LL, c)) / sigma;
-                s += -0.5f * u * u - logf(sigma) - 0.91893853320467274178f;
-                Dl(LL, c) = wgt * u / sigma;
-                Dl(LL, Ct + c) = wgt * (u * u - 1.0f) / sigma * ds;
+            if (Q.family == BSVI_DIST_NORMAL) {
+                for (uint32_t c = 0; c < Ct; ++c) {
+                    float ds;
+                    const float sigma = bnn_head_sigma(Q.heads, Q.head_a, Q.head_b, Y(LL, Ct + c), ds), u = (yb[c] - Y(LL, c)) / sigma;
+                    s += -0.5f * u * u - logf(sigma) - 0.91893853320467274178f;
+                    Dl(LL, c) = wgt * u / sigma;
+                    Dl(LL, Ct + c) = wgt * (u * u - 1.0f) / sigma * ds;
+                }
+            } else {      // Laplace | Cauchy: the same seeds with the family's value and score (bnn_family_value)
+                const float kf = bnn_family_const(Q.family);
+                for (uint32_t c = 0; c < Ct; ++c) {
+                    float ds, psi;
+                    const float sigma = bnn_head_sigma(Q.heads, Q.head_a, Q.head_b, Y(LL, Ct + c), ds), u = (yb[c] - Y(LL, c)) / sigma;
+                    s += bnn_family_value(Q.family, u, psi) - logf(sigma) + kf;
+                    Dl(LL, c) = wgt * psi / sigma;
+                    Dl(LL, Ct + c) = wgt * (u * psi - 1.0f) / sigma * ds;
+                }
             }
             lik = wgt * s;
         } else if (Q.likelihood == BSVI_LIK_NORMAL) {
@@ -369,11 +404,21 @@ __global__ void __launch_bounds__(256) bnn_upper(const BParams Q) {
             const float* const yb = Q.lab + (size_t)b * Q.LC;
             const float* const sg = Q.lab + (size_t)Q.B_pad * Q.LC;
             float s = 0.0f;
-            for (uint32_t c = 0; c < LL.rows; ++c) {
-                const float sigma = sg[c], u = (yb[c] - Y(LL, c)) / sigma;
-                s += -0.5f * u * u + sg[LL.rows + c];
-                Dl(LL, c) = wgt * u / sigma;
-                if (Q.scale_learn) Q.sigt[((size_t)c * Q.B_pad + b) * Q.n_pad + n] = wgt * (u * u - 1.0f) / sigma;
+            if (Q.family == BSVI_DIST_NORMAL) {
+                for (uint32_t c = 0; c < LL.rows; ++c) {
+                    const float sigma = sg[c], u = (yb[c] - Y(LL, c)) / sigma;
+                    s += -0.5f * u * u + sg[LL.rows + c];
+                    Dl(LL, c) = wgt * u / sigma;
+                    if (Q.scale_learn) Q.sigt[((size_t)c * Q.B_pad + b) * Q.n_pad + n] = wgt * (u * u - 1.0f) / sigma;
+                }
+            } else {      // Laplace | Cauchy (bnn_family_value; the family's constant stands behind the targets as the Normal's does)
+                for (uint32_t c = 0; c < LL.rows; ++c) {
+                    float psi;
+                    const float sigma = sg[c], u = (yb[c] - Y(LL, c)) / sigma;
+                    s += bnn_family_value(Q.family, u, psi) + sg[LL.rows + c];
+                    Dl(LL, c) = wgt * psi / sigma;
+                    if (Q.scale_learn) Q.sigt[((size_t)c * Q.B_pad + b) * Q.n_pad + n] = wgt * (u * psi - 1.0f) / sigma;
+                }
             }
             lik = wgt * s;
         } else if (Q.likelihood == BSVI_LIK_CATEGORICAL) {
@@ -739,6 +784,7 @@ struct bsvi_bnn {
     bool scale_learn = false;    // ... parameter entries (bsvi_bnn_create_normal_learnable), else constants
     uint32_t heads = 0;          // a scale head (bsvi_bnn_create_normal_heads): its BSVI_UT_* transform; the last layer has 2 C rows
     float head_a = 0.0f, head_b = 1.0f;
+    uint32_t family = BSVI_DIST_NORMAL;      // the loc-scale likelihood's family (bsvi_bnn_set_likelihood_family): Normal, Laplace or Cauchy
     uint8_t* row_kind = nullptr; // the prior of every row, in the blob (all Normal until bsvi_bnn_set_row_priors)
     bool mixed = false;          // some row is Laplace or Cauchy: the MIXED instantiations of bnn_draw / bnn_row_sums
     mutable std::atomic<bool> launched{false};      // a launch was made: the priors stay as they are
@@ -770,8 +816,41 @@ struct BnnUpperArgsSig { BnnUpperArgs a; float* sigt; };
 // the Normal likelihood of the two generated kernels (the text bnn_upper runs with loop bounds): targets [B_pad][C] in A.lab, then
 // sigma [C] and -log sigma - 1/2 log 2 pi [C] as bnn_head_body leaves them — the values of the uniform table, never a host copy
 // sig_terms (bnn_upper_gen with a learnable sigma): wgt (u^2 - 1) / sigma per (c, b, n) leaves for bnn_sig_rows
-static std::string bnn_normal_source(uint32_t C, uint32_t yl, bool sig_terms = false) {
-    char buf[1280];
+// the Laplace and Cauchy likelihoods of the generated kernels as text (bnn_family_value with the family a literal): what stands
+// between u and the sum, the value without its constant, and u psi(u)
+struct BnnFamilyText { const char* psi; const char* value; const char* upsi; };
+static BnnFamilyText bnn_family_text(uint32_t family) {
+    if (family == BSVI_DIST_LAPLACE) return {"const float psi = u > 0.0f ? 1.0f : (u < 0.0f ? -1.0f : 0.0f);", "-fabsf(u)", "fabsf(u)"};
+    // BSVI_BNN_CAUCHY_LOG=log1p: the library's log1pf in the place of the hardware logarithm (tools/bnn_likelihoods_timing.py measures both)
+    const char* e = getenv("BSVI_BNN_CAUCHY_LOG");
+    const bool lib = e && !strcmp(e, "log1p");
+    return {lib ? "const float uu = u * u, q = 1.0f + uu, psi = 2.0f * u / q;" : "const float q = 1.0f + u * u, psi = 2.0f * u / q;",
+            lib ? "-log1pf(uu)" : "-__logf(q)", "u * psi"};
+}
+
+static std::string bnn_normal_source(uint32_t C, uint32_t yl, bool sig_terms = false, uint32_t family = BSVI_DIST_NORMAL) {
+    char buf[1536];
+    if (family != BSVI_DIST_NORMAL) {
+        const BnnFamilyText t = bnn_family_text(family);
+        char sig[256];
+        snprintf(sig, sizeof sig, "                A.sigt[((size_t)c * A.B_pad + b) * A.n_pad + n] = wgt * (%s - 1.0f) / sigma;\n", t.upsi);
+        snprintf(buf, sizeof buf,
+                 "        {\n"
+                 "            const float* const yb = A.lab + (size_t)b * %uu;\n"
+                 "            const float* const sg = A.lab + (size_t)A.B_pad * %uu;\n"
+                 "            float sn = 0.0f;\n"
+                 "#pragma unroll\n"
+                 "            for (uint32_t c = 0; c < %uu; ++c) {\n"
+                 "                const float sigma = sg[c], u = (yb[c] - y[%uu + c]) / sigma;\n"
+                 "                %s\n"
+                 "                sn += %s + sg[%uu + c];\n"
+                 "                d[%uu + c] = wgt * psi / sigma;\n"
+                 "%s"
+                 "            }\n"
+                 "            lik = wgt * sn;\n"
+                 "        }\n", C, C, C, yl, t.psi, t.value, C, yl, sig_terms ? sig : "");
+        return std::string(buf);
+    }
     snprintf(buf, sizeof buf,
              "        {\n"
              "            const float* const yb = A.lab + (size_t)b * %uu;\n"
@@ -798,7 +877,29 @@ static std::string bnn_heads_source(const bsvi_bnn* p, uint32_t yl) {
     const char* g = p->heads == BSVI_UT_EXP ? "const float g = expf(raw), dg = g;"
                   : p->heads == BSVI_UT_SIGMOID ? "const float g = sigmoidf_(raw), dg = g * (1.0f - g);"
                   : "const float g = raw > 20.0f ? raw : log1pf(expf(raw)), dg = raw > 20.0f ? 1.0f : sigmoidf_(raw);";
-    char buf[1536];
+    char buf[1792];
+    if (p->family != BSVI_DIST_NORMAL) {
+        const BnnFamilyText t = bnn_family_text(p->family);
+        snprintf(buf, sizeof buf,
+                 "        {\n"
+                 "            const float* const yb = A.lab + (size_t)b * %uu;\n"
+                 "            const float ha = __uint_as_float(0x%08xu), hb = __uint_as_float(0x%08xu);\n"
+                 "            float sn = 0.0f;\n"
+                 "#pragma unroll\n"
+                 "            for (uint32_t c = 0; c < %uu; ++c) {\n"
+                 "                const float raw = y[%uu + c];\n"
+                 "                %s\n"
+                 "                const float sigma = ha + hb * g, u = (yb[c] - y[%uu + c]) / sigma;\n"
+                 "                %s\n"
+                 "                sn += %s - logf(sigma) + %s;\n"
+                 "                d[%uu + c] = wgt * psi / sigma;\n"
+                 "                d[%uu + c] = wgt * (%s - 1.0f) / sigma * (hb * dg);\n"
+                 "            }\n"
+                 "            lik = wgt * sn;\n"
+                 "        }\n", p->C, abits, bbits, p->C, yl + p->C, g, yl, t.psi, t.value,
+                 p->family == BSVI_DIST_LAPLACE ? "-0.69314718055994530942f" : "-1.14472988584940017414f", yl, yl + p->C, t.upsi);
+        return std::string(buf);
+    }
     snprintf(buf, sizeof buf,
              "        {\n"
              "            const float* const yb = A.lab + (size_t)b * %uu;\n"
@@ -890,7 +991,7 @@ static std::string bnn_upper_source(const bsvi_bnn* p) {
     s += std::string("        const float wgt = live ? A.lik_weight * (A.f_weight ? A.f_weight[n] : 1.0f) : 0.0f") +
          (p->d.likelihood == BSVI_LIK_NORMAL ? ";\n" : ", label = A.lab[b];\n") + "        float lik = 0.0f;\n";
     if (p->d.likelihood == BSVI_LIK_NORMAL) {
-        s += p->heads ? bnn_heads_source(p, yl) : bnn_normal_source(LL.rows, yl, p->scale_learn);
+        s += p->heads ? bnn_heads_source(p, yl) : bnn_normal_source(LL.rows, yl, p->scale_learn, p->family);
     } else if (p->d.likelihood == BSVI_LIK_CATEGORICAL) {
         s += "        {\n            float m = -INFINITY;\n#pragma unroll\n";
         s += fmt("            for (uint32_t c = 0; c < %uu; ++c) m = fmaxf(m, y[%uu + c]);\n", LL.rows, yl);
@@ -1045,7 +1146,7 @@ static std::string bnn_mid_source(const bsvi_bnn* p) {
     s += std::string("        const float wgt = live ? A.lik_weight * (A.f_weight ? A.f_weight[n] : 1.0f) : 0.0f") +
          (p->d.likelihood == BSVI_LIK_NORMAL ? ";\n" : ", label = A.lab[b];\n") + "        float lik = 0.0f;\n";
     if (p->d.likelihood == BSVI_LIK_NORMAL) {
-        s += p->heads ? bnn_heads_source(p, yl) : bnn_normal_source(LL.rows, yl);
+        s += p->heads ? bnn_heads_source(p, yl) : bnn_normal_source(LL.rows, yl, false, p->family);
     } else if (p->d.likelihood == BSVI_LIK_CATEGORICAL) {
         s += "        {\n            float m = -INFINITY;\n#pragma unroll\n";
         s += fmt("            for (uint32_t c = 0; c < %uu; ++c) m = fmaxf(m, y[%uu + c]);\n", LL.rows, yl);
@@ -1371,6 +1472,20 @@ extern "C" int bsvi_bnn_set_row_priors(bsvi_bnn* p, const uint8_t* kinds, uint32
     return BSVI_OK;
 }
 
+// the family of the loc-scale likelihood: Normal (what every regression handle is without this call), Laplace or Cauchy.  Before the
+// first launch only — the generated kernels carry the family as a literal and are compiled at the first launch
+extern "C" int bsvi_bnn_set_likelihood_family(bsvi_bnn* p, uint32_t kind) {
+    if (!p) return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_likelihood_family: null handle");
+    if (p->d.likelihood != BSVI_LIK_NORMAL)
+        return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_likelihood_family: the handle is a classifier's (the family is that of a model made by bsvi_bnn_create_normal*)");
+    if (kind != BSVI_DIST_NORMAL && kind != BSVI_DIST_LAPLACE && kind != BSVI_DIST_CAUCHY)
+        return fail(BSVI_ERR_UNSUPPORTED, "bsvi_bnn_set_likelihood_family: the likelihood is Normal, Laplace or Cauchy");
+    if (p->launched.load() || p->jit_state || p->mid_state)
+        return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_likelihood_family: the model was launched already (set the family before the first launch)");
+    p->family = kind;
+    return BSVI_OK;
+}
+
 extern "C" void bsvi_bnn_destroy(bsvi_bnn* p) {
     if (!p) return;
     if (p->dev_blob) (void)hipFree(p->dev_blob);
@@ -1458,7 +1573,7 @@ static int bnn_fill(const bsvi_bnn* p, const bsvi_bnn_args* a, BParams& Q, BnnLa
     Q.sample_base = a->sample_base; Q.NC = L.NC; Q.n_uniform_grad = p->d.n_uniform_grad; Q.likelihood = p->d.likelihood;
     Q.estimator = p->d.estimator; Q.exact = p->exact ? 1u : 0u; Q.act_width = (uint32_t)p->act_floats;
     Q.LC = p->LC; Q.scale_u = p->scale_u; Q.scale_stride = p->scale_stride; Q.scale_learn = p->scale_learn ? 1u : 0u;
-    Q.heads = p->heads; Q.head_a = p->head_a; Q.head_b = p->head_b;
+    Q.heads = p->heads; Q.head_a = p->head_a; Q.head_b = p->head_b; Q.family = p->family;
     Q.lik_weight = p->d.lik_weight; Q.prior_weight = p->d.prior_weight; Q.entropy_weight = p->d.entropy_weight;
     Q.seed_lo = (uint32_t)a->seed; Q.seed_hi = (uint32_t)(a->seed >> 32); Q.offset_lo = (uint32_t)a->offset; Q.offset_hi = (uint32_t)(a->offset >> 32);
     Q.noise_in = a->noise_dev; Q.noise_out = a->noise_out_dev; Q.indices_in = a->indices_dev; Q.indices_out = a->indices_out_dev;
@@ -1724,8 +1839,23 @@ __global__ void __launch_bounds__(256) bnn_predict_fwd(const BParams Q, const Bn
                 for (uint32_t c0 = 0; c0 < C; c0 += 4u) {
                     const u32x4 w = philox4x32(Q.sample_base + n, m, Q.offset_lo, Q.offset_hi, Q.seed_lo ^ BNN_KEY_PREDICT, Q.seed_hi ^ (c0 >> 2));
                     float e[4];
-                    box_muller_fast(w.x, w.y, e[0], e[1]);
-                    box_muller_fast(w.z, w.w, e[2], e[3]);
+                    if (Q.family == BSVI_DIST_NORMAL) {
+                        box_muller_fast(w.x, w.y, e[0], e[1]);
+                        box_muller_fast(w.z, w.w, e[2], e[3]);
+                    } else {
+                        // Laplace | Cauchy: ONE word per output, word c & 3 of the call the Normal's output c reads (philox.h) — a word of
+                        // its own for every output, so that no two outputs of a row share a draw.  The library's draws of the two
+                        // families (dist_math.h, sample_from_noise_generic): Laplace -sign(v) log1p(-|v|) of the uniform base noise v
+                        const uint32_t wd[4] = {w.x, w.y, w.z, w.w};
+                        for (uint32_t k = 0; k < 4u; ++k) {
+                            if (Q.family == BSVI_DIST_LAPLACE) {
+                                const float v = laplace_noise(wd[k]);
+                                e[k] = -(v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f)) * log1pf(-fabsf(v));
+                            } else {
+                                e[k] = cauchy_noise(wd[k]);
+                            }
+                        }
+                    }
                     for (uint32_t c = c0; c < C && c < c0 + 4u; ++c) V.draw_out[at + c] = Y(cur, c) + (Q.heads ? sp[c] : V.sg[c]) * e[c - c0];
                 }
             }
@@ -1777,12 +1907,15 @@ __global__ void __launch_bounds__(256) bnn_predict_reduce(const BParams Q, const
             const double d = (double)src[(size_t)n * V.p_stride] - mean, sn = (double)sg[(size_t)n * V.sig_stride];
             q += d * d; s2 += sn * sn;
         }
-        V.var_out[at] = (float)(q / (double)Q.n_local + s2 / (double)Q.n_local);
+        // (a Laplace likelihood's variance is 2 sigma^2)
+        if (Q.family == BSVI_DIST_LAPLACE) V.var_out[at] = (float)(q / (double)Q.n_local + 2.0 * s2 / (double)Q.n_local);
+        else V.var_out[at] = (float)(q / (double)Q.n_local + s2 / (double)Q.n_local);
     } else if (V.var_out) {
         double q = 0.0;
         for (uint32_t n = 0; n < Q.n_local; ++n) { const double d = (double)src[(size_t)n * V.p_stride] - mean; q += d * d; }
         const double sigma = (double)V.sg[c];
-        V.var_out[at] = (float)(q / (double)Q.n_local + sigma * sigma);
+        if (Q.family == BSVI_DIST_LAPLACE) V.var_out[at] = (float)(q / (double)Q.n_local + 2.0 * sigma * sigma);
+        else V.var_out[at] = (float)(q / (double)Q.n_local + sigma * sigma);
     }
 }
 
@@ -1829,6 +1962,7 @@ extern "C" int bsvi_bnn_predict(const bsvi_bnn* p, const bsvi_bnn_predict_args* 
     if (!a->params_dev && p->d.n_params) return fail(BSVI_ERR_INVALID, "bsvi_bnn_predict: params_dev is null");
     if (a->var_out && p->d.likelihood != BSVI_LIK_NORMAL)
         return fail(BSVI_ERR_INVALID, "bsvi_bnn_predict: var_out is for the Normal likelihood (a classifier's variance is p (1 - p) of mean_out)");
+    if (a->var_out && p->family == BSVI_DIST_CAUCHY) return fail(BSVI_ERR_UNSUPPORTED, "bsvi_bnn_predict: the Cauchy likelihood has no variance");
     const bsvi_bnn_select::PredictLayout L = bnn_predict_layout(p, a->n_samples_local, a->n_rows, a->rows_per_pass);
     if ((uint64_t)L.NC * (uint64_t)std::max(p->Kp, L.rows_pass) >= (1ull << 31))
         return fail(BSVI_ERR_UNSUPPORTED, "bsvi_bnn_predict: number_samples x hidden units x max(features, rows_per_pass) beyond the 32-bit index range of the product kernels");
@@ -1852,7 +1986,7 @@ extern "C" int bsvi_bnn_predict(const bsvi_bnn* p, const bsvi_bnn_predict_args* 
     Q.Kp = p->Kp; Q.P_ld = p->P_ld; Q.n_local = a->n_samples_local; Q.n_pad = L.n_pad; Q.n_global = a->n_samples_local;
     Q.sample_base = a->sample_base; Q.NC = L.NC; Q.likelihood = p->d.likelihood;
     Q.LC = p->LC; Q.scale_u = p->scale_u; Q.scale_stride = p->scale_stride;
-    Q.heads = p->heads; Q.head_a = p->head_a; Q.head_b = p->head_b;
+    Q.heads = p->heads; Q.head_a = p->head_a; Q.head_b = p->head_b; Q.family = p->family;
     Q.seed_lo = (uint32_t)a->seed; Q.seed_hi = (uint32_t)(a->seed >> 32); Q.offset_lo = (uint32_t)a->offset; Q.offset_hi = (uint32_t)(a->offset >> 32);
     Q.noise_in = a->noise_dev; Q.noise_out = a->noise_out;
     Q.rowp = (float*)(ws + L.rowp); Q.Wsm = (float*)(ws + L.Wsm);

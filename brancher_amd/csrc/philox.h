@@ -14,7 +14,9 @@
 // stream of its own:  c0 = global sample index, c1 = row m of the caller's x, c2 / c3 = the 64-bit offset, key word k0 = seed low ^
 // 0x2545f491 (another constant than the three of the minibatch / drawn-data streams, and not 0: no stream of the same seed has this
 // key), k1 = seed high ^ call.  Categorical and Bernoulli read u01(word 0) of call 0; the Normal likelihood's output c takes normal
-// c & 3 of the four box_muller_fast normals ((x, y) -> 0, 1; (z, w) -> 2, 3) of call c >> 2.  The weights of that pass are the BNN
+// c & 3 of the four box_muller_fast normals ((x, y) -> 0, 1; (z, w) -> 2, 3) of call c >> 2.  A Laplace or Cauchy likelihood's output c
+// takes ONE word, word c & 3 (x, y, z, w) of the same call c >> 2, through laplace_noise / cauchy_noise (bsvi_device.h) — the Laplace
+// draw is -sign(v) log1p(-|v|) of that uniform base noise v, the Cauchy draw the tangent itself.  The weights of that pass are the BNN
 // path's ordinary draw (c1 = (row >> 2) | 0x40000000, the seed as it is).
 #pragma once
 #if !defined(__HIPCC_RTC__)

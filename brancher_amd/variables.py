@@ -19,6 +19,7 @@ is missing.
 from abc import ABC, abstractmethod
 from collections.abc import Hashable, Iterable
 import warnings
+import zlib
 
 import numpy as np
 
@@ -147,8 +148,15 @@ class Variable(BrancherClass):
     def __repr__(self):
         return "{}({!r})".format(type(self).__name__, self.name)
 
-    # identity semantics: variables are dict keys everywhere, as in the reference
-    __hash__ = object.__hash__
+    # identity semantics: variables are dict keys everywhere, as in the reference.  The hash is a function of the NAME (fixed at its
+    # first use; equality stays identity, so two variables of one name merely share a bucket), not of the object's address: the graph is
+    # held in sets (`parents`, `model.variables`), whose iteration order is the order of every sum over them — in single precision the
+    # order of the rounding.  Hashed by address, the same model summed differently from one process to the next
+    def __hash__(self):
+        h = self.__dict__.get("_name_hash")
+        if h is None:
+            h = self.__dict__["_name_hash"] = zlib.crc32(str(self.name).encode("utf-8"))
+        return h
 
     def __eq__(self, other):
         return self is other

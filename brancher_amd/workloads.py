@@ -873,7 +873,7 @@ def build_bayesian_neural_network(api, dataset_size=48, batch_size=30, n_feature
 def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_hidden=9, n_outputs=1, hidden2=0, activation="tanh",
                          sigma=0.5, data="integers", bias=True, seed=0, prior_scale=2., q_scale=0.1, q_scale1=None, q_loc_scale=0.5,
                          widths=None, activations=None, learnable_sigma=False, sigma_init=None, prior="normal", prior_loc=0.,
-                         scale_head=None, scale_floor=0.05):
+                         scale_head=None, scale_floor=0.05, likelihood="normal"):
     """The regression model of the Bayesian-neural-network family: the network of `build_bayesian_neural_network` (latent weight
     matrices and biases under a mean-field Normal posterior) as the loc of an observed Normal,
     `y ~ NormalVariable(matmul(weights2, act(matmul(weights1, x) + b1)) + b2, sigma)`, the targets [DS, C, 1] an EmpiricalVariable that
@@ -890,8 +890,13 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
     prior="laplace").  scale_head: "softplus" / "exp" / "sigmoid" — heteroscedastic regression: a second head `weights_scale` (and
     `b_scale`) on the trunk of the last layer, `y ~ Normal(loc head, scale_floor + g(scale head))`, latents like the rest (prior may
     be a dict that names them); the teacher's noise scale then depends on the input through a head of its own, and sigma / learnable_sigma
-    are not used.  Without these keywords every model is built draw for draw as before."""
+    are not used.  likelihood: "normal", "laplace" (median / L1 regression: an observed `LaplaceVariable`) or "cauchy" (the heavy-tailed
+    fit: an observed `CauchyVariable`) — the family of y, with every form of the scale above; the teacher's noise is then drawn from that
+    family at scale sigma.  Without these keywords every model is built draw for draw as before."""
     BF = api.BF
+    if likelihood not in ("normal", "laplace", "cauchy"):
+        raise ValueError("likelihood is \"normal\", \"laplace\" or \"cauchy\"")
+    Observed = dict(normal=api.NormalVariable, laplace=api.LaplaceVariable, cauchy=api.CauchyVariable)[likelihood]
     prior_of = _bnn_prior(api, prior, prior_loc, prior_scale)
     if scale_head not in (None, "softplus", "exp", "sigmoid"):
         raise ValueError("scale_head is None, \"softplus\", \"exp\" or \"sigmoid\"")
@@ -924,7 +929,9 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
         g = dict(softplus=np_acts["softplus"], exp=np.exp, sigmoid=np_acts["sigmoid"])[scale_head]
         ws = 0.5 * rng.normal(0., 1., (n_outputs, trunk.shape[1])) / np.sqrt(max((trunk ** 2).mean(axis=0).sum(), 1e-6))
         sig = scale_floor + g(trunk @ ws.T - 1.)
-    Y = (h + sig * rng.normal(0., 1., h.shape)).astype(np.float32).reshape(dataset_size, n_outputs, 1)
+    teacher_noise = dict(normal=lambda: rng.normal(0., 1., h.shape), laplace=lambda: rng.laplace(0., 1., h.shape),
+                         cauchy=lambda: rng.standard_cauchy(h.shape))[likelihood]()
+    Y = (h + sig * teacher_noise).astype(np.float32).reshape(dataset_size, n_outputs, 1)
     if q_scale1 is None:
         q_scale1 = 0.4 / np.sqrt(float((X.astype(np.float64) ** 2).mean(axis=0).sum()))
     rng = np.random.RandomState(seed + 7)
@@ -954,7 +961,7 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
                                              "b_scale", learnable=True))
         q_vars.append(api.NormalVariable(q_loc_scale * sw * rng.normal(0., 1., (rows, cols)), sw * np.ones((rows, cols)),
                                          "weights_scale", learnable=True))
-        y = api.NormalVariable(layer, scale_floor + getattr(BF, scale_head)(raw), "y")
+        y = Observed(layer, scale_floor + getattr(BF, scale_head)(raw), "y")
         model = api.ProbabilisticModel([y])
         y.observe(targets)
         model.set_posterior_model(api.ProbabilisticModel(q_vars))
@@ -966,7 +973,7 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
     scale = float(sig[0]) if sig.size == 1 else sig.reshape(n_outputs, 1)
     if learnable_sigma == "exp":
         scale = BF.exp(api.RootVariable(np.log(scale), "y_log_scale", learnable=True))
-    y = api.NormalVariable(layer, scale, "y", learnable=bool(learnable_sigma is True))
+    y = Observed(layer, scale, "y", learnable=bool(learnable_sigma is True))
     model = api.ProbabilisticModel([y])
     y.observe(targets)
     model.set_posterior_model(api.ProbabilisticModel(q_vars))

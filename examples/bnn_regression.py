@@ -13,6 +13,8 @@ MI355X:
     python examples/bnn_regression.py --prior laplace    # LaplaceVariable(0, 0.5) on every weight and bias (the Bayesian lasso)
     python examples/bnn_regression.py --prior cauchy     # CauchyVariable(0, 0.5): heavy tails
     python examples/bnn_regression.py --scale-head       # input-dependent noise: a second head, sigma(x) = 0.05 + softplus(raw(x))
+    python examples/bnn_regression.py --likelihood laplace    # median (L1) regression: LaplaceVariable(chain, b, "y")
+    python examples/bnn_regression.py --likelihood cauchy     # the heavy-tailed fit for data with outliers: CauchyVariable(chain, gamma, "y")
 
 With --learn-sigma the model starts from a guess of 1.0 and learns the noise scale with the posterior (a learnable root `y_scale`
 behind a softplus in the joint model's parameter group, stepped from the second iteration on, as the reference steps it); the learned
@@ -23,6 +25,9 @@ run with --prior is a 64-8-1 network on minibatches of 512 rows, where the data 
 weights would return to their prior.  With --scale-head the noise level depends on the input: a second head `weights_scale`, `b_scale`
 on the hidden layer gives the scale of the Normal, `0.05 + BF.softplus(BF.matmul(weights_scale, hidden) + b_scale)`, latent like the
 rest; the teacher's noise varies from row to row, and the run prints how well the predicted scale follows the size of the residuals.
+With --likelihood the observed variable is a Laplace or a Cauchy variable over the same chain (it combines with every other switch): the
+teacher's noise is drawn from that family, so under "cauchy" a few targets lie far from the rest — the run prints the median absolute
+error beside the RMSE, which those few dominate.
 """
 import os
 import sys
@@ -50,6 +55,12 @@ if "--prior" in sys.argv[1:]:
     if PRIOR not in ("laplace", "cauchy"):
         sys.exit("--prior laplace | cauchy")
     KW.update(prior=PRIOR, prior_scale=0.5, dataset_size=2048, batch_size=512, n_features=64, n_hidden=8)
+LIKELIHOOD = "normal"
+if "--likelihood" in sys.argv[1:]:
+    LIKELIHOOD = (sys.argv[sys.argv.index("--likelihood") + 1:] or [""])[0]
+    if LIKELIHOOD not in ("laplace", "cauchy"):
+        sys.exit("--likelihood laplace | cauchy")
+    KW.update(likelihood=LIKELIHOOD)
 
 
 def dataset_of(variable):
@@ -65,11 +76,15 @@ def posterior_mean_rmse(model):
     p = engine.compile_model(model).named_params()
     hidden = np.tanh(X @ p["weights1_loc"].reshape(KW["n_hidden"], -1).T + p["b1_loc"].reshape(1, -1))
     pred = hidden @ p["weights2_loc"].reshape(KW["n_outputs"], -1).T + p["b2_loc"].reshape(1, -1)
+    if LIKELIHOOD != "normal":
+        print("    median |error| of the posterior-mean prediction: %.3f" % float(np.median(np.abs(pred - Y))))
     return float(np.sqrt(np.mean((pred - Y) ** 2)))
 
 
 model = W.build_bnn_regression(W.native_api(), **KW)
 print("engine: %s, data path %s" % (type(engine.compile_model(model)).__name__, engine.compile_model(model).data_path()))
+if LIKELIHOOD != "normal":
+    print("likelihood:", engine.compile_model(model).program.summary()["family"])
 if PRIOR:
     print("priors:", engine.compile_model(model).program.summary()["priors"])
 print("RMSE of the posterior-mean prediction before training: %.3f (noise scale %s)"

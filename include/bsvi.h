@@ -632,6 +632,20 @@ int bsvi_bnn_create_normal_heads(const bsvi_bnn_desc* desc, uint32_t transform, 
  * a Cauchy row  prior_weight (-log1p(u^2) - log(pi) - log(s0));  their gradients are per-sample sums taken in a fixed order inside the
  * launches that walk every (row, sample) anyway.  The posterior stays mean-field Normal.  No struct changes, the ABI version stays. */
 int bsvi_bnn_set_row_priors(bsvi_bnn* b, const uint8_t* kinds, uint32_t n_rows);
+/* The FAMILY of the regression likelihood (desc->likelihood stays BSVI_LIK_NORMAL, the library's loc-scale likelihood): kind is
+ * BSVI_DIST_NORMAL (a no-op: what every such handle is without this call), BSVI_DIST_LAPLACE or BSVI_DIST_CAUCHY — the reference's
+ * observed LaplaceVariable / CauchyVariable over the chain; another kind is BSVI_ERR_UNSUPPORTED.  Valid after bsvi_bnn_create_normal,
+ * bsvi_bnn_create_normal_learnable or bsvi_bnn_create_normal_heads and before the first launch or bsvi_bnn_middle (the generated kernels
+ * carry the family as a literal): a null handle, a classifier's handle or a call after a launch is BSVI_ERR_INVALID.  The scale keeps
+ * every form it has for the Normal.  With u = (y_c - z_c) / sigma_c and psi the family's score, per minibatch row, sample and output
+ *     Laplace  f += lik_weight (-|u| - log(2 sigma_c)),              psi = sign(u), sign(0) = 0
+ *     Cauchy   f += lik_weight (-log(1 + u^2) - log(pi sigma_c)),    psi = 2 u / (1 + u^2)
+ *     d f / d z_c = lik_weight psi / sigma_c,    d f / d sigma_c = lik_weight (u psi - 1) / sigma_c        (the Normal: psi = u)
+ * bsvi_bnn_predict: draw_out is loc + sigma_c e with e the family's draw from ONE Philox word, word c & 3 of the call whose k1 is
+ * xor-ed with c >> 2 (Laplace: -sign(v) log1p(-|v|) of the uniform base noise v; Cauchy: the tangent of the angle); var_out adds
+ * 2 sigma_c^2 for Laplace, and with var_out set a Cauchy model is BSVI_ERR_UNSUPPORTED ("the Cauchy likelihood has no variance"), before
+ * anything is launched.  No struct changes, the ABI version stays. */
+int bsvi_bnn_set_likelihood_family(bsvi_bnn* b, uint32_t kind);
 void bsvi_bnn_destroy(bsvi_bnn* b);
 size_t bsvi_bnn_workspace_bytes(const bsvi_bnn* b, uint32_t n_samples_local);
 int bsvi_bnn_exact_data(const bsvi_bnn* b);
