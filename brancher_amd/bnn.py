@@ -47,6 +47,8 @@ PREDICT_PATHS = ("global", "lds")                                      # bsvi_bn
 # the families of the loc-scale regression likelihood (bsvi_bnn_set_likelihood_family): the name a refusal gives the observed variable
 LIKELIHOOD_FAMILIES = {D.DIST_NORMAL: "Normal", D.DIST_LAPLACE: "Laplace", D.DIST_CAUCHY: "Cauchy"}
 PRIOR_KINDS = {D.DIST_NORMAL: "normal", D.DIST_LAPLACE: "laplace", D.DIST_CAUCHY: "cauchy"}      # bsvi_bnn_set_row_priors (BSVI_DIST_*)
+MAX_SCALE_LATENTS = 18                                                 # BNN_MAX_LATENTS: eight layers' weights and biases, two scale-head tensors
+NO_LATENT = 0xFF                                                       # row_latent of a row whose prior scale is a constant or a learnable root
 
 
 class BnnProgram:
@@ -55,6 +57,10 @@ class BnnProgram:
     family = D.DIST_NORMAL     # of a LIK_NORMAL program: D.DIST_NORMAL | DIST_LAPLACE | DIST_CAUCHY (the observed variable's distribution)
     scale_learnable = False
     scale_head = None          # (transform, a, b) of a scale head: sigma = a + b g(second head); the last layer then has 2 C rows
+    # latent prior scales (a hierarchical prior; bsvi_bnn_set_scale_latents): [dict(name, tensors=[(tensor name, multiplier b)])] in the
+    # order of their first tensor; then `row_latent` (a byte per row, NO_LATENT for none) and `latent_uniform` [4][T] (q loc, q scale,
+    # prior loc, prior scale) exist, and the noise has a row per latent behind the weights' (n_noise = n_rows + T)
+    scale_latents = ()
 
     def summary(self):
         s = dict(kind="bnn", layers=[(l["rows"], l["cols"], l["activation"]) for l in self.layers], n_rows=self.n_rows,
@@ -65,6 +71,8 @@ class BnnProgram:
             if self.family != D.DIST_NORMAL:
                 s["family"] = LIKELIHOOD_FAMILIES[self.family].lower()
         s["priors"] = {t["name"]: t.get("prior", "normal") for t in self.tensors}
+        if self.scale_latents:
+            s["scale_latents"] = {l["name"]: [(name, b) for name, b in l["tensors"]] for l in self.scale_latents}
         return s
 
 
@@ -110,6 +118,40 @@ def _depends_on_latent(e):
             return any(_depends_on_latent(x.expr) for x in v.link.expressions().values())
         return isinstance(v, RandomVariable)
     return any(_depends_on_latent(a) for a in e.args if hasattr(a, "op"))
+
+
+def _random_variables(e):
+    """the random variables a link expression reads (through deterministic nodes too), in the order met"""
+    if e.op == "var":
+        v = e.attr
+        if getattr(v, "_type", None) == "Deterministic node":
+            return [r for x in v.link.expressions().values() for r in _random_variables(x.expr)]
+        return [v] if isinstance(v, RandomVariable) else []
+    return [r for a in e.args if hasattr(a, "op") for r in _random_variables(a)]
+
+
+def _latent_scale(v):
+    """the prior scale of the tensor `v` when it reads a latent: b * tau -> (tau, b) — tau itself, b * tau, tau * b or tau / b with a
+    number b > 0 —, or the refusal"""
+    e = v.link.expressions()["scale"].expr
+    taus = _random_variables(e)
+    if len({id(t) for t in taus}) > 1:
+        raise LoweringError("bnn path: the prior scale of %r is computed from two latent variables (%s): a tensor takes one scale latent"
+                            % (v.name, ", ".join(repr(t.name) for t in taus)))
+    number = lambda x: float(np.asarray(x.attr).reshape(-1)[0]) if x.op == "const" and np.size(x.attr) == 1 else None
+    b = None
+    if e.op == "var" and e.attr is taus[0]:
+        b = 1.0
+    elif e.op in ("mul", "truediv") and len(e.args) == 2:
+        l, r = e.args
+        if l.op == "var" and l.attr is taus[0] and number(r) is not None:
+            b = number(r) if e.op == "mul" else (1.0 / number(r) if number(r) else None)
+        elif e.op == "mul" and r.op == "var" and r.attr is taus[0] and number(l) is not None:
+            b = number(l)
+    if b is None or not (b > 0 and np.isfinite(b)):
+        raise LoweringError("bnn path: the prior scale of %r must be its scale latent %r times a number b > 0 (tau, b * tau, tau * b or tau / b)"
+                            % (v.name, taus[0].name))
+    return taus[0], float(b)
 
 
 LEARNABLE_SCALE_TRANSFORMS = ("softplus", "exp", "sigmoid")          # what keeps sigma off zero whatever a step does to its root
@@ -205,9 +247,19 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
             # (a scale computed from a matmul is a scale head, or refused below with its own cause)
             raise LoweringError("bnn path: the scale of the %s likelihood %r is a latent variable or computed from one "
                                 "(it must be a constant of the model)" % (LIKELIHOOD_FAMILIES[v.distribution.kind], v.name))
-    if not q_random or any(v.distribution.kind != D.DIST_NORMAL for v in q_random):
-        raise LoweringError("bnn path: the posterior must be mean-field Normal variables")
     p_random = [v for v in joint._flatten() if _is_random(v)]
+    # latent prior scales: the latents that the prior scale of an unobserved Normal / Laplace / Cauchy variable reads.  Their posterior is a
+    # LogNormal of the same name, not one of the weights' Normals: by name they stand outside the checks of the weights' posterior
+    scale_vars = []
+    for v in p_random:
+        if v.distribution.kind in PRIOR_KINDS and not v.is_observed:
+            for t in _random_variables(v.link.expressions()["scale"].expr):
+                if all(t is not o for o in scale_vars):
+                    scale_vars.append(t)
+    scale_names = {t.name for t in scale_vars}
+    q_weights = [v for v in q_random if v.name not in scale_names]
+    if not q_weights or any(v.distribution.kind != D.DIST_NORMAL for v in q_weights):
+        raise LoweringError("bnn path: the posterior must be mean-field Normal variables")
     # the likelihood: a Categorical / Binomial(1) over logits, or — regression — an OBSERVED Normal, Laplace or Cauchy whose loc is the chain
     liks = [v for v in p_random if v.distribution.kind in (D.DIST_CATEGORICAL, D.DIST_BINOMIAL, D.DIST_BERNOULLI)
             or (v.distribution.kind in LIKELIHOOD_FAMILIES and v.is_observed)]
@@ -259,8 +311,36 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     names = [v.name for v in latents]
     if len(set(names)) != len(names):
         raise LoweringError("bnn path: a latent tensor is used by two layers")
-    others = [v for v in p_random if v is not k and v not in latents and v.distribution.kind != D.DIST_EMPIRICAL]
-    if others or sorted(names) != sorted(v.name for v in q_random):
+    # latent prior scales of the network's tensors: tensor -> (latent, multiplier); every refusal names the variable and the cause
+    scale_of, taus = {}, []
+    for v in latents:
+        if _is_random(v) and v.distribution.kind in PRIOR_KINDS and _random_variables(v.link.expressions()["scale"].expr):
+            tau, b = _latent_scale(v)
+            scale_of[v.name] = (tau, b)
+            if all(tau is not o for o in taus):
+                taus.append(tau)
+    for tau in taus:
+        q_tau = L.q_by_name.get(tau.name)
+        if tau.distribution.kind != D.DIST_LOGNORMAL:
+            raise LoweringError("bnn path: the scale latent %r must be a LogNormal variable: it is %s"
+                                % (tau.name, type(tau.distribution).__name__.replace("Distribution", "")))
+        if q_tau is None or not _is_random(q_tau) or q_tau.distribution.kind != D.DIST_LOGNORMAL:
+            raise LoweringError("bnn path: the posterior of the scale latent %r must be a LogNormal variable of the same name: it is %s"
+                                % (tau.name, "missing" if q_tau is None else type(getattr(q_tau, "distribution", None)).__name__.replace("Distribution", "")))
+        if any(t.name == tau.name for t in latents):
+            raise LoweringError("bnn path: the scale latent %r is also a tensor of the network" % tau.name)
+        for var, where in ((tau, "prior"), (q_tau, "posterior")):
+            if any(_random_variables(x.expr) for x in var.link.expressions().values()):
+                raise LoweringError("bnn path: the %s of the scale latent %r depends on another latent variable (its loc and scale must be "
+                                    "constants or parameter transforms)" % (where, tau.name))
+    if taus and estimator == "taylor1":
+        raise LoweringError("bnn path: the Taylor1 estimator does not serve a model with scale latents (%s): the mean of a LogNormal is "
+                            "exp(m + s^2 / 2), not the value at the zero draw the estimator is evaluated on" % ", ".join(repr(t.name) for t in taus))
+    if len(taus) > MAX_SCALE_LATENTS:
+        raise LoweringError("bnn path: the model has %d scale latents, the kernels serve at most %d" % (len(taus), MAX_SCALE_LATENTS))
+    others = [v for v in p_random if v is not k and v not in latents and v.distribution.kind != D.DIST_EMPIRICAL
+              and all(v is not t for t in taus)]
+    if others or sorted(names + [t.name for t in taus]) != sorted(v.name for v in q_random):
         raise LoweringError("bnn path: every latent of the network needs a Normal posterior of the same name, and nothing else may be latent")
     for v in latents:
         # (loc / scale families on the whole real line: a Normal posterior covers their support — LogNormal, Beta and the rest do not)
@@ -297,9 +377,12 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     if P % 4:
         raise LoweringError("bnn path: the number of features must be a multiple of 4")
 
-    def row_params(var, ctx):
+    def row_params(var, ctx, scale=None):
+        # (scale: the multiplier b of a tensor under a scale latent — a constant in the place of its prior scale)
+        nodes = L.node_params(var, ctx) if scale is None else [
+            L.from_expr(var.link.expressions()["loc"].expr, ctx), L.mk("carr", (), np.full((1,), scale, dtype=np.float32), (1, 1, 1))]
         out = []
-        for node in L.node_params(var, ctx):
+        for node in nodes:
             m = L.match_uniform(node)
             if m is None:
                 raise LoweringError("bnn path: the parameters of %r must be constants or parameter transforms" % var.name)
@@ -321,7 +404,7 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     for v in order:
         q = L.q_by_name[v.name]
         ql, qs = row_params(q, L.q_value)
-        pl, ps = row_params(v, L.p_value)
+        pl, ps = row_params(v, L.p_value, scale_of[v.name][1] if v.name in scale_of else None)
         shape = tuple(int(s) for s in ql[3])
         if len(shape) != 3 or shape[0] != 1:
             raise LoweringError("bnn path: %r must be a matrix [rows, cols] or a column [rows, 1]" % v.name)
@@ -375,6 +458,15 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
             if tc is None or tc[0].op != "root" or float(np.asarray(tc[0].attr.value).reshape(-1)[0]) != 1.0:
                 raise LoweringError("bnn path: Binomial likelihood supports total_count = 1 only")
 
+    # the scale latents' own parameters: one value each, constants or parameter transforms
+    latent_entries = []
+    for tau in taus:
+        ents = row_params(L.q_by_name[tau.name], L.q_value) + row_params(tau, L.p_value)
+        for ent in ents:
+            if ent[2] != 1:
+                raise LoweringError("bnn path: the scale latent %r has %d values (a scale latent is one value: one scale for a whole tensor)"
+                                    % (tau.name, max(e[2] for e in ents)))
+        latent_entries.append(ents)
     uni, n_up = L.uniform_table()
     prog = BnnProgram()
     prog.estimator = estimator
@@ -407,6 +499,15 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     prog.x_name, prog.likelihood_name = x_var.name, k.name       # (engine.posterior_sample: the variables a prediction is keyed by)
     prog.lik_weight, prog.prior_weight, prog.entropy_weight = 1.0, 1.0, 1.0
     prog.n_noise = R
+    if taus:
+        index = {t.name: i for i, t in enumerate(taus)}
+        prog.scale_latents = [dict(name=t.name, tensors=[(x["name"], scale_of[x["name"]][1]) for x in tensors
+                                                         if x["name"] in scale_of and scale_of[x["name"]][0] is t]) for t in taus]
+        prog.row_latent = np.concatenate([np.full(x["size"], index[scale_of[x["name"]][0].name] if x["name"] in scale_of else NO_LATENT,
+                                                  dtype=np.uint8) for x in tensors])
+        prog.latent_uniform = np.array([[k0 if is_param else n_up + k0 for is_param, k0, _, _ in ents] for ents in latent_entries],
+                                       dtype=np.uint32).T.copy()
+        prog.n_noise = R + len(taus)
     prog.bmax = 1
     return prog
 
@@ -496,6 +597,11 @@ class CompiledBnn:
         row_prior = np.ascontiguousarray(getattr(p, "row_prior", np.zeros(0)), dtype=np.uint8)
         if (row_prior != D.DIST_NORMAL).any():             # (without the call every row is Normal)
             native.check(lib.bsvi_bnn_set_row_priors(handle, row_prior.ctypes.data_as(C.c_void_p), row_prior.size))
+        if getattr(p, "scale_latents", None):              # (without the call no prior scale is latent)
+            row_latent = np.ascontiguousarray(p.row_latent, dtype=np.uint8)
+            self._keep["latent_uniform"] = lu = np.ascontiguousarray(p.latent_uniform, dtype=np.uint32)
+            native.check(lib.bsvi_bnn_set_scale_latents(handle, len(p.scale_latents), row_latent.ctypes.data_as(C.c_void_p), row_latent.size,
+                                                        lu.ctypes.data_as(C.c_void_p)))
         self._exact_data = bool(lib.bsvi_bnn_exact_data(handle))
         dev = self.device
         self.n_params = p.n_params
@@ -570,23 +676,34 @@ class CompiledBnn:
         return z
 
     def noise_from_named(self, named, n):
-        """{variable name: [N, 1, rows, cols]}  ->  [n_rows, N] (the latent vector's row order)"""
-        out = np.zeros((self.program.n_rows, n), dtype=np.float32)
+        """{variable name: [N, 1, rows, cols]}  ->  [n_noise, N] (the latent vector's row order; a scale latent, [N, 1, 1, 1], is row
+        n_rows + t behind the weights')"""
+        out = np.zeros((self.program.n_noise, n), dtype=np.float32)
         for t in self.program.tensors:
             a = np.asarray(named[t["name"]], dtype=np.float32)
             out[t["row0"]:t["row0"] + t["size"]] = a.reshape(a.shape[0], -1).T
+        for i, l in enumerate(self.program.scale_latents):
+            out[self.program.n_rows + i] = np.asarray(named[l["name"]], dtype=np.float32).reshape(-1)
         return out
 
     def named_noise(self, noise, n):
         """[n_rows, N] -> {variable name: [N, 1, rows, cols]} (what the oracle takes)"""
         noise = np.asarray(noise)
-        return {t["name"]: noise[t["row0"]:t["row0"] + t["size"]].T.reshape(n, 1, t["rows"], t["cols"]) for t in self.program.tensors}
+        named = {t["name"]: noise[t["row0"]:t["row0"] + t["size"]].T.reshape(n, 1, t["rows"], t["cols"]) for t in self.program.tensors}
+        if noise.shape[0] > self.program.n_rows:          # (the draw of a training launch; `predict` reports the weights' rows alone)
+            for i, l in enumerate(self.program.scale_latents):
+                named[l["name"]] = noise[self.program.n_rows + i].reshape(n, 1, 1, 1)
+        return named
 
-    def _noise_tensor(self, noise, n_global, base, n_local):
+    def _noise_tensor(self, noise, n_global, base, n_local, rows=None):
         if noise is None:
             return None
         if isinstance(noise, dict):
             noise = self.noise_from_named(noise, n_global)
+        # (a training launch reads row n_rows + t for scale latent t: a matrix of the weights' rows alone is refused here, not read past)
+        rows = self.program.n_noise if rows is None else rows
+        if self.program.scale_latents and noise.shape[0] != rows:
+            raise ValueError("noise must have {} rows: got {}".format(rows, noise.shape[0]))
         if isinstance(noise, np.ndarray):
             return torch.from_numpy(np.ascontiguousarray(noise[:, base:base + n_local], dtype=np.float32)).to(self.device)
         return noise if noise.shape[1] == n_local else noise[:, base:base + n_local].contiguous()
@@ -689,9 +806,11 @@ class CompiledBnn:
             offset = (1 << 62) + _engine._sample_tick[0]
         if getattr(p, "estimator", "pathwise") == "taylor1":
             noise = self._zero_noise(N)                       # (f at the posterior's means: `_args`)
-        noise_t = self._noise_tensor(noise, N, 0, N)
-        if noise_t is not None and tuple(noise_t.shape) != (p.n_noise, N):
-            raise ValueError("noise must be [{}, {}]: got {}".format(p.n_noise, N, tuple(noise_t.shape)))
+        if isinstance(noise, dict):                           # (named as the oracle takes it: the weights' rows; a scale latent's draw is not read)
+            noise = self.noise_from_named(dict({l["name"]: np.zeros(N) for l in p.scale_latents}, **noise), N)[:p.n_rows]
+        noise_t = self._noise_tensor(noise, N, 0, N, rows=p.n_rows)
+        if noise_t is not None and tuple(noise_t.shape) != (p.n_rows, N):
+            raise ValueError("noise must be [{}, {}]: got {}".format(p.n_rows, N, tuple(noise_t.shape)))
         if not isinstance(seed, int) or seed is True:
             seed = _engine.shared_seed(seed, dev)
         key = (N, M, rpp)
@@ -706,7 +825,7 @@ class CompiledBnn:
         heads = bool(getattr(p, "scale_head", None))        # (z_out is then [N, M, 2 C]: the loc, then sigma itself)
         outputs = new(N, M, 2 * Cn if heads else Cn) if want_outputs else None
         draws = new(N, M, Cn) if want_draws else None
-        noise_o = new(p.n_noise, N) if want_noise else None
+        noise_o = new(p.n_rows, N) if want_noise else None      # (the posterior of the weights does not involve a scale latent)
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         args = native.BnnPredictArgs(params_dev=ptr(self.params), x_dev=ptr(rows), noise_dev=ptr(noise_t), seed=int(seed),
                                      offset=int(offset), n_samples_local=N, sample_base=int(sample_base), n_rows=M, rows_per_pass=rpp,

@@ -97,6 +97,16 @@ struct BParams {
     // the family of the loc-scale likelihood (bsvi_bnn_set_likelihood_family): BSVI_DIST_NORMAL | _LAPLACE | _CAUCHY, launch-uniform.
     // Behind every other member, so that no field the kernels of the models without it read has moved
     uint32_t family;
+    // latent prior scales (bsvi_bnn_set_scale_latents; n_latents = 0: none, and nothing below is read): tau_t = exp(m_t + s_t eps) scales the
+    // prior of the rows whose byte of row_latent is t (0xFF: none; padded with 0xFF to a whole quad), lat_uniform [4][T] the entries of
+    // q loc, q scale, prior loc, prior scale, lat_count [T] the number of rows under each.  Per launch and (t, n), [T][n_pad]:
+    // l, 1 / tau and eps (the latent blocks of bnn_head_gather), D = d f_n / d l and z = (l - m0) / s0 (bnn_latent_terms); lat_upart
+    // [row_chunks][T][n_pad] the chunks' sums of u psi - 1 over the rows under t (bnn_draw), lat_f / lat_q [n_pad] the latents' per-sample
+    // parts of f and log q, lat_b [n_pad] the score weights b_n (bnn_epilogue).  Behind every other member, as `family` is
+    uint32_t n_latents;
+    const uint8_t* row_latent; const uint32_t* lat_uniform; const uint32_t* lat_count;
+    float* lat_l; float* lat_itau; float* lat_eps; float* lat_D; float* lat_z; float* lat_upart;
+    double* lat_f; double* lat_q; double* lat_b;
 };
 
 __device__ __forceinline__ float bnn_act(uint32_t act, float v) {
@@ -234,11 +244,40 @@ __device__ __forceinline__ void bnn_gather_body(const BParams& Q, const uint32_t
     }
 }
 
-// ONE launch for the two: the first B_pad x gy blocks gather, the rest are the head's
+// the normal of latent t and sample n: normal t & 3 of the row-quad call whose quad index is ceil(R / 4) + (t >> 2) — behind every quad of
+// rows, the same counters, key and pairing as bnn_eps4 —, or row R + t of the caller's noise
+__device__ __forceinline__ float bnn_latent_eps(const BParams& Q, const uint32_t n, const uint32_t t) {
+    if (Q.noise_in) return Q.noise_in[(size_t)(Q.R + t) * Q.n_local + n];
+    const uint32_t g = (Q.R + 3u) / 4u + (t >> 2);
+    const u32x4 x = philox4x32(Q.sample_base + n, g | 0x40000000u, Q.offset_lo, Q.offset_hi, Q.seed_lo, Q.seed_hi);
+    float e[4];
+    box_muller_fast(x.x, x.y, e[0], e[1]);
+    box_muller_fast(x.z, x.w, e[2], e[3]);
+    const uint32_t j = t & 3u;
+    return j == 0u ? e[0] : (j == 1u ? e[1] : (j == 2u ? e[2] : e[3]));
+}
+
+// latent prior scales: l = m_t + s_t eps, 1 / tau and eps of every (latent, sample), once per launch and from the uniform table (the
+// head's blocks fill rowp in the same launch).  threads: T x n_pad
+__device__ __forceinline__ void bnn_latent_body(const BParams& Q, const uint32_t i) {
+    if (i >= Q.n_latents * Q.n_pad) return;
+    const uint32_t t = i / Q.n_pad, n = i - t * Q.n_pad;
+    float l = 0.0f, e = 0.0f;
+    if (n < Q.n_local) {
+        e = bnn_latent_eps(Q, n, t);
+        l = bnn_uniform_value(Q, Q.lat_uniform[t]) + bnn_uniform_value(Q, Q.lat_uniform[Q.n_latents + t]) * e;
+        if (Q.noise_out) Q.noise_out[(size_t)(Q.R + t) * Q.n_local + n] = e;
+    }
+    Q.lat_l[i] = l; Q.lat_eps[i] = e; Q.lat_itau[i] = expf(-l);
+}
+
+// ONE launch for the two: the first B_pad x gy blocks gather, the rest are the head's (and behind those, the blocks of a model with
+// latent prior scales: bnn_latent_body)
 __global__ void __launch_bounds__(256) bnn_head_gather(const BParams Q, const uint32_t gy, const uint32_t head_blocks) {
     const uint32_t gather_blocks = Q.B_pad * gy;
     if (blockIdx.x < gather_blocks) bnn_gather_body(Q, blockIdx.x / gy, (blockIdx.x % gy) * 256u + threadIdx.x);
-    else bnn_head_body(Q, (blockIdx.x - gather_blocks) * 256u + threadIdx.x, head_blocks * 256u);
+    else if (blockIdx.x < gather_blocks + head_blocks) bnn_head_body(Q, (blockIdx.x - gather_blocks) * 256u + threadIdx.x, head_blocks * 256u);
+    else bnn_latent_body(Q, (blockIdx.x - gather_blocks - head_blocks) * 256u + threadIdx.x);
 }
 
 // W = mu + s eps.  One wave = (chunk of 64 row quads, sample), lanes along the rows: the pieces of weights1 leave as consecutive
@@ -247,16 +286,23 @@ __global__ void __launch_bounds__(256) bnn_head_gather(const BParams Q, const ui
 // parameters of a quad by 16- / 8-byte loads where their arrays' offsets allow)
 // MIXED: some row's prior is Laplace or Cauchy.  The lanes run along the rows, and a quad of the small tensors can straddle two
 // tensors, so the kind is per row and the value is picked by select; MIXED = false is the kernel of the all-Normal models as it was.
-template <bool MIXED>
+// LATENT (with MIXED; bsvi_bnn_set_scale_latents): the prior scale of a row under latent t is b_r tau_(t, n), so u takes 1 / tau of the
+// sample, and the wave holds u of every such row: it leaves sum_(r under t) (u psi - 1) of its chunk per latent present in the chunk (a wave
+// sum per latent, lat_upart; zero for the others), which bnn_latent_terms adds in chunk order.  (u psi - 1, not u psi: the terms are
+// centred, so the sum over 15 680 rows does not carry their count in its leading bits.)
+template <bool MIXED, bool LATENT = false>
 __global__ void __launch_bounds__(256) bnn_draw(const BParams Q) {
     const uint32_t chunk = blockIdx.x, lane = threadIdx.x & 63u, n = blockIdx.y * 4u + (threadIdx.x >> 6), g = chunk * 64u + lane;
     if (n >= Q.n_pad) return;
     const bool live = n < Q.n_local;
     const uint32_t quads = (Q.R + 3u) / 4u;
     float pv = 0.0f, qv = 0.0f;
+    float up[4] = {0.0f, 0.0f, 0.0f, 0.0f};      // LATENT: u psi - 1 of the quad's rows, and their latents (a byte per row)
+    uint32_t lats = 0xFFFFFFFFu;
     if (g < quads) {
         float e[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         if (live) bnn_eps4(Q, n, g, e);
+        if (LATENT) lats = *reinterpret_cast<const uint32_t*>(Q.row_latent + 4u * (size_t)g);
         uint16_t hi[4] = {0, 0, 0, 0}, mid[4] = {0, 0, 0, 0}, lo[4] = {0, 0, 0, 0};
         float w4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         // {q loc, q scale, prior loc, prior scale} of the quad's rows
@@ -287,7 +333,15 @@ __global__ void __launch_bounds__(256) bnn_draw(const BParams Q) {
             const float w = mu + s * e[j];
             w4[j] = live ? w : 0.0f;
             if (live) {
-                const float u = (w - mu0) / s0;
+                float u = (w - mu0) / s0;
+                if (LATENT) {
+                    const uint32_t lt = (lats >> (8 * j)) & 0xFFu, kind = (kinds >> (8 * j)) & 0xFFu;
+                    if (lt != 0xFFu) {
+                        u *= Q.lat_itau[(size_t)lt * Q.n_pad + n];
+                        const float au = fabsf(u), uu = u * u;
+                        up[j] = (kind == BSVI_DIST_LAPLACE ? au : (kind == BSVI_DIST_CAUCHY ? 2.0f * uu / (1.0f + uu) : uu)) - 1.0f;
+                    }
+                }
                 if (MIXED) pv += bnn_prior_value((kinds >> (8 * j)) & 0xFFu, u);
                 else pv += -0.5f * u * u;
                 qv += -0.5f * e[j] * e[j];
@@ -319,6 +373,20 @@ __global__ void __launch_bounds__(256) bnn_draw(const BParams Q) {
     }
     pv = wave_sum(pv); qv = wave_sum(qv);
     if (lane == 0) { Q.pv_part[(size_t)chunk * Q.n_pad + n] = pv; Q.qv_part[(size_t)chunk * Q.n_pad + n] = qv; }
+    if (LATENT) {
+        for (uint32_t t = 0; t < Q.n_latents; ++t) {
+            float v = 0.0f;
+            bool has = false;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool mine = ((lats >> (8 * j)) & 0xFFu) == t;
+                v += mine ? up[j] : 0.0f;
+                has = has || mine;
+            }
+            if (__ballot(has) != 0ull) v = wave_sum(v);      // (wave-uniform: a chunk without a row under t writes the zero)
+            if (lane == 0) Q.lat_upart[((size_t)chunk * Q.n_latents + t) * Q.n_pad + n] = v;
+        }
+    }
 }
 
 // (the pad columns P .. Kp of the pieces are written by bnn_draw too — the lane that holds a row's last quad: no memset per call)
@@ -596,12 +664,34 @@ __device__ __forceinline__ void bnn_row_terms_mixed(const BParams& Q, const uint
     qconst = -log(sd) - 0.91893853320467274178;
 }
 
+// ... of a row under a latent prior scale (bnn_row_sums<true, true>): its prior scale is b_r tau_(t, n), so T0 and T1 carry 1 / (b_r tau)
+// inside the sum for all three kinds, and the row's prior scale entry holds b_r: log p = g(u) - log b_r - l with u = (w - mu0) / (b_r tau), so
+// d log p / d b_r = -(w - mu0) t / b_r - 1 / b_r, summed -((mu - mu0) T0 + s T1 + N) / b_r — T2's identity with b_r in the place of s0 —, and -log b_r stands in
+// the constant where -log s0 does; the per-sample -l is the latent's (bnn_latent_terms)
+__device__ __forceinline__ void bnn_row_terms_latent(const BParams& Q, const uint32_t r, const uint32_t kind, const float ds_lik, const float dmu_lik,
+                                                     const float T0, const float T1, const float N, double& hconst, double& qconst) {
+    const float mu = Q.rowp[r], s = Q.rowp[Q.R + r], mu0 = Q.rowp[2 * (size_t)Q.R + r], b = Q.rowp[3 * (size_t)Q.R + r];
+    const float T2 = -((mu - mu0) * T0 + s * T1 + N) / b;
+    Q.rowg[r] = dmu_lik + Q.prior_weight * T0;
+    Q.rowg[Q.R + r] = ds_lik + Q.prior_weight * T1 + Q.entropy_weight * N / s;
+    Q.rowg[2 * (size_t)Q.R + r] = -Q.prior_weight * T0;
+    Q.rowg[3 * (size_t)Q.R + r] = Q.prior_weight * T2;
+    const double sd = bnn_uniform_value_d(Q, Q.row_uniform[Q.R + r]), bd = bnn_uniform_value_d(Q, Q.row_uniform[3 * (size_t)Q.R + r]);
+    const double pconst = kind == BSVI_DIST_LAPLACE ? -log(2.0 * bd) : (kind == BSVI_DIST_CAUCHY ? -1.14472988584940017414 - log(bd) : -log(bd) - 0.91893853320467274178);
+    hconst = (double)Q.prior_weight * pconst + (double)Q.entropy_weight * (1.41893853320467274178 + log(sd));
+    qconst = -log(sd) - 0.91893853320467274178;
+}
+
 // per row quad (one wave, lanes = samples): sum_n eps G, sum_n G, sum_n eps, sum_n eps^2, then the rows' gradients and constants.  grid: ceil(quads / 4), block 256: a wave per quad
 // (round 6: four quads per workgroup, as bnn_draw)
 // MIXED: eight more accumulators, T0 and T1 of bnn_row_terms_mixed for each of the four rows, from w and u recomputed as bnn_draw
 // computed them on the eps redrawn here anyway — no pass over memory of their own, the same wave_sum order; a Normal row of such a model
 // keeps its closed form.  MIXED = false is the kernel of the all-Normal models as it was.
-template <bool MIXED>
+// LATENT (with MIXED; bsvi_bnn_set_scale_latents): a row under a latent has the prior scale b_r tau_(t, n), another one per sample, so all
+// three kinds take T0 and T1 with 1 / (b_r tau) inside the sum (the Normal: t = -u / s0) — the same eight accumulators, one load of
+// 1 / tau per sample where the quad's rows share a latent (every quad inside a tensor), else one per row; rows under no latent keep
+// what MIXED gives them.
+template <bool MIXED, bool LATENT = false>
 __global__ void __launch_bounds__(256) bnn_row_sums(const BParams Q) {
     const uint32_t quads = (Q.R + 3u) / 4u, g = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u, r0 = 4u * g;
     if (g >= quads) return;
@@ -610,7 +700,9 @@ __global__ void __launch_bounds__(256) bnn_row_sums(const BParams Q) {
     for (int k = 0; k < 16; ++k) acc[k] = 0.0f;
     float asum = 0.0f;
     float tacc[8], rp[4][4], is0[4];
-    uint32_t kinds = 0u;
+    uint32_t kinds = 0u, lats = 0xFFFFFFFFu;
+    if (LATENT) lats = *reinterpret_cast<const uint32_t*>(Q.row_latent + (size_t)r0);
+    const bool lat_shared = LATENT && lats == (lats & 0xFFu) * 0x01010101u, lat_any = LATENT && lats != 0xFFFFFFFFu;
     if (MIXED) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) tacc[k] = 0.0f;
@@ -627,6 +719,18 @@ __global__ void __launch_bounds__(256) bnn_row_sums(const BParams Q) {
         bnn_eps4(Q, n, g, e);
         const float aw = Q.f_weight ? Q.f_weight[n] : 1.0f;      // (G carries a_n already: the seeds were scaled)
         asum += aw;
+        float it[4] = {1.0f, 1.0f, 1.0f, 1.0f};      // LATENT: 1 / tau of the sample for the quad's rows (1 for a row under no latent)
+        if (LATENT && lat_any) {
+            if (lat_shared) {
+                it[0] = it[1] = it[2] = it[3] = Q.lat_itau[(size_t)(lats & 0xFFu) * Q.n_pad + n];
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t lt = (lats >> (8 * j)) & 0xFFu;
+                    if (lt != 0xFFu) it[j] = Q.lat_itau[(size_t)lt * Q.n_pad + n];
+                }
+            }
+        }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const uint32_t r = r0 + j;
@@ -641,10 +745,13 @@ __global__ void __launch_bounds__(256) bnn_row_sums(const BParams Q) {
             acc[j] += e[j] * G; acc[4 + j] += G; acc[8 + j] += aw * e[j]; acc[12 + j] += aw * (e[j] * e[j]);
             if (MIXED) {
                 const uint32_t kind = (kinds >> (8 * j)) & 0xFFu;
-                const float w = rp[0][j] + rp[1][j] * e[j], dw = w - rp[2][j], u = dw * is0[j];
+                const float isn = LATENT ? is0[j] * it[j] : is0[j];
+                const float w = rp[0][j] + rp[1][j] * e[j], dw = w - rp[2][j], u = dw * isn;
                 // Laplace: t = -sign(u) / s0 (sign(0) = 0, as torch's abs backward);  Cauchy: t = -2 u / ((1 + u^2) s0)
+                // (LATENT: s0 the sample's b_r tau, and a Normal row under a latent t = -u / s0: its closed form does not hold)
                 const float sg = dw > 0.0f ? 1.0f : (dw < 0.0f ? -1.0f : 0.0f);
-                const float t = (kind == BSVI_DIST_LAPLACE ? -sg : (kind == BSVI_DIST_CAUCHY ? -2.0f * u / (1.0f + u * u) : 0.0f)) * is0[j];
+                const float tn = (LATENT && ((lats >> (8 * j)) & 0xFFu) != 0xFFu) ? -u : 0.0f;
+                const float t = (kind == BSVI_DIST_LAPLACE ? -sg : (kind == BSVI_DIST_CAUCHY ? -2.0f * u / (1.0f + u * u) : tn)) * isn;
                 tacc[j] += aw * t; tacc[4 + j] += aw * (e[j] * t);
             }
         }
@@ -683,13 +790,41 @@ __global__ void __launch_bounds__(256) bnn_row_sums(const BParams Q) {
             for (int j = 0; j < 4; ++j) { T0 = (lane == (uint32_t)j) ? tacc[j] : T0; T1 = (lane == (uint32_t)j) ? tacc[4 + j] : T1; }
             kind = (kinds >> (8u * lane)) & 0xFFu;
         }
-        if (MIXED && kind != BSVI_DIST_NORMAL) bnn_row_terms_mixed(Q, r, kind, ds_lik, dmu_lik, T0, T1, Nw, hconst, qconst);
+        if (LATENT && ((lats >> (8u * lane)) & 0xFFu) != 0xFFu) bnn_row_terms_latent(Q, r, kind, ds_lik, dmu_lik, T0, T1, Nw, hconst, qconst);
+        else if (MIXED && kind != BSVI_DIST_NORMAL) bnn_row_terms_mixed(Q, r, kind, ds_lik, dmu_lik, T0, T1, Nw, hconst, qconst);
         else bnn_row_terms(Q, r, ds_lik, dmu_lik, S1, S2, Nw, hconst, qconst);
     }
     double h4 = 0.0, q4 = 0.0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) { h4 += __shfl(hconst, j, 64); q4 += __shfl(qconst, j, 64); }
     if (lane == 0u) { Q.hpart[g] = h4; Q.hpart[quads + g] = q4; }
+}
+
+// latent prior scales, one thread per sample: the chunks' sums of u psi - 1 in chunk order, then per latent, with z = (l - m0) / s0,
+//     D = d f_n / d l = prior_weight (sum_(r under t) (u psi - 1) - 1 - z / s0)
+// and the latents' per-sample parts of f and log q (their constants are bnn_epilogue's, in double precision):
+//     f_n += prior_weight sum_t (-(K_t + 1) l - 1/2 z^2),      log q_n += sum_t (-l - 1/2 eps^2)
+// (K_t l in double precision: K_t is the number of rows of a tensor).  grid: ceil(n_pad / 256), block 256
+__global__ void __launch_bounds__(256) bnn_latent_terms(const BParams Q) {
+    const uint32_t n = blockIdx.x * 256u + threadIdx.x, T = Q.n_latents;
+    if (n >= Q.n_pad) return;
+    const bool live = n < Q.n_local;
+    double fl = 0.0, ql = 0.0;
+    for (uint32_t t = 0; t < T; ++t) {
+        float U = 0.0f;
+        const float* __restrict__ const up = Q.lat_upart + (size_t)t * Q.n_pad + n;
+#pragma unroll 8
+        for (uint32_t ch = 0; ch < Q.row_chunks; ++ch) U += up[(size_t)ch * T * Q.n_pad];
+        const size_t at = (size_t)t * Q.n_pad + n;
+        const float l = Q.lat_l[at], e = Q.lat_eps[at];
+        const float m0 = bnn_uniform_value(Q, Q.lat_uniform[2u * T + t]), s0 = bnn_uniform_value(Q, Q.lat_uniform[3u * T + t]);
+        const float z = (l - m0) / s0;
+        Q.lat_D[at] = live ? Q.prior_weight * (U - 1.0f - z / s0) : 0.0f;
+        Q.lat_z[at] = live ? z : 0.0f;
+        fl += (double)Q.prior_weight * (-((double)Q.lat_count[t] + 1.0) * (double)l - 0.5 * (double)z * (double)z);
+        ql += -(double)l - 0.5 * (double)e * (double)e;
+    }
+    Q.lat_f[n] = live ? fl : 0.0; Q.lat_q[n] = live ? ql : 0.0;
 }
 
 // one workgroup: per-sample f (and log q), the value of the estimator, its sum; all in a fixed order
@@ -711,8 +846,17 @@ __global__ void __launch_bounds__(1024) bnn_epilogue(const BParams Q, uint32_t r
     };
     double hc = 0.0, qc = 0.0;
     for (uint32_t i = tid; i < row_blocks; i += 1024u) { hc += Q.hpart[i]; qc += Q.hpart[row_blocks + i]; }
-    const double htot = total(hc), qtot = total(qc);
+    double htot = total(hc), qtot = total(qc);
     const bool blackbox = Q.estimator == BSVI_EST_BLACKBOX;
+    // latent prior scales: the sample-independent terms of their log p, entropy (a LogNormal's, analytic) and log q, in latent order and in
+    // double precision as the rows' (every thread the same sums)
+    for (uint32_t t = 0; t < Q.n_latents; ++t) {
+        const uint32_t T = Q.n_latents;
+        const double md = bnn_uniform_value_d(Q, Q.lat_uniform[t]), sd = bnn_uniform_value_d(Q, Q.lat_uniform[T + t]);
+        const double s0d = bnn_uniform_value_d(Q, Q.lat_uniform[3u * T + t]);
+        htot += (double)Q.prior_weight * (-log(s0d) - 0.91893853320467274178) + (double)Q.entropy_weight * (md + 1.41893853320467274178 + log(sd));
+        qtot += -log(sd) - 0.91893853320467274178;
+    }
     double fsum = 0.0, vsum = 0.0, bad = 0.0;
     for (uint32_t n = tid; n < Q.n_local; n += 1024u) {
         if (Q.q_weight) fsum += (double)Q.q_weight[n];            // (caller weights of grad log q_n in place of f_n: bnn_uniform_grads reads their sum)
@@ -723,7 +867,8 @@ __global__ void __launch_bounds__(1024) bnn_epilogue(const BParams Q, uint32_t r
         const float* __restrict__ const qvp = Q.qv_part + n;
 #pragma unroll 8
         for (uint32_t ch = 0; ch < Q.row_chunks; ++ch) { pv += (double)pvp[(size_t)ch * Q.n_pad]; qv += (double)qvp[(size_t)ch * Q.n_pad]; }
-        const double f = htot + (double)Q.lik[n] + (double)Q.prior_weight * pv;
+        double f = htot + (double)Q.lik[n] + (double)Q.prior_weight * pv;
+        if (Q.n_latents) { f += Q.lat_f[n]; qv += Q.lat_q[n]; Q.lat_b[n] = Q.q_weight ? (double)Q.q_weight[n] : f; }
         if (Q.fvalue_out) Q.fvalue_out[n] = (float)f;
         double value = f;
         if (blackbox) {
@@ -743,6 +888,43 @@ __global__ void __launch_bounds__(1024) bnn_epilogue(const BParams Q, uint32_t r
             const double gt = total(g);
             if (tid == 0) Q.gsd[c] = gt;
         }
+    }
+}
+
+// latent prior scales: the four gradients of every latent, sums over n in a fixed order and double precision, into the items behind the
+// rows' in rowg (bnn_uniform_grads adds them to their entries as it adds a row's):
+//     m_t   sum a D + ew sum a  [- sum b]                            s_t   sum a D eps + ew sum a / s_t  [- sum b (eps + 1 / s_t)]
+//     m0_t  pw sum a z / s0                                          s0_t  pw (sum a z^2 - sum a) / s0
+// (a_n the caller's weights or 1; in brackets the BlackBox score term, b_n = f_n or the caller's as bnn_epilogue left them in lat_b, and
+//  sum b in fs: d log q_n / d m_t = -1, d log q_n / d s_t = -eps - 1 / s_t).  grid: T, block 256: a workgroup per latent
+__global__ void __launch_bounds__(256) bnn_latent_grads(const BParams Q) {
+    __shared__ double dred[4];
+    const uint32_t tid = threadIdx.x, t = blockIdx.x, T = Q.n_latents;
+    auto total = [&](double v) {      // (bnn_epilogue's: a butterfly inside each wave, then the waves in order)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        __syncthreads();
+        if ((tid & 63u) == 0u) dred[tid >> 6] = v;
+        __syncthreads();
+        return (dred[0] + dred[1]) + (dred[2] + dred[3]);
+    };
+    const bool blackbox = Q.estimator == BSVI_EST_BLACKBOX;
+    double as = 0.0, d0 = 0.0, d1 = 0.0, z1 = 0.0, z2 = 0.0, be = 0.0;
+    for (uint32_t n = tid; n < Q.n_local; n += 256u) {
+        const size_t at = (size_t)t * Q.n_pad + n;
+        const double a = Q.f_weight ? (double)Q.f_weight[n] : 1.0, D = (double)Q.lat_D[at], e = (double)Q.lat_eps[at], z = (double)Q.lat_z[at];
+        as += a; d0 += a * D; d1 += a * D * e; z1 += a * z; z2 += a * z * z;
+        if (blackbox) be += Q.lat_b[n] * e;
+    }
+    const double asum = total(as), D0 = total(d0), D1 = total(d1), Z1 = total(z1), Z2 = total(z2), BE = total(be);
+    if (tid == 0) {
+        const double sd = bnn_uniform_value_d(Q, Q.lat_uniform[T + t]), s0d = bnn_uniform_value_d(Q, Q.lat_uniform[3u * T + t]);
+        const double ew = (double)Q.entropy_weight, pw = (double)Q.prior_weight, fs = blackbox ? (double)Q.fs[0] : 0.0;
+        float* const g = Q.rowg + 4 * (size_t)Q.R;
+        g[t] = (float)(D0 + ew * asum - fs);
+        g[T + t] = (float)(D1 + ew * asum / sd - (blackbox ? BE + fs / sd : 0.0));
+        g[2u * T + t] = (float)(pw * Z1 / s0d);
+        g[3u * T + t] = (float)(pw * (Z2 - asum) / s0d);
     }
 }
 
@@ -787,6 +969,12 @@ struct bsvi_bnn {
     uint32_t family = BSVI_DIST_NORMAL;      // the loc-scale likelihood's family (bsvi_bnn_set_likelihood_family): Normal, Laplace or Cauchy
     uint8_t* row_kind = nullptr; // the prior of every row, in the blob (all Normal until bsvi_bnn_set_row_priors)
     bool mixed = false;          // some row is Laplace or Cauchy: the MIXED instantiations of bnn_draw / bnn_row_sums
+    // latent prior scales (bsvi_bnn_set_scale_latents; 0: none): their tables and the entry -> item lists extended by their items, in a
+    // blob of their own; the LATENT instantiations of bnn_draw / bnn_row_sums, bnn_latent_terms and the workspace behind everything else
+    uint32_t n_latents = 0;
+    void* lat_blob = nullptr;
+    const uint8_t* row_latent = nullptr; const uint32_t* lat_uniform = nullptr; const uint32_t* lat_count = nullptr;
+    std::vector<uint32_t> row_uniform_host;      // [4][R], kept for that call
     mutable std::atomic<bool> launched{false};      // a launch was made: the priors stay as they are
     uint64_t act_floats = 0, delta_floats = 0;      // per (sample, minibatch row)
     uint32_t act_off[BNN_MAX_LAYERS] = {};
@@ -1381,6 +1569,7 @@ static int bnn_create(const bsvi_bnn_desc* desc, const bool normal, const uint32
     p->d = *desc;
     p->layers.assign(desc->layers, desc->layers + desc->n_layers);
     p->d.layers = nullptr;
+    p->row_uniform_host.assign(desc->row_uniform, desc->row_uniform + 4 * (size_t)R);
     p->R = R; p->P = desc->n_features; p->C = width; p->H1 = desc->layers[0].rows;
     p->R1 = p->H1 * p->P; p->Rs = R - p->R1;
     p->Kp = (p->P + 31) / 32 * 32; p->P_ld = (p->P + 3) / 4 * 4;
@@ -1486,9 +1675,58 @@ extern "C" int bsvi_bnn_set_likelihood_family(bsvi_bnn* p, uint32_t kind) {
     return BSVI_OK;
 }
 
+// latent prior scales (include/bsvi.h).  Before the first launch only: the launches choose their instantiations and their workspace
+// from what stands here.  The entry -> item lists are built again with the latents' items 4 R + q T + t behind the rows' of every entry
+// (a fixed order of additions), and bnn_epilogue leaves the latents' gradients at those items of rowg.
+constexpr uint32_t BNN_MAX_LATENTS = 18;
+extern "C" int bsvi_bnn_set_scale_latents(bsvi_bnn* p, uint32_t n_latents, const uint8_t* row_latent, uint32_t n_rows, const uint32_t* latent_uniform) {
+    if (!p || !row_latent || !latent_uniform) return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_scale_latents: null argument");
+    if (n_rows != p->R) return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_scale_latents: n_rows is not the model's number of rows");
+    if (!n_latents || n_latents > BNN_MAX_LATENTS) return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_scale_latents: 1 .. 18 latents");
+    if (p->launched.load()) return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_scale_latents: the model was launched already (set the latents before the first launch)");
+    const uint32_t T = n_latents, R = p->R, NG = p->d.n_uniform_grad;
+    for (uint32_t i = 0; i < 4u * T; ++i)
+        if (latent_uniform[i] >= p->d.n_uniform) return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_scale_latents: latent parameter out of the uniform table");
+    std::vector<uint32_t> count(T, 0u);
+    for (uint32_t r = 0; r < R; ++r) {
+        if (row_latent[r] == 0xFFu) continue;
+        if (row_latent[r] >= T) return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_scale_latents: a row names a latent past n_latents");
+        ++count[row_latent[r]];
+    }
+    const std::vector<uint32_t>& ru = p->row_uniform_host;
+    std::vector<uint32_t> ur_ptr(NG + 1, 0u), ur_item, n_items(NG, 0u);
+    for (size_t i = 0; i < 4 * (size_t)R; ++i) if (ru[i] < NG) ++n_items[ru[i]];
+    for (uint32_t i = 0; i < 4u * T; ++i) if (latent_uniform[i] < NG) ++n_items[latent_uniform[i]];
+    for (uint32_t k = 0; k < NG; ++k) ur_ptr[k + 1] = ur_ptr[k] + n_items[k];
+    ur_item.resize(ur_ptr[NG]);
+    std::vector<uint32_t> at(ur_ptr.begin(), ur_ptr.end() - 1);
+    for (size_t i = 0; i < 4 * (size_t)R; ++i) if (ru[i] < NG) ur_item[at[ru[i]]++] = (uint32_t)i;
+    for (uint32_t i = 0; i < 4u * T; ++i) if (latent_uniform[i] < NG) ur_item[at[latent_uniform[i]]++] = 4u * R + i;
+    std::vector<uint8_t> bytes(((size_t)R + 3) / 4 * 4, (uint8_t)0xFFu);
+    memcpy(bytes.data(), row_latent, R);
+    const size_t sizes[5] = {ur_ptr.size() * 4, ur_item.size() * 4, bytes.size(), 4 * (size_t)T * 4, (size_t)T * 4};
+    const void* srcs[5] = {ur_ptr.data(), ur_item.data(), bytes.data(), latent_uniform, count.data()};
+    size_t offs[5], total = 0;
+    for (int i = 0; i < 5; ++i) { offs[i] = total; total += align_up(sizes[i], 256); }
+    std::vector<char> host(total + 256, 0);
+    for (int i = 0; i < 5; ++i) if (sizes[i]) memcpy(&host[offs[i]], srcs[i], sizes[i]);
+    void* blob = nullptr;
+    hipError_t e = hipMalloc(&blob, host.size());
+    if (e == hipSuccess) e = hipMemcpy(blob, host.data(), host.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { if (blob) (void)hipFree(blob); return fail(BSVI_ERR_HIP, std::string("bsvi_bnn_set_scale_latents: ") + hipGetErrorString(e)); }
+    if (p->lat_blob) (void)hipFree(p->lat_blob);
+    p->lat_blob = blob;
+    char* base = (char*)blob;
+    p->ur_ptr = (const uint32_t*)(base + offs[0]); p->ur_item = (const uint32_t*)(base + offs[1]);
+    p->row_latent = (const uint8_t*)(base + offs[2]); p->lat_uniform = (const uint32_t*)(base + offs[3]); p->lat_count = (const uint32_t*)(base + offs[4]);
+    p->n_latents = T;
+    return BSVI_OK;
+}
+
 extern "C" void bsvi_bnn_destroy(bsvi_bnn* p) {
     if (!p) return;
     if (p->dev_blob) (void)hipFree(p->dev_blob);
+    if (p->lat_blob) (void)hipFree(p->lat_blob);
     if (p->jit_module) (void)hipModuleUnload(p->jit_module);
     if (p->mid_module) (void)hipModuleUnload(p->mid_module);
     delete p;
@@ -1508,6 +1746,7 @@ extern "C" int bsvi_bnn_middle(const bsvi_bnn* p) {
 struct BnnLayout {
     size_t rowp, idx, lab, Xb, Xb_bf, XbT_bf, W1f, Wp, Wsm, a1T, acts, deltas, liknb, da1T, dlogp, GT, gsm, lik, pv, qv, sums, rowg, hpart, partial, fs, total;
     size_t sigt, gsig, gsd;
+    size_t lat_l, lat_itau, lat_eps, lat_D, lat_z, lat_upart, lat_f, lat_q, lat_b;
     uint32_t n_pad, NC, row_chunks, row_blocks;
 };
 static BnnLayout bnn_layout(const bsvi_bnn* p, uint32_t n_local) {
@@ -1532,10 +1771,17 @@ static BnnLayout bnn_layout(const bsvi_bnn* p, uint32_t n_local) {
     L.GT = take(p->exact ? (size_t)p->P * L.NC * 4 : (size_t)L.NC * p->P_ld * 4);
     L.gsm = take((size_t)L.n_pad * (p->Rs ? p->Rs : 1) * 4); L.lik = take((size_t)L.n_pad * 4);
     L.pv = take((size_t)L.row_chunks * L.n_pad * 4); L.qv = take((size_t)L.row_chunks * L.n_pad * 4);
-    L.sums = take(4 * (size_t)p->R * 4); L.rowg = take(4 * (size_t)p->R * 4); L.hpart = take(2 * (size_t)L.row_blocks * 8);
+    L.sums = take(4 * (size_t)p->R * 4); L.rowg = take(4 * ((size_t)p->R + p->n_latents) * 4); L.hpart = take(2 * (size_t)L.row_blocks * 8);
     L.partial = take((2 + (size_t)p->d.n_uniform_grad) * 4); L.fs = take(256);
     // (a learnable sigma's three arrays behind everything else: nothing moves, and nothing is added, for the networks without one)
     if (p->scale_learn) { L.sigt = take(nb * p->C * 4); L.gsig = take((size_t)L.n_pad * p->C * 4); L.gsd = take((size_t)p->C * 8); }
+    // (latent prior scales: behind everything else, for such handles only)
+    if (p->n_latents) {
+        const size_t tn = (size_t)p->n_latents * L.n_pad * 4;
+        L.lat_l = take(tn); L.lat_itau = take(tn); L.lat_eps = take(tn); L.lat_D = take(tn); L.lat_z = take(tn);
+        L.lat_upart = take((size_t)L.row_chunks * tn);
+        L.lat_f = take((size_t)L.n_pad * 8); L.lat_q = take((size_t)L.n_pad * 8); L.lat_b = take((size_t)L.n_pad * 8);
+    }
     L.total = o + 256;
     return L;
 }
@@ -1593,6 +1839,12 @@ static int bnn_fill(const bsvi_bnn* p, const bsvi_bnn_args* a, BParams& Q, BnnLa
     Q.fs = (float*)(ws + L.fs); Q.row_chunks = L.row_chunks;
     if (p->scale_learn) { Q.sigt = (float*)(ws + L.sigt); Q.gsig = (float*)(ws + L.gsig); Q.gsd = (double*)(ws + L.gsd); }
     Q.row_kind = p->row_kind;
+    if (p->n_latents) {
+        Q.n_latents = p->n_latents; Q.row_latent = p->row_latent; Q.lat_uniform = p->lat_uniform; Q.lat_count = p->lat_count;
+        Q.lat_l = (float*)(ws + L.lat_l); Q.lat_itau = (float*)(ws + L.lat_itau); Q.lat_eps = (float*)(ws + L.lat_eps);
+        Q.lat_D = (float*)(ws + L.lat_D); Q.lat_z = (float*)(ws + L.lat_z); Q.lat_upart = (float*)(ws + L.lat_upart);
+        Q.lat_f = (double*)(ws + L.lat_f); Q.lat_q = (double*)(ws + L.lat_q); Q.lat_b = (double*)(ws + L.lat_b);
+    }
     return BSVI_OK;
 }
 
@@ -1600,8 +1852,10 @@ static int bnn_launch(const bsvi_bnn* p, const BParams& Q, const BnnLayout& L, h
     const uint32_t head_n = std::max(Q.R, Q.B_pad);
     const uint32_t head_blocks = (head_n + 255) / 256, gy = (std::max(Q.Kp, Q.P_ld) + 255) / 256;
     p->launched.store(true);
-    hipLaunchKernelGGL(bnn_head_gather, dim3(Q.B_pad * gy + head_blocks), dim3(256), 0, s, Q, gy, head_blocks);
-    if (p->mixed) hipLaunchKernelGGL(bnn_draw<true>, dim3(L.row_chunks, (Q.n_pad + 3u) / 4u), dim3(256), 0, s, Q);
+    const uint32_t lat_blocks = (Q.n_latents * Q.n_pad + 255u) / 256u;      // (none without latent prior scales)
+    hipLaunchKernelGGL(bnn_head_gather, dim3(Q.B_pad * gy + head_blocks + lat_blocks), dim3(256), 0, s, Q, gy, head_blocks);
+    if (Q.n_latents) hipLaunchKernelGGL((bnn_draw<true, true>), dim3(L.row_chunks, (Q.n_pad + 3u) / 4u), dim3(256), 0, s, Q);
+    else if (p->mixed) hipLaunchKernelGGL(bnn_draw<true>, dim3(L.row_chunks, (Q.n_pad + 3u) / 4u), dim3(256), 0, s, Q);
     else hipLaunchKernelGGL(bnn_draw<false>, dim3(L.row_chunks, (Q.n_pad + 3u) / 4u), dim3(256), 0, s, Q);
     int rc;
     const bool mid = bnn_mid_ready(p);
@@ -1643,9 +1897,14 @@ static int bnn_launch(const bsvi_bnn* p, const BParams& Q, const BnnLayout& L, h
     if (Q.exact) rc = bsvi_xgemm_nt(Q.XbT_bf, nullptr, Q.dlogp, (long)Q.NC * Q.B_pad, Q.GT, (int)Q.NC, (int)Q.P, (int)Q.NC, (int)Q.B_pad, s);
     else rc = bsvi_gemm_f32(1, Q.da1T, (int)Q.B_pad, Q.Xb, (int)Q.P_ld, Q.GT, (int)Q.P_ld, (int)Q.NC, (int)Q.P, (int)Q.B_pad, s);
     if (rc) return rc;
-    if (p->mixed) hipLaunchKernelGGL(bnn_row_sums<true>, dim3(((Q.R + 3) / 4 + 3) / 4), dim3(256), 0, s, Q);
+    if (Q.n_latents) {
+        hipLaunchKernelGGL((bnn_row_sums<true, true>), dim3(((Q.R + 3) / 4 + 3) / 4), dim3(256), 0, s, Q);
+        hipLaunchKernelGGL(bnn_latent_terms, dim3(Q.n_pad / 256u + (Q.n_pad % 256u ? 1u : 0u)), dim3(256), 0, s, Q);
+    }
+    else if (p->mixed) hipLaunchKernelGGL(bnn_row_sums<true>, dim3(((Q.R + 3) / 4 + 3) / 4), dim3(256), 0, s, Q);
     else hipLaunchKernelGGL(bnn_row_sums<false>, dim3(((Q.R + 3) / 4 + 3) / 4), dim3(256), 0, s, Q);
     hipLaunchKernelGGL(bnn_epilogue, dim3(1), dim3(1024), 0, s, Q, L.row_blocks);
+    if (Q.n_latents) hipLaunchKernelGGL(bnn_latent_grads, dim3(Q.n_latents), dim3(256), 0, s, Q);
     if (Q.n_uniform_grad) hipLaunchKernelGGL(bnn_uniform_grads, dim3((Q.n_uniform_grad + 255) / 256), dim3(256), 0, s, Q);
     HIP_TRY(hipGetLastError());
     return BSVI_OK;

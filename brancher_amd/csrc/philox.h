@@ -18,6 +18,11 @@
 // takes ONE word, word c & 3 (x, y, z, w) of the same call c >> 2, through laplace_noise / cauchy_noise (bsvi_device.h) — the Laplace
 // draw is -sign(v) log1p(-|v|) of that uniform base noise v, the Cauchy draw the tangent itself.  The weights of that pass are the BNN
 // path's ordinary draw (c1 = (row >> 2) | 0x40000000, the seed as it is).
+//
+// Latent prior scales of the Bayesian neural networks (bsvi_bnn_set_scale_latents): with quads = ceil(n_rows / 4), latent t takes
+// normal t & 3 of the ordinary row-quad call whose quad index is quads + (t >> 2) — c1 = (quads + (t >> 2)) | 0x40000000, the same
+// counters, key and box_muller_fast pairing as the rows, behind every quad a row uses.  A pure function of (seed, offset, global sample,
+// t): the same over sample shards.  It is reported in row n_rows + t of noise_out and replayed from there when the caller hands noise in.
 #pragma once
 #if !defined(__HIPCC_RTC__)
 #include <hip/hip_runtime.h>

@@ -1353,6 +1353,11 @@ def _bnn_posterior_sample(model, compiled, number_samples, input_values):
     from brancher_amd import bnn
     from brancher_amd.variables import RootVariable
     p, dev, N = compiled.program, compiled.device, int(number_samples)
+    if getattr(p, "scale_latents", None):
+        # (a dict without the latents would look complete: the draw of a scale latent is not part of `predict`)
+        raise NotImplementedError("_get_posterior_sample of a Bayesian neural network with scale latents (%s) is not implemented: the "
+                                  "sample would lack them; CompiledBnn.predict serves the posterior predictive"
+                                  % ", ".join(repr(l["name"]) for l in p.scale_latents))
     by_name = {v.name: v for v in model.flatten()}
     x_var, lik_var = by_name[p.x_name], by_name[p.likelihood_name]
     _sample_tick[0] += 1

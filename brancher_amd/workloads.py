@@ -781,25 +781,71 @@ def _bnn_activations(activations, activation, n_hidden_layers):
     return list(activations)
 
 
-def _bnn_prior(api, prior, prior_loc, prior_scale):
+def _bnn_scale_latents(scale_latent, tensor_names):
+    """`scale_latent=` of the two builders -> {tensor name: (latent name, multiplier)}: None; "layer" — one latent `tau<l>` per layer,
+    shared by its weights and bias (a scale head's two tensors share `tau_scale`); "global" — one latent `tau` for every tensor; or a
+    dict from latent name to its tensors, each a name or a (name, multiplier b > 0) pair: the tensor's prior scale is b * latent"""
+    if scale_latent is None:
+        return {}
+    if scale_latent == "global":
+        return {name: ("tau", 1.0) for name in tensor_names}
+    if scale_latent == "layer":
+        return {name: ("tau" + (name[7:] if name.startswith("weights") else name[1:]), 1.0) for name in tensor_names}
+    if not isinstance(scale_latent, dict):
+        raise ValueError("scale_latent is None, \"layer\", \"global\" or a dict from latent name to tensor names")
+    out = {}
+    for latent, members in scale_latent.items():
+        for m in members:
+            name, b = (m, 1.0) if isinstance(m, str) else (m[0], float(m[1]))
+            if name not in tensor_names:
+                raise ValueError("scale_latent names the tensor %r, the network has %s" % (name, ", ".join(tensor_names)))
+            if name in out:
+                raise ValueError("scale_latent names the tensor %r under two latents" % name)
+            out[name] = (latent, b)
+    return out
+
+
+def _bnn_prior(api, prior, prior_loc, prior_scale, scale_latent=None, scale_latent_prior=(0., 1.), scale_latent_q=None, tensor_names=()):
     """the prior of the two Bayesian-neural-network builders' tensors: one of "normal" / "laplace" / "cauchy" for every tensor, or a
     dict by tensor name ("weights1", "b1", ...; tensors it does not name are Normal) -> (name, shape) -> the prior variable.
     Without the builders' new keywords that is `NormalVariable(zeros, prior_scale * ones, name)` as it always was — whose auto-created
     roots `<name>_loc` / `<name>_scale` are, by the reference's name-collision rule, the POSTERIOR's parameters of the same names.  With
     them the prior's loc and scale are roots of their own names, `<name>_prior_loc` / `<name>_prior_scale`: constants of the model,
-    so that the prior asked for is the prior scored."""
+    so that the prior asked for is the prior scored.
+    scale_latent (`_bnn_scale_latents`): a hierarchical prior — the scale of a tensor under a latent is `b * tau` with tau a
+    `LogNormalVariable(<tau>_prior_loc, <tau>_prior_scale, <tau>)` whose two parameters (scale_latent_prior) are roots of their own names
+    too, and prior_scale is not used for that tensor; `make.latent_posteriors()` are the latents' learnable LogNormal posteriors
+    (scale_latent_q = (loc, scale); default: the prior's loc and 0.2) for the posterior model, in the order the latents were first used."""
     classes = {"normal": api.NormalVariable, "laplace": api.LaplaceVariable, "cauchy": api.CauchyVariable}
+    under = _bnn_scale_latents(scale_latent, list(tensor_names))
+    taus = {}
+
+    def tau_of(latent):
+        if latent not in taus:
+            taus[latent] = api.LogNormalVariable(api.RootVariable(float(scale_latent_prior[0]), latent + "_prior_loc"),
+                                                 api.RootVariable(float(scale_latent_prior[1]), latent + "_prior_scale"), latent)
+        return taus[latent]
+
     kinds = list(prior.values()) if isinstance(prior, dict) else [prior]
     if any(k not in classes for k in kinds):
         raise ValueError("prior is 'normal', 'laplace' or 'cauchy', or a dict of them by tensor name")
     as_before = all(k == "normal" for k in kinds) and float(prior_loc) == 0.0
 
     def make(name, shape):
+        if name in under:
+            latent, b = under[name]
+            cls = classes[prior.get(name, "normal") if isinstance(prior, dict) else prior]
+            return cls(api.RootVariable(prior_loc + np.zeros(shape), name + "_prior_loc"), tau_of(latent) if b == 1.0 else b * tau_of(latent), name)
         if as_before:
             return api.NormalVariable(np.zeros(shape), prior_scale * np.ones(shape), name)
         cls = classes[prior.get(name, "normal") if isinstance(prior, dict) else prior]
         return cls(api.RootVariable(prior_loc + np.zeros(shape), name + "_prior_loc"),
                    api.RootVariable(prior_scale * np.ones(shape), name + "_prior_scale"), name)
+
+    def latent_posteriors():
+        loc, scale = scale_latent_q if scale_latent_q is not None else (scale_latent_prior[0], 0.2)
+        return [api.LogNormalVariable(float(loc), float(scale), latent, learnable=True) for latent in taus]
+    make.latent_posteriors = latent_posteriors
     return make
 
 
@@ -813,7 +859,8 @@ def _bnn_features(rng, data, dataset_size, n_features):
 
 def build_bayesian_neural_network(api, dataset_size=48, batch_size=30, n_features=784, n_hidden=20, n_classes=10, seed=0,
                                   prior_scale=10., q_scale=0.2, q_scale1=None, q_loc_scale=0.0, pixels="uint8",
-                                  activation="tanh", hidden2=0, widths=None, activations=None, teacher=None, prior="normal", prior_loc=0.):
+                                  activation="tanh", hidden2=0, widths=None, activations=None, teacher=None, prior="normal", prior_loc=0.,
+                                  scale_latent=None, scale_latent_prior=(0., 1.), scale_latent_q=None):
     """`tests/test_MNIST_bayesian_neural_network.py:20-60` of the reference: a one-hidden-layer network whose weight matrices AND
     biases are latent — weights1 [H, P], b1 [H, 1], weights2 [C, H], b2 [C, 1], priors N(0, 10), a mean-field Normal posterior
     over all four (scale 0.2) — `tanh(matmul(weights1, x) + b1)`, `matmul(weights2, hidden) + b2` as the logits of an observed
@@ -829,10 +876,13 @@ def build_bayesian_neural_network(api, dataset_size=48, batch_size=30, n_feature
     second build with another `seed` is held-out data of the same task (examples/bnn_predict.py); None: uniformly random labels.
     prior: "normal" | "laplace" | "cauchy" — the family of every weight's and bias's prior (loc prior_loc, scale prior_scale), or a dict
     by tensor name ("weights1", "b1", ...: the tensors it leaves out are Normal); its parameters are then constants of the model under
-    names of their own (`_bnn_prior`).  Without the two keywords every model is built draw for draw as before."""
+    names of their own (`_bnn_prior`).  scale_latent: None | "layer" | "global" | a dict from latent name to tensor names — a
+    hierarchical prior whose scales are LogNormal latents with a learnable LogNormal posterior (`_bnn_scale_latents`, `_bnn_prior`;
+    scale_latent_prior / scale_latent_q: their (loc, scale)).  Without these keywords every model is built draw for draw as before."""
     BF = api.BF
-    prior_of = _bnn_prior(api, prior, prior_loc, prior_scale)
     n_features, n_classes, widths = _bnn_widths(widths, n_features, [n_hidden] + ([hidden2] if hidden2 else []), n_classes)
+    prior_of = _bnn_prior(api, prior, prior_loc, prior_scale, scale_latent, scale_latent_prior, scale_latent_q,
+                          [t % l for l in range(1, len(widths)) for t in ("weights%d", "b%d")])
     if pixels in ("integers", "normal"):
         rng = np.random.RandomState(seed)
         X = _bnn_features(rng, pixels, dataset_size, n_features)
@@ -866,14 +916,15 @@ def build_bayesian_neural_network(api, dataset_size=48, batch_size=30, n_feature
     k = api.CategoricalVariable(logits=layer, name="k") if n_classes > 1 else api.BinomialVariable(1, logits=layer, name="k")
     model = api.ProbabilisticModel([k])
     k.observe(y)
-    model.set_posterior_model(api.ProbabilisticModel(q_vars))
+    model.set_posterior_model(api.ProbabilisticModel(q_vars + prior_of.latent_posteriors()))
     return model
 
 
 def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_hidden=9, n_outputs=1, hidden2=0, activation="tanh",
                          sigma=0.5, data="integers", bias=True, seed=0, prior_scale=2., q_scale=0.1, q_scale1=None, q_loc_scale=0.5,
                          widths=None, activations=None, learnable_sigma=False, sigma_init=None, prior="normal", prior_loc=0.,
-                         scale_head=None, scale_floor=0.05, likelihood="normal"):
+                         scale_head=None, scale_floor=0.05, likelihood="normal", scale_latent=None, scale_latent_prior=(0., 1.),
+                         scale_latent_q=None):
     """The regression model of the Bayesian-neural-network family: the network of `build_bayesian_neural_network` (latent weight
     matrices and biases under a mean-field Normal posterior) as the loc of an observed Normal,
     `y ~ NormalVariable(matmul(weights2, act(matmul(weights1, x) + b1)) + b2, sigma)`, the targets [DS, C, 1] an EmpiricalVariable that
@@ -892,12 +943,12 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
     be a dict that names them); the teacher's noise scale then depends on the input through a head of its own, and sigma / learnable_sigma
     are not used.  likelihood: "normal", "laplace" (median / L1 regression: an observed `LaplaceVariable`) or "cauchy" (the heavy-tailed
     fit: an observed `CauchyVariable`) — the family of y, with every form of the scale above; the teacher's noise is then drawn from that
-    family at scale sigma.  Without these keywords every model is built draw for draw as before."""
+    family at scale sigma.  scale_latent / scale_latent_prior / scale_latent_q: a hierarchical prior, as for
+    `build_bayesian_neural_network`.  Without these keywords every model is built draw for draw as before."""
     BF = api.BF
     if likelihood not in ("normal", "laplace", "cauchy"):
         raise ValueError("likelihood is \"normal\", \"laplace\" or \"cauchy\"")
     Observed = dict(normal=api.NormalVariable, laplace=api.LaplaceVariable, cauchy=api.CauchyVariable)[likelihood]
-    prior_of = _bnn_prior(api, prior, prior_loc, prior_scale)
     if scale_head not in (None, "softplus", "exp", "sigmoid"):
         raise ValueError("scale_head is None, \"softplus\", \"exp\" or \"sigmoid\"")
     if scale_head and (learnable_sigma or sigma_init is not None):
@@ -908,6 +959,9 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
         raise ValueError("sigma_init is the start of a learnable sigma")
     n_features, n_outputs, widths = _bnn_widths(widths, n_features, ([n_hidden] if n_hidden else []) + ([hidden2] if n_hidden and hidden2 else []),
                                                 n_outputs)
+    prior_of = _bnn_prior(api, prior, prior_loc, prior_scale, scale_latent, scale_latent_prior, scale_latent_q,
+                          [t % l for l in range(1, len(widths)) for t in (("weights%d", "b%d") if bias else ("weights%d",))]
+                          + ((["weights_scale", "b_scale"] if bias else ["weights_scale"]) if scale_head else []))
     rng = np.random.RandomState(seed)
     X = _bnn_features(rng, data, dataset_size, n_features)
     acts = _bnn_activations(activations, activation, len(widths) - 2)
@@ -964,7 +1018,7 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
         y = Observed(layer, scale_floor + getattr(BF, scale_head)(raw), "y")
         model = api.ProbabilisticModel([y])
         y.observe(targets)
-        model.set_posterior_model(api.ProbabilisticModel(q_vars))
+        model.set_posterior_model(api.ProbabilisticModel(q_vars + prior_of.latent_posteriors()))
         return model
     if sigma_init is not None:
         sig = np.asarray(sigma_init, dtype=np.float64).reshape(-1)
@@ -976,7 +1030,7 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
     y = Observed(layer, scale, "y", learnable=bool(learnable_sigma is True))
     model = api.ProbabilisticModel([y])
     y.observe(targets)
-    model.set_posterior_model(api.ProbabilisticModel(q_vars))
+    model.set_posterior_model(api.ProbabilisticModel(q_vars + prior_of.latent_posteriors()))
     return model
 
 

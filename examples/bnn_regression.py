@@ -15,6 +15,7 @@ MI355X:
     python examples/bnn_regression.py --scale-head       # input-dependent noise: a second head, sigma(x) = 0.05 + softplus(raw(x))
     python examples/bnn_regression.py --likelihood laplace    # median (L1) regression: LaplaceVariable(chain, b, "y")
     python examples/bnn_regression.py --likelihood cauchy     # the heavy-tailed fit for data with outliers: CauchyVariable(chain, gamma, "y")
+    python examples/bnn_regression.py --hierarchical     # a latent prior scale per layer: NormalVariable(0, tau1, "weights1"), tau1 LogNormal
 
 With --learn-sigma the model starts from a guess of 1.0 and learns the noise scale with the posterior (a learnable root `y_scale`
 behind a softplus in the joint model's parameter group, stepped from the second iteration on, as the reference steps it); the learned
@@ -27,7 +28,10 @@ on the hidden layer gives the scale of the Normal, `0.05 + BF.softplus(BF.matmul
 rest; the teacher's noise varies from row to row, and the run prints how well the predicted scale follows the size of the residuals.
 With --likelihood the observed variable is a Laplace or a Cauchy variable over the same chain (it combines with every other switch): the
 teacher's noise is drawn from that family, so under "cauchy" a few targets lie far from the rest — the run prints the median absolute
-error beside the RMSE, which those few dominate.
+error beside the RMSE, which those few dominate.  With --hierarchical the prior scale of every layer is itself a latent: `tau1`,
+a `LogNormalVariable(0, 1)`, scales the priors of weights1 and b1, `tau2` those of weights2 and b2, each under a learnable LogNormal
+posterior (the hierarchical BNN of the textbooks: per-layer shrinkage learned with the weights; it combines with --prior).  The run is
+the 64-8-1 network of --prior, for its reason, and prints the posterior medians exp(m_t) of the layers' scales after training.
 """
 import os
 import sys
@@ -55,6 +59,10 @@ if "--prior" in sys.argv[1:]:
     if PRIOR not in ("laplace", "cauchy"):
         sys.exit("--prior laplace | cauchy")
     KW.update(prior=PRIOR, prior_scale=0.5, dataset_size=2048, batch_size=512, n_features=64, n_hidden=8)
+HIERARCHICAL = "--hierarchical" in sys.argv[1:]
+if HIERARCHICAL:
+    KW.update(scale_latent="layer", scale_latent_prior=(0., 1.), scale_latent_q=(0., 0.2), dataset_size=2048, batch_size=512, n_features=64,
+              n_hidden=8)
 LIKELIHOOD = "normal"
 if "--likelihood" in sys.argv[1:]:
     LIKELIHOOD = (sys.argv[sys.argv.index("--likelihood") + 1:] or [""])[0]
@@ -111,3 +119,10 @@ if SCALE_HEAD:
     quarter = len(order) // 4
     print("predicted noise scale: %.3f .. %.3f over the rows; mean |residual| in the quarter of the rows with the smallest predicted "
           "scale %.3f, with the largest %.3f" % (sigma.min(), sigma.max(), resid[order[:quarter]].mean(), resid[order[-quarter:]].mean()))
+if HIERARCHICAL:
+    c = engine.compile_model(model)
+    params = c.named_params()
+    for latent, members in c.program.summary()["scale_latents"].items():
+        print("posterior median of %s (the prior scale of %s): exp(%s_loc) = %.3f (started at %.3f)"
+              % (latent, ", ".join(name for name, _ in members), latent, float(np.exp(params[latent + "_loc"].reshape(-1)[0])),
+                 float(np.exp(KW["scale_latent_q"][0]))))

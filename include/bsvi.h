@@ -577,6 +577,7 @@ typedef struct bsvi_bnn_args {
     uint32_t reserved0;
     const float* params_dev;         /* [n_params]                                                   */
     const float* noise_dev;          /* eps [n_rows][n_samples_local] or NULL -> Philox               */
+                                     /* (after bsvi_bnn_set_scale_latents: [n_rows + n_latents][n_samples_local], here and in noise_out_dev) */
     const int32_t* indices_dev;      /* minibatch rows [batch_size] or NULL -> drawn on the device    */
     uint64_t seed, offset;
     uint32_t n_samples_local, n_samples_global, sample_base, reserved;
@@ -646,6 +647,22 @@ int bsvi_bnn_set_row_priors(bsvi_bnn* b, const uint8_t* kinds, uint32_t n_rows);
  * 2 sigma_c^2 for Laplace, and with var_out set a Cauchy model is BSVI_ERR_UNSUPPORTED ("the Cauchy likelihood has no variance"), before
  * anything is launched.  No struct changes, the ABI version stays. */
 int bsvi_bnn_set_likelihood_family(bsvi_bnn* b, uint32_t kind);
+/* LATENT PRIOR SCALES (a hierarchical prior): n_latents <= 18 scalar latents tau_t with a LogNormal prior and a mean-field LogNormal
+ * posterior, tau_t = exp(l), l = m_t + s_t eps.  row_latent[r] is the latent that scales the prior of row r, or 0xFF for none; the prior
+ * scale of such a row is  b_r tau_t  per sample, with b_r what the row's prior scale entry holds (a constant of the model).
+ * latent_uniform is [4][n_latents]: the uniform entries of q loc m_t, q scale s_t, prior loc m0_t and prior scale s0_t.  Valid after any
+ * of the create calls and before the first launch: a null pointer, n_rows other than the model's, n_latents outside 1 .. 18, an entry past
+ * the uniform table, a byte >= n_latents that is not 0xFF or a call after a launch is BSVI_ERR_INVALID.  Per sample, with K_t the number
+ * of rows under t and z = (l - m0_t) / s0_t:
+ *     f     += prior_weight sum_t (-(K_t + 1) l - log s0_t - 1/2 log 2 pi - 1/2 z^2)  +  entropy_weight sum_t (m_t + 1/2 + 1/2 log 2 pi + log s_t)
+ *     log q += sum_t (-l - log s_t - 1/2 log 2 pi - 1/2 eps^2)
+ * and the rows keep their per-sample form in u = (w - mu0) / (b_r tau_t).  The four gradients of every latent reach their uniform entries
+ * as a row's do (BlackBox: the score term of m_t and s_t with them); every sum is taken in a fixed order, no atomics.
+ * For such a handle noise_dev / noise_out_dev of bsvi_bnn_args are [n_rows + n_latents][n_samples_local]: the draw of latent t is row
+ * n_rows + t.  Without a caller's noise it is normal t & 3 of the row-quad Philox call with quad index ceil(n_rows / 4) + (t >> 2): a pure
+ * function of (seed, offset, global sample, t).  bsvi_bnn_workspace_bytes grows for such handles only; bsvi_bnn_predict is unchanged
+ * (the weights' posterior does not involve the latents: its noise stays [n_rows][N]).  No struct changes, the ABI version stays. */
+int bsvi_bnn_set_scale_latents(bsvi_bnn* b, uint32_t n_latents, const uint8_t* row_latent, uint32_t n_rows, const uint32_t* latent_uniform);
 void bsvi_bnn_destroy(bsvi_bnn* b);
 size_t bsvi_bnn_workspace_bytes(const bsvi_bnn* b, uint32_t n_samples_local);
 int bsvi_bnn_exact_data(const bsvi_bnn* b);
