@@ -5,8 +5,10 @@ product against the redrawn normals) against
   (2) the f32-input MFMA kernels (BSVI_DENSE_XGEMM=0),
 over shapes that exercise every edge of the tiling: classes that do not divide the 64 weight rows of a workgroup, a
 feature count that is not a multiple of the 128-feature chunk or of the 112-row tile of x^T, minibatches below and above
-one 512-row tile, sample counts that leave ragged sample groups, the Bernoulli likelihood (one output), both estimators,
-emitted and supplied noise.  Reference behaviour: examples/MNIST_logistic_regression.py:15-54 through
+one 512-row tile, sample counts that leave ragged sample groups, a single output, both estimators, emitted and supplied noise.
+(The `C = 1` shapes are Categorical models with ONE class: log-probability 0 and likelihood gradient 0 whatever the labels, NOT the
+Bernoulli likelihood — they compare the prior, the entropy and the launch plan.  The Bernoulli / Binomial(1) likelihood on the same
+shapes, against the oracle: tests/test_gpu_dense_models.py.)  Reference behaviour: examples/MNIST_logistic_regression.py:15-54 through
 brancher/variables.py:843-870 (pinned against the reference itself by the `logreg_pixels_*` fixtures in test_gpu_parity)."""
 import numpy as np
 import pytest
