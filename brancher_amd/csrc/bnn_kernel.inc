@@ -23,7 +23,7 @@
 // a literal in the generated kernels): with psi the family's score, -|u| - log(2 sigma) and psi = sign(u), or -log(1 + u^2) - log(pi sigma)
 // and psi = 2 u / (1 + u^2), and at every site  delta_c = wgt psi / sigma_c,  d f / d sigma_c = wgt (u psi - 1) / sigma_c  (the Normal:
 // psi = u) — so a learnable sigma's sums and a scale head's second delta are what they were with u psi in the place of u^2, and
-// bnn_mid_gen's sigma elements, which sum delta_c (y_c - z_c) = wgt u psi, need nothing.  The Normal arms keep their text.
+// bnn_mid_gen's sigma elements, which sum delta_c (y_c - z_c) = wgt u psi, need nothing.  One device function serves the three families (bnn_loc_scale_term).
 // All latent scalars form ONE vector of R rows (weights1 first: H_1 x P
 // rows r = h * P + p, then the other tensors); row r draws eps from the dense path's Philox counters (sample, r >> 2), so the
 // noise of a model is one [R][N] matrix as on the dense path, and reads its four parameters (q loc, q scale, prior loc, prior
@@ -42,10 +42,13 @@
 //   bnn_row_sums    per row: sum_n eps G, sum_n G, sum_n eps, sum_n eps^2 (fixed order)
 //   bnn_row_sums (its last part) / bnn_epilogue / bnn_uniform_grads / dense_param_kernel      closed-form prior and entropy terms, the value, chain rule
 // The two products carry the flops (2 x 2 N H_1 P B); everything else is elementwise or tiny and written for clarity.
+// The text of the two generated kernels, bnn_upper_gen and bnn_mid_gen, lives in bnn_source.h (host only: tests/test_bnn_source_cpu.py
+// holds it to recorded digests without a GPU); this file fills its input (bnn_source_net) and compiles what it writes (bnn_gen_ready).
 
 #include <atomic>
 
 #include "bnn_select.h"
+#include "bnn_source.h"
 
 constexpr uint32_t BNN_MAX_LAYERS = 8;
 
@@ -140,19 +143,24 @@ __device__ __forceinline__ float bnn_head_sigma(const uint32_t t, const float a,
     return a + b * g;
 }
 
-// the Laplace and Cauchy likelihoods in u = (y - z) / sigma: the value without its constant and the score psi(u) = -d value / d u, so that
-// every site seeds d f / d z = wgt psi / sigma and d f / d sigma = wgt (u psi - 1) / sigma as the Normal does with psi = u
-//     Laplace  -|u|,  psi = sign(u) with sign(0) = 0 (torch's abs backward);      Cauchy  -log(1 + u^2),  psi = 2 u / (1 + u^2)
+// the loc-scale likelihoods in u = (y - z) / sigma: the value without its constant, plus the term k that stands beside it in the sum, and
+// the score psi(u) = -d value / d u, so that every site seeds d f / d z = wgt psi / sigma and d f / d sigma = wgt (u psi - 1) / sigma
+//     Normal  -u^2 / 2,  psi = u;      Laplace  -|u|,  psi = sign(u) with sign(0) = 0 (torch's abs backward);
+//     Cauchy  -log(1 + u^2),  psi = 2 u / (1 + u^2)
 // (the hardware logarithm, as bnn_prior_value: the sum 1 + u^2 rounds to 6e-8 absolute, what any term of O(1) of the sample's sum does)
-__device__ __forceinline__ float bnn_family_value(const uint32_t family, const float u, float& psi) {
-    if (family == BSVI_DIST_LAPLACE) { psi = u > 0.0f ? 1.0f : (u < 0.0f ? -1.0f : 0.0f); return -fabsf(u); }
+// One launch-uniform branch per family with `+ k` inside it, each family's expression as it stood when each had a loop of its own.  The
+// Normal's -0.5f * u * u + k was contracted to one FMA there; here the compiler sinks the `+ k` the three branches share behind them and
+// leaves the product unfused (the per-sample f then differs in its last bit, tools/bnn_outputs_digest.py), so the FMA is spelled out.
+__device__ __forceinline__ float bnn_loc_scale_term(const uint32_t family, const float u, const float k, float& psi) {
+    if (family == BSVI_DIST_NORMAL) { psi = u; return fmaf(-0.5f * u, u, k); }
+    if (family == BSVI_DIST_LAPLACE) { psi = u > 0.0f ? 1.0f : (u < 0.0f ? -1.0f : 0.0f); return -fabsf(u) + k; }
     const float q = 1.0f + u * u;
     psi = 2.0f * u / q;
-    return -__logf(q);
+    return -__logf(q) + k;
 }
-// ... and the constant of either beside -log sigma: -log 2 | -log pi
+// ... and the constant of each beside -log sigma: -1/2 log 2 pi | -log 2 | -log pi
 __device__ __forceinline__ float bnn_family_const(const uint32_t family) {
-    return family == BSVI_DIST_LAPLACE ? -0.69314718055994530942f : -1.14472988584940017414f;
+    return family == BSVI_DIST_NORMAL ? -0.91893853320467274178f : (family == BSVI_DIST_LAPLACE ? -0.69314718055994530942f : -1.14472988584940017414f);
 }
 
 __device__ __forceinline__ float bnn_uniform_value(const BParams& Q, uint32_t k) {
@@ -180,7 +188,7 @@ __device__ __forceinline__ double bnn_uniform_value_d(const BParams& Q, uint32_t
 }
 
 // the per-sample part of log p(w) of a row in u = (w - mu0) / s0, by select (the kinds differ across the lanes of bnn_draw); the
-// sample-independent part is bnn_row_terms' / bnn_row_terms_mixed's
+// sample-independent part is bnn_row_terms' / bnn_row_terms_sums'
 // (log(1 + u^2) by the hardware logarithm: every lane evaluates all three, and log1pf's polynomial alone doubled the kernel's time at
 //  784-20-10; the sum 1 + u^2 rounds to 6e-8 absolute, the size of the rounding of the Normal's -u^2 / 2 at u ~ 1)
 __device__ __forceinline__ float bnn_prior_value(const uint32_t kind, const float u) {
@@ -188,16 +196,21 @@ __device__ __forceinline__ float bnn_prior_value(const uint32_t kind, const floa
     return kind == BSVI_DIST_LAPLACE ? vl : (kind == BSVI_DIST_CAUCHY ? vc : vn);
 }
 
-// the normals of rows 4g .. 4g+3 of sample n: the dense path's definition (dense_eps4), or the caller's
+// the four normals of quad g and sample n: the dense path's definition (dense_eps4)
+__device__ __forceinline__ void bnn_philox_quad(const BParams& Q, uint32_t n, uint32_t g, float e[4]) {
+    const u32x4 x = philox4x32(Q.sample_base + n, g | 0x40000000u, Q.offset_lo, Q.offset_hi, Q.seed_lo, Q.seed_hi);
+    box_muller_fast(x.x, x.y, e[0], e[1]);
+    box_muller_fast(x.z, x.w, e[2], e[3]);
+}
+
+// the normals of rows 4g .. 4g+3 of sample n: that quad, or the caller's
 __device__ __forceinline__ void bnn_eps4(const BParams& Q, uint32_t n, uint32_t g, float e[4]) {
     if (Q.noise_in) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) e[j] = (4u * g + j < Q.R) ? Q.noise_in[(size_t)(4u * g + j) * Q.n_local + n] : 0.0f;
         return;
     }
-    const u32x4 x = philox4x32(Q.sample_base + n, g | 0x40000000u, Q.offset_lo, Q.offset_hi, Q.seed_lo, Q.seed_hi);
-    box_muller_fast(x.x, x.y, e[0], e[1]);
-    box_muller_fast(x.z, x.w, e[2], e[3]);
+    bnn_philox_quad(Q, n, g, e);
 }
 
 // the keyed bijection of the dense path (the fields minibatch_index reads): row of the dataset behind minibatch position i
@@ -225,8 +238,7 @@ __device__ __forceinline__ void bnn_head_body(const BParams& Q, const uint32_t i
         const float sigma = bnn_uniform_value(Q, Q.scale_u + i * Q.scale_stride);
         float* const sg = Q.lab + (size_t)Q.B_pad * Q.LC;
         sg[i] = sigma;
-        if (Q.family == BSVI_DIST_NORMAL) sg[Q.C + i] = -logf(sigma) - 0.91893853320467274178f;
-        else sg[Q.C + i] = -logf(sigma) + bnn_family_const(Q.family);      // -log(2 sigma) | -log(pi sigma)
+        sg[Q.C + i] = -logf(sigma) + bnn_family_const(Q.family);      // -log sigma - 1/2 log 2 pi | -log(2 sigma) | -log(pi sigma)
     }
     for (uint32_t k = i; k < 2u + Q.n_uniform_grad; k += n_threads) Q.partial[k] = 0.0f;
 }
@@ -248,11 +260,8 @@ __device__ __forceinline__ void bnn_gather_body(const BParams& Q, const uint32_t
 // rows, the same counters, key and pairing as bnn_eps4 —, or row R + t of the caller's noise
 __device__ __forceinline__ float bnn_latent_eps(const BParams& Q, const uint32_t n, const uint32_t t) {
     if (Q.noise_in) return Q.noise_in[(size_t)(Q.R + t) * Q.n_local + n];
-    const uint32_t g = (Q.R + 3u) / 4u + (t >> 2);
-    const u32x4 x = philox4x32(Q.sample_base + n, g | 0x40000000u, Q.offset_lo, Q.offset_hi, Q.seed_lo, Q.seed_hi);
     float e[4];
-    box_muller_fast(x.x, x.y, e[0], e[1]);
-    box_muller_fast(x.z, x.w, e[2], e[3]);
+    bnn_philox_quad(Q, n, (Q.R + 3u) / 4u + (t >> 2), e);
     const uint32_t j = t & 3u;
     return j == 0u ? e[0] : (j == 1u ? e[1] : (j == 2u ? e[2] : e[3]));
 }
@@ -441,52 +450,24 @@ __global__ void __launch_bounds__(256) bnn_upper(const BParams Q) {
         // ---- likelihood and d f / d logits (distributions.py:294-311 / 561-592 through torch: log_softmax, BCE with logits)
         const float wgt = live ? Q.lik_weight * (Q.f_weight ? Q.f_weight[n] : 1.0f) : 0.0f, label = Q.lab[(size_t)b * Q.LC];
         float lik = 0.0f;
-        if (Q.likelihood == BSVI_LIK_NORMAL && Q.heads) {
-            // y_c ~ Normal(z_c, a + b g(z_(C + c))): the second half of the last layer is the raw scale, and its delta carries
-            // d f / d sigma through the transform — the reverse sweep takes both halves down like any delta
-            const float* const yb = Q.lab + (size_t)b * Q.LC;
-            const uint32_t Ct = LL.rows / 2u;
-            float s = 0.0f;
-            if (Q.family == BSVI_DIST_NORMAL) {
-                for (uint32_t c = 0; c < Ct; ++c) {
-                    float ds;
-                    const float sigma = bnn_head_sigma(Q.heads, Q.head_a, Q.head_b, Y(LL, Ct + c), ds), u = (yb[c] - Y(LL, c)) / sigma;
-                    s += -0.5f * u * u - logf(sigma) - 0.91893853320467274178f;
-                    Dl(LL, c) = wgt * u / sigma;
-                    Dl(LL, Ct + c) = wgt * (u * u - 1.0f) / sigma * ds;
-                }
-            } else {      // Laplace | Cauchy: the same seeds with the family's value and score (bnn_family_value)
-                const float kf = bnn_family_const(Q.family);
-                for (uint32_t c = 0; c < Ct; ++c) {
-                    float ds, psi;
-                    const float sigma = bnn_head_sigma(Q.heads, Q.head_a, Q.head_b, Y(LL, Ct + c), ds), u = (yb[c] - Y(LL, c)) / sigma;
-                    s += bnn_family_value(Q.family, u, psi) - logf(sigma) + kf;
-                    Dl(LL, c) = wgt * psi / sigma;
-                    Dl(LL, Ct + c) = wgt * (u * psi - 1.0f) / sigma * ds;
-                }
-            }
-            lik = wgt * s;
-        } else if (Q.likelihood == BSVI_LIK_NORMAL) {
-            // y_c ~ Normal(z_c, sigma_c), sigma a constant of the model (distributions.py:137 through torch): the targets of row b,
-            // then sigma and -log sigma - 1/2 log 2 pi per output behind the targets (bnn_head_body)
+        if (Q.likelihood == BSVI_LIK_NORMAL) {
+            // y_c ~ family(z_c, sigma_c) (distributions.py:137 through torch; bnn_loc_scale_term), the targets of row b in lab.  sigma a
+            // constant or a parameter of the model: sigma and -log sigma + the family's constant per output behind the targets
+            // (bnn_head_body).  A scale head, sigma_c = a + b g(z_(C + c)): the second half of the last layer is the raw scale, and its
+            // delta carries d f / d sigma through the transform — the reverse sweep takes both halves down like any delta
             const float* const yb = Q.lab + (size_t)b * Q.LC;
             const float* const sg = Q.lab + (size_t)Q.B_pad * Q.LC;
+            const uint32_t Ct = Q.heads ? LL.rows / 2u : LL.rows;
+            const float kf = bnn_family_const(Q.family);
             float s = 0.0f;
-            if (Q.family == BSVI_DIST_NORMAL) {
-                for (uint32_t c = 0; c < LL.rows; ++c) {
-                    const float sigma = sg[c], u = (yb[c] - Y(LL, c)) / sigma;
-                    s += -0.5f * u * u + sg[LL.rows + c];
-                    Dl(LL, c) = wgt * u / sigma;
-                    if (Q.scale_learn) Q.sigt[((size_t)c * Q.B_pad + b) * Q.n_pad + n] = wgt * (u * u - 1.0f) / sigma;
-                }
-            } else {      // Laplace | Cauchy (bnn_family_value; the family's constant stands behind the targets as the Normal's does)
-                for (uint32_t c = 0; c < LL.rows; ++c) {
-                    float psi;
-                    const float sigma = sg[c], u = (yb[c] - Y(LL, c)) / sigma;
-                    s += bnn_family_value(Q.family, u, psi) + sg[LL.rows + c];
-                    Dl(LL, c) = wgt * psi / sigma;
-                    if (Q.scale_learn) Q.sigt[((size_t)c * Q.B_pad + b) * Q.n_pad + n] = wgt * (u * psi - 1.0f) / sigma;
-                }
+            for (uint32_t c = 0; c < Ct; ++c) {
+                float ds = 0.0f, psi;
+                const float sigma = Q.heads ? bnn_head_sigma(Q.heads, Q.head_a, Q.head_b, Y(LL, Ct + c), ds) : sg[c], u = (yb[c] - Y(LL, c)) / sigma;
+                if (Q.heads) s += bnn_loc_scale_term(Q.family, u, -logf(sigma), psi) + kf;
+                else s += bnn_loc_scale_term(Q.family, u, sg[Ct + c], psi);
+                Dl(LL, c) = wgt * psi / sigma;
+                if (Q.heads) Dl(LL, Ct + c) = wgt * (u * psi - 1.0f) / sigma * ds;
+                else if (Q.scale_learn) Q.sigt[((size_t)c * Q.B_pad + b) * Q.n_pad + n] = wgt * (u * psi - 1.0f) / sigma;
             }
             lik = wgt * s;
         } else if (Q.likelihood == BSVI_LIK_CATEGORICAL) {
@@ -587,29 +568,11 @@ __global__ void __launch_bounds__(256) bnn_small(const BParams Q, const uint32_t
         }
 }
 
-// the likelihood of a sample: wave w adds the minibatch rows w, w + 4, ... (eight loads in flight), the four slices are joined in order.
-// grid: ceil(n_pad / 64), block 256
-__global__ void __launch_bounds__(256) bnn_lik(const BParams Q) {
+// out[n] = sum over the minibatch rows b of t[b][n]: wave w adds the rows w, w + 4, ... (eight loads in flight), the four slices are
+// joined in order.  block 256, lanes along the samples
+__device__ __forceinline__ void bnn_rows_sum(const BParams& Q, const float* const t, float* const out) {
     __shared__ float part[4][64];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, n = blockIdx.x * 64u + lane;
-    float s = 0.0f;
-    for (uint32_t b0 = wave; b0 < Q.B; b0 += 32u) {
-        float v[8];
-#pragma unroll
-        for (uint32_t u = 0; u < 8u; ++u) v[u] = b0 + 4u * u < Q.B ? Q.liknb[(size_t)(b0 + 4u * u) * Q.n_pad + n] : 0.0f;
-        s += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-    }
-    part[wave][lane] = s;
-    __syncthreads();
-    if (wave == 0) Q.lik[n] = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
-}
-
-// a learnable sigma behind the bnn_upper sites: the sum over the minibatch rows of output c's terms, in bnn_lik's order.
-// grid: ceil(n_pad / 64) x C, block 256
-__global__ void __launch_bounds__(256) bnn_sig_rows(const BParams Q) {
-    __shared__ float part[4][64];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, n = blockIdx.x * 64u + lane, c = blockIdx.y;
-    const float* const t = Q.sigt + (size_t)c * Q.B_pad * Q.n_pad;
     float s = 0.0f;
     for (uint32_t b0 = wave; b0 < Q.B; b0 += 32u) {
         float v[8];
@@ -619,7 +582,16 @@ __global__ void __launch_bounds__(256) bnn_sig_rows(const BParams Q) {
     }
     part[wave][lane] = s;
     __syncthreads();
-    if (wave == 0) Q.gsig[(size_t)c * Q.n_pad + n] = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
+    if (wave == 0) out[n] = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
+}
+
+// the likelihood of a sample.  grid: ceil(n_pad / 64), block 256
+__global__ void __launch_bounds__(256) bnn_lik(const BParams Q) { bnn_rows_sum(Q, Q.liknb, Q.lik); }
+
+// a learnable sigma behind the bnn_upper sites: the sum over the minibatch rows of output c's terms, in bnn_lik's order.
+// grid: ceil(n_pad / 64) x C, block 256
+__global__ void __launch_bounds__(256) bnn_sig_rows(const BParams Q) {
+    bnn_rows_sum(Q, Q.sigt + (size_t)blockIdx.y * Q.B_pad * Q.n_pad, Q.gsig + (size_t)blockIdx.y * Q.n_pad);
 }
 
 // one row: gradients with respect to its four uniform entries (the formulas of dense_rows_body) and its sample-independent terms of f
@@ -644,47 +616,33 @@ __device__ __forceinline__ void bnn_row_terms(const BParams& Q, const uint32_t r
     qconst = -log(sd) - 0.91893853320467274178;
 }
 
-// ... of a row whose prior is Laplace or Cauchy: no closed form in sum eps, sum eps^2 — the per-sample sums of bnn_row_sums<true>,
+// ... of a row without that closed form in sum eps, sum eps^2: from the per-sample sums of bnn_row_sums<true>,
 //     T0 = sum_n a_n t_n,  T1 = sum_n a_n eps_n t_n,      t = d log p / d w
-// and T2 = sum_n a_n d log p / d s0 from the two: log p = g(u) - log s0 with u = (w - mu0) / s0 for either family, so
+// and T2 = sum_n a_n d log p / d s0 from the two: log p = g(u) - log s0 with u = (w - mu0) / s0 for every family, so
 // d log p / d s0 = -u t - 1 / s0, and with w - mu0 = (mu - mu0) + s eps:   T2 = -((mu - mu0) T0 + s T1 + N) / s0
-// (the same summands regrouped: no accumulators and no per-sample arithmetic of its own)
-__device__ __forceinline__ void bnn_row_terms_mixed(const BParams& Q, const uint32_t r, const uint32_t kind, const float ds_lik, const float dmu_lik,
-                                                    const float T0, const float T1, const float N, double& hconst, double& qconst) {
+// (the same summands regrouped: no accumulators and no per-sample arithmetic of its own).
+// Such rows are those whose prior is Laplace or Cauchy, and every row under a latent prior scale (bnn_row_sums<true, true>), the Normal
+// ones too: the prior scale is then b_r tau_(t, n), so T0 and T1 carry 1 / (b_r tau) inside the sum, and the row's prior scale entry holds
+// b_r — log p = g(u) - log b_r - l with u = (w - mu0) / (b_r tau), d log p / d b_r = -(w - mu0) t / b_r - 1 / b_r: T2's identity with b_r in
+// the place of s0, and -log b_r in the constant where -log s0 stands; the per-sample -l is the latent's (bnn_latent_terms)
+__device__ __forceinline__ void bnn_row_terms_sums(const BParams& Q, const uint32_t r, const uint32_t kind, const float ds_lik, const float dmu_lik,
+                                                   const float T0, const float T1, const float N, double& hconst, double& qconst) {
     const float mu = Q.rowp[r], s = Q.rowp[Q.R + r], mu0 = Q.rowp[2 * (size_t)Q.R + r], s0 = Q.rowp[3 * (size_t)Q.R + r];
     const float T2 = -((mu - mu0) * T0 + s * T1 + N) / s0;
     Q.rowg[r] = dmu_lik + Q.prior_weight * T0;
     Q.rowg[Q.R + r] = ds_lik + Q.prior_weight * T1 + Q.entropy_weight * N / s;
     Q.rowg[2 * (size_t)Q.R + r] = -Q.prior_weight * T0;
     Q.rowg[3 * (size_t)Q.R + r] = Q.prior_weight * T2;
-    // (double precision, for bnn_row_terms' reason)  Laplace: -log(2 s0); Cauchy: -log(pi) - log(s0)
+    // (double precision, for bnn_row_terms' reason)  Laplace: -log(2 s0); Cauchy: -log(pi) - log(s0); Normal: -log(s0) - 1/2 log 2 pi
     const double sd = bnn_uniform_value_d(Q, Q.row_uniform[Q.R + r]), s0d = bnn_uniform_value_d(Q, Q.row_uniform[3 * (size_t)Q.R + r]);
-    const double pconst = kind == BSVI_DIST_LAPLACE ? -log(2.0 * s0d) : -1.14472988584940017414 - log(s0d);
-    hconst = (double)Q.prior_weight * pconst + (double)Q.entropy_weight * (1.41893853320467274178 + log(sd));
-    qconst = -log(sd) - 0.91893853320467274178;
-}
-
-// ... of a row under a latent prior scale (bnn_row_sums<true, true>): its prior scale is b_r tau_(t, n), so T0 and T1 carry 1 / (b_r tau)
-// inside the sum for all three kinds, and the row's prior scale entry holds b_r: log p = g(u) - log b_r - l with u = (w - mu0) / (b_r tau), so
-// d log p / d b_r = -(w - mu0) t / b_r - 1 / b_r, summed -((mu - mu0) T0 + s T1 + N) / b_r — T2's identity with b_r in the place of s0 —, and -log b_r stands in
-// the constant where -log s0 does; the per-sample -l is the latent's (bnn_latent_terms)
-__device__ __forceinline__ void bnn_row_terms_latent(const BParams& Q, const uint32_t r, const uint32_t kind, const float ds_lik, const float dmu_lik,
-                                                     const float T0, const float T1, const float N, double& hconst, double& qconst) {
-    const float mu = Q.rowp[r], s = Q.rowp[Q.R + r], mu0 = Q.rowp[2 * (size_t)Q.R + r], b = Q.rowp[3 * (size_t)Q.R + r];
-    const float T2 = -((mu - mu0) * T0 + s * T1 + N) / b;
-    Q.rowg[r] = dmu_lik + Q.prior_weight * T0;
-    Q.rowg[Q.R + r] = ds_lik + Q.prior_weight * T1 + Q.entropy_weight * N / s;
-    Q.rowg[2 * (size_t)Q.R + r] = -Q.prior_weight * T0;
-    Q.rowg[3 * (size_t)Q.R + r] = Q.prior_weight * T2;
-    const double sd = bnn_uniform_value_d(Q, Q.row_uniform[Q.R + r]), bd = bnn_uniform_value_d(Q, Q.row_uniform[3 * (size_t)Q.R + r]);
-    const double pconst = kind == BSVI_DIST_LAPLACE ? -log(2.0 * bd) : (kind == BSVI_DIST_CAUCHY ? -1.14472988584940017414 - log(bd) : -log(bd) - 0.91893853320467274178);
+    const double pconst = kind == BSVI_DIST_LAPLACE ? -log(2.0 * s0d) : (kind == BSVI_DIST_CAUCHY ? -1.14472988584940017414 - log(s0d) : -log(s0d) - 0.91893853320467274178);
     hconst = (double)Q.prior_weight * pconst + (double)Q.entropy_weight * (1.41893853320467274178 + log(sd));
     qconst = -log(sd) - 0.91893853320467274178;
 }
 
 // per row quad (one wave, lanes = samples): sum_n eps G, sum_n G, sum_n eps, sum_n eps^2, then the rows' gradients and constants.  grid: ceil(quads / 4), block 256: a wave per quad
 // (round 6: four quads per workgroup, as bnn_draw)
-// MIXED: eight more accumulators, T0 and T1 of bnn_row_terms_mixed for each of the four rows, from w and u recomputed as bnn_draw
+// MIXED: eight more accumulators, T0 and T1 of bnn_row_terms_sums for each of the four rows, from w and u recomputed as bnn_draw
 // computed them on the eps redrawn here anyway — no pass over memory of their own, the same wave_sum order; a Normal row of such a model
 // keeps its closed form.  MIXED = false is the kernel of the all-Normal models as it was.
 // LATENT (with MIXED; bsvi_bnn_set_scale_latents): a row under a latent has the prior scale b_r tau_(t, n), another one per sample, so all
@@ -790,8 +748,8 @@ __global__ void __launch_bounds__(256) bnn_row_sums(const BParams Q) {
             for (int j = 0; j < 4; ++j) { T0 = (lane == (uint32_t)j) ? tacc[j] : T0; T1 = (lane == (uint32_t)j) ? tacc[4 + j] : T1; }
             kind = (kinds >> (8u * lane)) & 0xFFu;
         }
-        if (LATENT && ((lats >> (8u * lane)) & 0xFFu) != 0xFFu) bnn_row_terms_latent(Q, r, kind, ds_lik, dmu_lik, T0, T1, Nw, hconst, qconst);
-        else if (MIXED && kind != BSVI_DIST_NORMAL) bnn_row_terms_mixed(Q, r, kind, ds_lik, dmu_lik, T0, T1, Nw, hconst, qconst);
+        const bool under_latent = LATENT && ((lats >> (8u * lane)) & 0xFFu) != 0xFFu;
+        if (under_latent || (MIXED && kind != BSVI_DIST_NORMAL)) bnn_row_terms_sums(Q, r, kind, ds_lik, dmu_lik, T0, T1, Nw, hconst, qconst);
         else bnn_row_terms(Q, r, ds_lik, dmu_lik, S1, S2, Nw, hconst, qconst);
     }
     double h4 = 0.0, q4 = 0.0;
@@ -952,6 +910,9 @@ __global__ void __launch_bounds__(256) bnn_uniform_grads(const BParams Q) {
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
+// a generated kernel of a handle; state: 0 not tried, 1 ready, -1 declined / failed (what stands behind it serves)
+struct BnnGen { int state = 0; hipModule_t module = nullptr; hipFunction_t fn = nullptr; };
+
 struct bsvi_bnn {
     bsvi_bnn_desc d;
     std::vector<bsvi_bnn_layer> layers;
@@ -980,18 +941,14 @@ struct bsvi_bnn {
     uint32_t act_off[BNN_MAX_LAYERS] = {};
     bool exact = false;
     bool upper_lds = false;      // the small tensors of 64 samples fit LDS ([Rs][65] floats): bnn_upper<true>
-    // bnn_upper specialised to THIS network (round 5, bnn_upper_source below): compiled with hiprtc at the first launch
+    // the two kernels written for THIS network (round 5; their text: bnn_source.h), compiled with hiprtc at the first launch:
+    // bnn_upper specialised, and the exact-data path's middle as one kernel (bnn_gen_ready)
     mutable std::mutex jit_mu;
-    mutable int jit_state = 0;   // 0 not tried, 1 ready, -1 declined / failed (bnn_upper serves)
-    mutable hipModule_t jit_module = nullptr;
-    mutable hipFunction_t jit_fn = nullptr;
-    mutable int mid_state = 0;   // the exact-data path's middle as one generated kernel (bnn_mid_source): same states
-    mutable hipModule_t mid_module = nullptr;
-    mutable hipFunction_t mid_fn = nullptr;
+    mutable BnnGen upper_gen, mid_gen;
     uint32_t n_cu = 256;
 };
 
-// what the generated kernel reads of an iteration (bnn_upper_source declares the same struct)
+// what bnn_upper_gen reads of an iteration (bnn_source.h's upper_source declares the same struct)
 struct BnnUpperArgs {
     const float* Wsm; const float* a1T; const float* lab; float* acts; float* deltas; float* liknb; float* da1T; uint16_t* dlogp;
     uint32_t n_local, n_pad, B, B_pad, NC, rows_per_wave, exact;
@@ -1001,436 +958,27 @@ struct BnnUpperArgs {
 // ... of a network with a learnable sigma: the same fields, then where its terms go (the generated struct gains the same last member)
 struct BnnUpperArgsSig { BnnUpperArgs a; float* sigt; };
 
-// the Normal likelihood of the two generated kernels (the text bnn_upper runs with loop bounds): targets [B_pad][C] in A.lab, then
-// sigma [C] and -log sigma - 1/2 log 2 pi [C] as bnn_head_body leaves them — the values of the uniform table, never a host copy
-// sig_terms (bnn_upper_gen with a learnable sigma): wgt (u^2 - 1) / sigma per (c, b, n) leaves for bnn_sig_rows
-// the Laplace and Cauchy likelihoods of the generated kernels as text (bnn_family_value with the family a literal): what stands
-// between u and the sum, the value without its constant, and u psi(u)
-struct BnnFamilyText { const char* psi; const char* value; const char* upsi; };
-static BnnFamilyText bnn_family_text(uint32_t family) {
-    if (family == BSVI_DIST_LAPLACE) return {"const float psi = u > 0.0f ? 1.0f : (u < 0.0f ? -1.0f : 0.0f);", "-fabsf(u)", "fabsf(u)"};
-    // BSVI_BNN_CAUCHY_LOG=log1p: the library's log1pf in the place of the hardware logarithm (tools/bnn_likelihoods_timing.py measures both)
-    const char* e = getenv("BSVI_BNN_CAUCHY_LOG");
-    const bool lib = e && !strcmp(e, "log1p");
-    return {lib ? "const float uu = u * u, q = 1.0f + uu, psi = 2.0f * u / q;" : "const float q = 1.0f + u * u, psi = 2.0f * u / q;",
-            lib ? "-log1pf(uu)" : "-__logf(q)", "u * psi"};
-}
-
-static std::string bnn_normal_source(uint32_t C, uint32_t yl, bool sig_terms = false, uint32_t family = BSVI_DIST_NORMAL) {
-    char buf[1536];
-    if (family != BSVI_DIST_NORMAL) {
-        const BnnFamilyText t = bnn_family_text(family);
-        char sig[256];
-        snprintf(sig, sizeof sig, "                A.sigt[((size_t)c * A.B_pad + b) * A.n_pad + n] = wgt * (%s - 1.0f) / sigma;\n", t.upsi);
-        snprintf(buf, sizeof buf,
-                 "        {\n"
-                 "            const float* const yb = A.lab + (size_t)b * %uu;\n"
-                 "            const float* const sg = A.lab + (size_t)A.B_pad * %uu;\n"
-                 "            float sn = 0.0f;\n"
-                 "#pragma unroll\n"
-                 "            for (uint32_t c = 0; c < %uu; ++c) {\n"
-                 "                const float sigma = sg[c], u = (yb[c] - y[%uu + c]) / sigma;\n"
-                 "                %s\n"
-                 "                sn += %s + sg[%uu + c];\n"
-                 "                d[%uu + c] = wgt * psi / sigma;\n"
-                 "%s"
-                 "            }\n"
-                 "            lik = wgt * sn;\n"
-                 "        }\n", C, C, C, yl, t.psi, t.value, C, yl, sig_terms ? sig : "");
-        return std::string(buf);
-    }
-    snprintf(buf, sizeof buf,
-             "        {\n"
-             "            const float* const yb = A.lab + (size_t)b * %uu;\n"
-             "            const float* const sg = A.lab + (size_t)A.B_pad * %uu;\n"
-             "            float sn = 0.0f;\n"
-             "#pragma unroll\n"
-             "            for (uint32_t c = 0; c < %uu; ++c) {\n"
-             "                const float sigma = sg[c], u = (yb[c] - y[%uu + c]) / sigma;\n"
-             "                sn += -0.5f * u * u + sg[%uu + c];\n"
-             "                d[%uu + c] = wgt * u / sigma;\n"
-             "%s"
-             "            }\n"
-             "            lik = wgt * sn;\n"
-             "        }\n", C, C, C, yl, C, yl,
-             sig_terms ? "                A.sigt[((size_t)c * A.B_pad + b) * A.n_pad + n] = wgt * (u * u - 1.0f) / sigma;\n" : "");
-    return std::string(buf);
-}
-
-// ... of a network with a scale head (bsvi_bnn_create_normal_heads): y[yl + c] the loc, y[yl + C + c] the raw scale, the transform and its
-// two constants as literals (their bits: no decimal round trip); the text bnn_upper runs through bnn_head_sigma
-static std::string bnn_heads_source(const bsvi_bnn* p, uint32_t yl) {
-    uint32_t abits, bbits;
-    memcpy(&abits, &p->head_a, 4); memcpy(&bbits, &p->head_b, 4);
-    const char* g = p->heads == BSVI_UT_EXP ? "const float g = expf(raw), dg = g;"
-                  : p->heads == BSVI_UT_SIGMOID ? "const float g = sigmoidf_(raw), dg = g * (1.0f - g);"
-                  : "const float g = raw > 20.0f ? raw : log1pf(expf(raw)), dg = raw > 20.0f ? 1.0f : sigmoidf_(raw);";
-    char buf[1792];
-    if (p->family != BSVI_DIST_NORMAL) {
-        const BnnFamilyText t = bnn_family_text(p->family);
-        snprintf(buf, sizeof buf,
-                 "        {\n"
-                 "            const float* const yb = A.lab + (size_t)b * %uu;\n"
-                 "            const float ha = __uint_as_float(0x%08xu), hb = __uint_as_float(0x%08xu);\n"
-                 "            float sn = 0.0f;\n"
-                 "#pragma unroll\n"
-                 "            for (uint32_t c = 0; c < %uu; ++c) {\n"
-                 "                const float raw = y[%uu + c];\n"
-                 "                %s\n"
-                 "                const float sigma = ha + hb * g, u = (yb[c] - y[%uu + c]) / sigma;\n"
-                 "                %s\n"
-                 "                sn += %s - logf(sigma) + %s;\n"
-                 "                d[%uu + c] = wgt * psi / sigma;\n"
-                 "                d[%uu + c] = wgt * (%s - 1.0f) / sigma * (hb * dg);\n"
-                 "            }\n"
-                 "            lik = wgt * sn;\n"
-                 "        }\n", p->C, abits, bbits, p->C, yl + p->C, g, yl, t.psi, t.value,
-                 p->family == BSVI_DIST_LAPLACE ? "-0.69314718055994530942f" : "-1.14472988584940017414f", yl, yl + p->C, t.upsi);
-        return std::string(buf);
-    }
-    snprintf(buf, sizeof buf,
-             "        {\n"
-             "            const float* const yb = A.lab + (size_t)b * %uu;\n"
-             "            const float ha = __uint_as_float(0x%08xu), hb = __uint_as_float(0x%08xu);\n"
-             "            float sn = 0.0f;\n"
-             "#pragma unroll\n"
-             "            for (uint32_t c = 0; c < %uu; ++c) {\n"
-             "                const float raw = y[%uu + c];\n"
-             "                %s\n"
-             "                const float sigma = ha + hb * g, u = (yb[c] - y[%uu + c]) / sigma;\n"
-             "                sn += -0.5f * u * u - logf(sigma) - 0.91893853320467274178f;\n"
-             "                d[%uu + c] = wgt * u / sigma;\n"
-             "                d[%uu + c] = wgt * (u * u - 1.0f) / sigma * (hb * dg);\n"
-             "            }\n"
-             "            lik = wgt * sn;\n"
-             "        }\n", p->C, abits, bbits, p->C, yl + p->C, g, yl, yl, yl + p->C);
-    return std::string(buf);
-}
-
-// ---- bnn_upper as generated source.  The generic kernel above walks the network with run-time loop bounds: every weight of the
-// sample's small tensors and every activation is an LDS read in front of the FMA that needs it (~2 200 of them per (sample, row) of
-// the 784-20-10 network), from ONE wave per SIMD: 434 of the 941 us of an iteration at config 4's scale.  A model is compiled once and
-// iterated thousands of times, so — as specialize.cpp does for the scalar programs — the library writes the kernel for THIS network:
-// layer sizes, offsets and activations as literals, every loop unrolled, the sample's small tensors (230 floats for 784-20-10) and the
-// activations in REGISTERS (staged through LDS once per workgroup, transposed, as before).  Same arithmetic in the same order.
-static std::string bnn_upper_source(const bsvi_bnn* p) {
-    auto fmt = [](const char* f, ...) { char buf[512]; va_list ap; va_start(ap, f); vsnprintf(buf, sizeof buf, f, ap); va_end(ap); return std::string(buf); };
-    const uint32_t NL = p->d.n_layers, RS = p->Rs ? p->Rs : 1, R1 = p->R1, AW = (uint32_t)p->act_floats;
-    auto act = [&](uint32_t a, const std::string& v) {
-        switch (a) {
-        case BSVI_BNN_ACT_TANH: return "tanhf(" + v + ")";
-        case BSVI_BNN_ACT_RELU: return "fmaxf(" + v + ", 0.0f)";
-        case BSVI_BNN_ACT_SIGMOID: return "sigmoidf_(" + v + ")";
-        case BSVI_BNN_ACT_SOFTPLUS: return "((" + v + ") > 20.0f ? (" + v + ") : log1pf(expf(" + v + ")))";
-        default: return v;
-        }
-    };
-    auto act_grad = [&](uint32_t a, const std::string& y) {      // through the OUTPUT of the activation
-        switch (a) {
-        case BSVI_BNN_ACT_TANH: return "(1.0f - " + y + " * " + y + ")";
-        case BSVI_BNN_ACT_RELU: return "(" + y + " > 0.0f ? 1.0f : 0.0f)";
-        case BSVI_BNN_ACT_SIGMOID: return "(" + y + " * (1.0f - " + y + "))";
-        case BSVI_BNN_ACT_SOFTPLUS: return "(" + y + " > 20.0f ? 1.0f : -expm1f(-" + y + "))";
-        default: return std::string("1.0f");
-        }
-    };
-    std::string s;
-    s += "// generated by libbsvi (bnn_kernel.inc) for one Bayesian neural network: do not edit\n";
-    s += "#include \"bsvi_device.h\"\nusing namespace bsvi;\n";
-    s += "struct BnnUpperArgs { const float* Wsm; const float* a1T; const float* lab; float* acts; float* deltas; float* liknb; float* da1T; uint16_t* dlogp;\n"
-         "    uint32_t n_local, n_pad, B, B_pad, NC, rows_per_wave, exact; float lik_weight; const float* f_weight;";
-    s += p->scale_learn ? " float* sigt; };\n" : " };\n";
-    s += "__device__ __forceinline__ uint16_t gen_bf16(float x) { const uint32_t u = __float_as_uint(x); return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16); }\n";
-    s += fmt("#define RS %uu\n#define AW %uu\n", RS, AW);
-    s += "extern \"C\" __global__ void __launch_bounds__(256) bnn_upper_gen(const BnnUpperArgs A) {\n"
-         "    extern __shared__ float wl[];                       // [RS][65]: the small tensors of the workgroup's 64 samples, transposed\n"
-         "    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, n = blockIdx.x * 64u + lane;\n"
-         "    for (uint32_t i = threadIdx.x; i < 64u * RS; i += 256u) {\n"
-         "        const uint32_t sn = i / RS, r = i - sn * RS;\n"
-         "        wl[r * 65u + sn] = A.Wsm[(size_t)(blockIdx.x * 64u + sn) * RS + r];\n"
-         "    }\n"
-         "    __syncthreads();\n"
-         "    float w[RS];\n"
-         "#pragma unroll\n"
-         "    for (uint32_t r = 0; r < RS; ++r) w[r] = wl[r * 65u + lane];\n"
-         "    for (uint32_t bi = 0; bi < A.rows_per_wave; ++bi) {\n"
-         "        const uint32_t b = (blockIdx.y * 4u + wave) * A.rows_per_wave + bi;\n"
-         "        if (b >= A.B_pad) break;\n"
-         "        const bool live = n < A.n_local && b < A.B;\n"
-         "        float y[AW], d[AW];\n";
-    // forward
-    const bsvi_bnn_layer& L0 = p->layers[0];
-    s += "#pragma unroll\n";
-    s += fmt("        for (uint32_t h = 0; h < %uu; ++h) {\n            float v = A.a1T[(size_t)b * A.NC + (size_t)h * A.n_pad + n];\n", L0.rows);
-    if (L0.bias_row0 != 0xFFFFFFFFu) s += fmt("            v += w[%uu + h];\n", L0.bias_row0 - R1);
-    s += "            y[" + fmt("%uu", p->act_off[0]) + " + h] = " + act(L0.activation, "v") + ";\n        }\n";
-    for (uint32_t l = 1; l < NL; ++l) {
-        const bsvi_bnn_layer& L = p->layers[l];
-        s += "#pragma unroll\n";
-        s += fmt("        for (uint32_t i = 0; i < %uu; ++i) {\n", L.rows);
-        s += L.bias_row0 != 0xFFFFFFFFu ? fmt("            float sm = w[%uu + i];\n", L.bias_row0 - R1) : std::string("            float sm = 0.0f;\n");
-        s += "#pragma unroll\n";
-        s += fmt("            for (uint32_t j = 0; j < %uu; ++j) sm += w[%uu + i * %uu + j] * y[%uu + j];\n", L.cols, L.weight_row0 - R1, L.cols, p->act_off[l - 1]);
-        s += "            y[" + fmt("%uu", p->act_off[l]) + " + i] = " + act(L.activation, "sm") + ";\n        }\n";
-    }
-    // likelihood
-    const bsvi_bnn_layer& LL = p->layers[NL - 1];
-    const uint32_t yl = p->act_off[NL - 1];
-    s += std::string("        const float wgt = live ? A.lik_weight * (A.f_weight ? A.f_weight[n] : 1.0f) : 0.0f") +
-         (p->d.likelihood == BSVI_LIK_NORMAL ? ";\n" : ", label = A.lab[b];\n") + "        float lik = 0.0f;\n";
-    if (p->d.likelihood == BSVI_LIK_NORMAL) {
-        s += p->heads ? bnn_heads_source(p, yl) : bnn_normal_source(LL.rows, yl, p->scale_learn, p->family);
-    } else if (p->d.likelihood == BSVI_LIK_CATEGORICAL) {
-        s += "        {\n            float m = -INFINITY;\n#pragma unroll\n";
-        s += fmt("            for (uint32_t c = 0; c < %uu; ++c) m = fmaxf(m, y[%uu + c]);\n", LL.rows, yl);
-        s += "            float se = 0.0f, zl = 0.0f;\n#pragma unroll\n";
-        s += fmt("            for (uint32_t c = 0; c < %uu; ++c) { const float z = y[%uu + c]; se += expf(z - m); if (label == (float)c) zl = z; }\n", LL.rows, yl);
-        s += "            const float lse = m + logf(se);\n            lik = wgt * (zl - lse);\n#pragma unroll\n";
-        s += fmt("            for (uint32_t c = 0; c < %uu; ++c) d[%uu + c] = wgt * ((label == (float)c ? 1.0f : 0.0f) - expf(y[%uu + c] - lse));\n        }\n", LL.rows, yl, yl);
-    } else {
-        s += fmt("        {\n            const float z = y[%uu];\n            lik = wgt * (label * z - (fmaxf(z, 0.0f) + log1pf(expf(-fabsf(z)))));\n            d[%uu] = wgt * (label - sigmoidf_(z));\n        }\n", yl, yl);
-    }
-    s += "        A.liknb[(size_t)b * A.n_pad + n] = lik;\n";
-    // reverse sweep
-    for (uint32_t l = NL - 1; l >= 1; --l) {
-        const bsvi_bnn_layer& L = p->layers[l];
-        const bsvi_bnn_layer& Lp = p->layers[l - 1];
-        s += "#pragma unroll\n";
-        s += fmt("        for (uint32_t j = 0; j < %uu; ++j) {\n            float sm = 0.0f;\n#pragma unroll\n", L.cols);
-        s += fmt("            for (uint32_t i = 0; i < %uu; ++i) sm += w[%uu + i * %uu + j] * d[%uu + i];\n", L.rows, L.weight_row0 - R1, L.cols, p->act_off[l]);
-        s += "            d[" + fmt("%uu", p->act_off[l - 1]) + " + j] = sm * " + act_grad(Lp.activation, "y[" + fmt("%uu", p->act_off[l - 1]) + " + j]") + ";\n        }\n";
-    }
-    // what bnn_small reads
-    for (uint32_t l = 0; l < NL; ++l) {
-        const bsvi_bnn_layer& L = p->layers[l];
-        s += "#pragma unroll\n";
-        s += fmt("        for (uint32_t u = 0; u < %uu; ++u) {\n            const size_t at = ((size_t)(%uu + u) * A.B_pad + b) * A.n_pad + n;\n", L.rows, p->act_off[l]);
-        if (l + 1 < NL) s += fmt("            A.acts[at] = y[%uu + u];\n", p->act_off[l]);
-        s += fmt("            A.deltas[at] = d[%uu + u];\n        }\n", p->act_off[l]);
-    }
-    // d f / d a1 as the operand of the second product, [(h, n)][b]
-    s += "#pragma unroll\n";
-    s += fmt("        for (uint32_t h = 0; h < %uu; ++h) {\n", L0.rows);
-    s += "            const size_t at = ((size_t)h * A.n_pad + n) * A.B_pad + b;\n";
-    s += fmt("            const float g = live ? d[%uu + h] : 0.0f;\n", p->act_off[0]);
-    s += "            if (A.exact) {\n"
-         "                const uint16_t hi = gen_bf16(g);\n"
-         "                const float r1 = g - __uint_as_float((uint32_t)hi << 16);\n"
-         "                const uint16_t mid = gen_bf16(r1);\n"
-         "                const uint16_t lo = gen_bf16(r1 - __uint_as_float((uint32_t)mid << 16));\n"
-         "                const size_t plane = (size_t)A.NC * A.B_pad;\n"
-         "                A.dlogp[at] = hi; A.dlogp[plane + at] = mid; A.dlogp[2 * plane + at] = lo;\n"
-         "            } else {\n"
-         "                A.da1T[at] = g;\n"
-         "            }\n"
-         "        }\n"
-         "    }\n"
-         "}\n";
-    return s;
-}
-
-// ---- the exact-data path's middle as ONE generated kernel, lanes along the MINIBATCH ROWS (round 5).  With lanes along the samples
-// (bnn_upper, bnn_upper_gen) the operand of the second product — d f / d a1 as bf16 pieces [(h, n)][b] — leaves as 2-byte stores a
-// kilobyte apart, 60 per (sample, row): most of what those kernels take.  Here a workgroup owns ONE sample: product 1 delivers a1
-// transposed, [(h, n)][b] (bsvi_xgemm_nt_t), so loads and piece stores are contiguous along b; the sample's small tensors are 230
-// floats of LDS read as broadcasts; activations and deltas of the sample's rows stay in an LDS tile [unit][b], from which the same
-// workgroup then takes the gradients of the small tensors (one thread per element, rows in order: bnn_small's job) and the sample's
-// likelihood — acts / deltas / liknb never reach memory, bnn_small and bnn_lik are not launched.
+// ... and of bnn_mid_gen (bnn_source.h's mid_source declares the same struct; a learnable sigma: its per-sample sums [C][n_pad])
 struct BnnMidArgs {
     const float* Wsm; const float* a1; const float* lab; float* gsm; float* lik; uint16_t* dlogp;
     uint32_t n_local, n_pad, B, B_pad, NC;
     float lik_weight;
     const float* f_weight;      // a_n per sample, or null
 };
-struct BnnMidArgsSig { BnnMidArgs a; float* gsig; };      // a learnable sigma: its per-sample sums [C][n_pad] (as BnnUpperArgsSig)
-static std::string bnn_mid_source(const bsvi_bnn* p) {
-    auto fmt = [](const char* f, ...) { char buf[512]; va_list ap; va_start(ap, f); vsnprintf(buf, sizeof buf, f, ap); va_end(ap); return std::string(buf); };
-    const uint32_t NL = p->d.n_layers, RS = p->Rs ? p->Rs : 1, R1 = p->R1, AW = (uint32_t)p->act_floats;
-    auto act = [&](uint32_t a, const std::string& v) {
-        switch (a) {
-        case BSVI_BNN_ACT_TANH: return "tanhf(" + v + ")";
-        case BSVI_BNN_ACT_RELU: return "fmaxf(" + v + ", 0.0f)";
-        case BSVI_BNN_ACT_SIGMOID: return "sigmoidf_(" + v + ")";
-        case BSVI_BNN_ACT_SOFTPLUS: return "((" + v + ") > 20.0f ? (" + v + ") : log1pf(expf(" + v + ")))";
-        default: return v;
-        }
-    };
-    auto act_grad = [&](uint32_t a, const std::string& y) {
-        switch (a) {
-        case BSVI_BNN_ACT_TANH: return "(1.0f - " + y + " * " + y + ")";
-        case BSVI_BNN_ACT_RELU: return "(" + y + " > 0.0f ? 1.0f : 0.0f)";
-        case BSVI_BNN_ACT_SIGMOID: return "(" + y + " * (1.0f - " + y + "))";
-        case BSVI_BNN_ACT_SOFTPLUS: return "(" + y + " > 20.0f ? 1.0f : -expm1f(-" + y + "))";
-        default: return std::string("1.0f");
-        }
-    };
-    // element r of the small tensors -> (unit of its delta row, unit of its input row in the tile, or "one" for a bias); the tile holds
-    // the activations y at units [0, AW) and the deltas d at [AW, 2 AW)
-    std::vector<uint32_t> du(RS, 0u), yu(RS, 0xFFFFu);
-    for (uint32_t l = 0; l < NL; ++l) {
-        const bsvi_bnn_layer& L = p->layers[l];
-        if (L.bias_row0 != 0xFFFFFFFFu)
-            for (uint32_t i = 0; i < L.rows; ++i) du[L.bias_row0 - R1 + i] = AW + p->act_off[l] + i;
-        if (l == 0) continue;
-        for (uint32_t i = 0; i < L.rows; ++i)
-            for (uint32_t j = 0; j < L.cols; ++j) {
-                du[L.weight_row0 - R1 + i * L.cols + j] = AW + p->act_off[l] + i;
-                yu[L.weight_row0 - R1 + i * L.cols + j] = p->act_off[l - 1] + j;
-            }
-    }
-    std::string s;
-    s += "// generated by libbsvi (bnn_kernel.inc) for one Bayesian neural network: do not edit\n";
-    s += "#include \"bsvi_device.h\"\nusing namespace bsvi;\n";
-    s += "struct BnnMidArgs { const float* Wsm; const float* a1; const float* lab; float* gsm; float* lik; uint16_t* dlogp;\n"
-         "    uint32_t n_local, n_pad, B, B_pad, NC; float lik_weight; const float* f_weight;";
-    s += p->scale_learn ? " float* gsig; };\n" : " };\n";
-    s += "typedef float gen_f4 __attribute__((ext_vector_type(4)));\n";
-    s += "__device__ __forceinline__ uint16_t gen_bf16(float x) { const uint32_t u = __float_as_uint(x); return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16); }\n";
-    s += fmt("#define RS %uu\n#define RSP %uu\n#define AW %uu\n", RS, (RS + 3u) / 4u * 4u, AW);
-    s += "__device__ const unsigned short GEN_DU[RS] = {";
-    for (uint32_t r = 0; r < RS; ++r) s += fmt("%u%s", du[r], r + 1 < RS ? "," : "");
-    s += "};\n__device__ const unsigned short GEN_YU[RS] = {";
-    for (uint32_t r = 0; r < RS; ++r) s += fmt("%u%s", yu[r], r + 1 < RS ? "," : "");
-    s += "};\n";
-    s += "extern \"C\" __global__ void __launch_bounds__(256) bnn_mid_gen(const BnnMidArgs A) {\n"
-         "    extern __shared__ __attribute__((aligned(16))) float lds[];      // small tensors [RSP] | tile [2 AW][BS]: y, then d, of every row b\n"
-         "    __shared__ float red[4];\n"
-         "    const uint32_t tid = threadIdx.x, n = blockIdx.x, BS = A.B_pad + 4u;\n"
-         "    float* const wl = lds;\n"
-         "    float* const T = lds + RSP;\n"
-         "    for (uint32_t r = tid; r < RS; r += 256u) wl[r] = A.Wsm[(size_t)n * RS + r];\n"
-         "    __syncthreads();\n"
-         "    float lik_acc = 0.0f;\n";
-    // (round 6: with 512 and more rows a thread takes PAIRS of neighbouring rows, so that the pieces of d f / d a1 leave as 4-byte
-    //  stores — 106 -> 97 us at config 4's scale; the example's 32 rows keep one row per thread: half the threads would do twice the work)
-    const bool pairs = p->B_pad >= 512u;
-    if (pairs)
-        s += "    for (uint32_t b2 = tid; b2 < A.B_pad / 2u; b2 += 256u) {\n"
-             "      uint32_t pk[3][" + fmt("%u", p->layers[0].rows) + "];\n"
-             "#pragma unroll\n"
-             "      for (uint32_t bb = 0; bb < 2u; ++bb) {\n"
-             "        const uint32_t b = 2u * b2 + bb;\n";
-    else
-        s += "    for (uint32_t b = tid; b < A.B_pad; b += 256u) {\n"
-             "      {\n";
-    s += "        const bool live = n < A.n_local && b < A.B;\n"
-         "        float y[AW], d[AW];\n";
-    const bsvi_bnn_layer& L0 = p->layers[0];
-    s += "#pragma unroll\n";
-    s += fmt("        for (uint32_t h = 0; h < %uu; ++h) {\n            float v = A.a1[((size_t)h * A.n_pad + n) * A.B_pad + b];\n", L0.rows);
-    if (L0.bias_row0 != 0xFFFFFFFFu) s += fmt("            v += wl[%uu + h];\n", L0.bias_row0 - R1);
-    s += "            y[" + fmt("%uu", p->act_off[0]) + " + h] = " + act(L0.activation, "v") + ";\n        }\n";
-    for (uint32_t l = 1; l < NL; ++l) {
-        const bsvi_bnn_layer& L = p->layers[l];
-        s += "#pragma unroll\n";
-        s += fmt("        for (uint32_t i = 0; i < %uu; ++i) {\n", L.rows);
-        s += L.bias_row0 != 0xFFFFFFFFu ? fmt("            float sm = wl[%uu + i];\n", L.bias_row0 - R1) : std::string("            float sm = 0.0f;\n");
-        s += "#pragma unroll\n";
-        s += fmt("            for (uint32_t j = 0; j < %uu; ++j) sm += wl[%uu + i * %uu + j] * y[%uu + j];\n", L.cols, L.weight_row0 - R1, L.cols, p->act_off[l - 1]);
-        s += "            y[" + fmt("%uu", p->act_off[l]) + " + i] = " + act(L.activation, "sm") + ";\n        }\n";
-    }
-    const bsvi_bnn_layer& LL = p->layers[NL - 1];
-    const uint32_t yl = p->act_off[NL - 1];
-    s += std::string("        const float wgt = live ? A.lik_weight * (A.f_weight ? A.f_weight[n] : 1.0f) : 0.0f") +
-         (p->d.likelihood == BSVI_LIK_NORMAL ? ";\n" : ", label = A.lab[b];\n") + "        float lik = 0.0f;\n";
-    if (p->d.likelihood == BSVI_LIK_NORMAL) {
-        s += p->heads ? bnn_heads_source(p, yl) : bnn_normal_source(LL.rows, yl, false, p->family);
-    } else if (p->d.likelihood == BSVI_LIK_CATEGORICAL) {
-        s += "        {\n            float m = -INFINITY;\n#pragma unroll\n";
-        s += fmt("            for (uint32_t c = 0; c < %uu; ++c) m = fmaxf(m, y[%uu + c]);\n", LL.rows, yl);
-        s += "            float se = 0.0f, zl = 0.0f;\n#pragma unroll\n";
-        s += fmt("            for (uint32_t c = 0; c < %uu; ++c) { const float z = y[%uu + c]; se += expf(z - m); if (label == (float)c) zl = z; }\n", LL.rows, yl);
-        s += "            const float lse = m + logf(se);\n            lik = wgt * (zl - lse);\n#pragma unroll\n";
-        s += fmt("            for (uint32_t c = 0; c < %uu; ++c) d[%uu + c] = wgt * ((label == (float)c ? 1.0f : 0.0f) - expf(y[%uu + c] - lse));\n        }\n", LL.rows, yl, yl);
-    } else {
-        s += fmt("        {\n            const float z = y[%uu];\n            lik = wgt * (label * z - (fmaxf(z, 0.0f) + log1pf(expf(-fabsf(z)))));\n            d[%uu] = wgt * (label - sigmoidf_(z));\n        }\n", yl, yl);
-    }
-    s += "        lik_acc += lik;\n";
-    for (uint32_t l = NL - 1; l >= 1; --l) {
-        const bsvi_bnn_layer& L = p->layers[l];
-        const bsvi_bnn_layer& Lp = p->layers[l - 1];
-        s += "#pragma unroll\n";
-        s += fmt("        for (uint32_t j = 0; j < %uu; ++j) {\n            float sm = 0.0f;\n#pragma unroll\n", L.cols);
-        s += fmt("            for (uint32_t i = 0; i < %uu; ++i) sm += wl[%uu + i * %uu + j] * d[%uu + i];\n", L.rows, L.weight_row0 - R1, L.cols, p->act_off[l]);
-        s += "            d[" + fmt("%uu", p->act_off[l - 1]) + " + j] = sm * " + act_grad(Lp.activation, "y[" + fmt("%uu", p->act_off[l - 1]) + " + j]") + ";\n        }\n";
-    }
-    s += "#pragma unroll\n        for (uint32_t u = 0; u < AW; ++u) { T[(size_t)u * BS + b] = y[u]; T[(size_t)(AW + u) * BS + b] = d[u]; }\n";
-    if (p->scale_learn)      // (the residuals where the last layer's outputs stood: what sigma's elements of the loop below read)
-        s += fmt("#pragma unroll\n        for (uint32_t c = 0; c < %uu; ++c) T[(size_t)(%uu + c) * BS + b] = A.lab[(size_t)b * %uu + c] - y[%uu + c];\n",
-                 LL.rows, yl, LL.rows, yl);
-    s += "#pragma unroll\n";
-    s += fmt("        for (uint32_t h = 0; h < %uu; ++h) {\n", L0.rows);
-    s += fmt("            const float g = live ? d[%uu + h] : 0.0f;\n", p->act_off[0]);
-    s += "            const uint16_t hi = gen_bf16(g);\n"
-         "            const float r1 = g - __uint_as_float((uint32_t)hi << 16);\n"
-         "            const uint16_t mid = gen_bf16(r1);\n"
-         "            const uint16_t lo = gen_bf16(r1 - __uint_as_float((uint32_t)mid << 16));\n";
-    if (pairs) {
-        s += "            pk[0][h] = bb ? (pk[0][h] | ((uint32_t)hi << 16)) : (uint32_t)hi;\n"
-             "            pk[1][h] = bb ? (pk[1][h] | ((uint32_t)mid << 16)) : (uint32_t)mid;\n"
-             "            pk[2][h] = bb ? (pk[2][h] | ((uint32_t)lo << 16)) : (uint32_t)lo;\n"
-             "        }\n"
-             "      }\n"
-             "#pragma unroll\n";
-        s += fmt("      for (uint32_t h = 0; h < %uu; ++h) {\n", L0.rows);
-        s += "          const size_t at = ((size_t)h * A.n_pad + n) * A.B_pad + 2u * b2, plane = (size_t)A.NC * A.B_pad;\n"
-             "          *reinterpret_cast<uint32_t*>(A.dlogp + at) = pk[0][h];\n"
-             "          *reinterpret_cast<uint32_t*>(A.dlogp + plane + at) = pk[1][h];\n"
-             "          *reinterpret_cast<uint32_t*>(A.dlogp + 2 * plane + at) = pk[2][h];\n"
-             "      }\n"
-             "    }\n";
-    } else {
-        s += "            const size_t at = ((size_t)h * A.n_pad + n) * A.B_pad + b, plane = (size_t)A.NC * A.B_pad;\n"
-             "            A.dlogp[at] = hi; A.dlogp[plane + at] = mid; A.dlogp[2 * plane + at] = lo;\n"
-             "        }\n"
-             "      }\n"
-             "    }\n";
-    }
-    s += ""
-         "    // the sample's likelihood: lanes, then the four waves, in order\n"
-         "    {\n"
-         "        const float ws = wave_sum(lik_acc);\n"
-         "        if ((tid & 63u) == 0u) red[tid >> 6] = ws;\n"
-         "    }\n"
-         "    __syncthreads();                                   // (and the tile is complete)\n"
-         "    if (tid == 0u) A.lik[n] = (red[0] + red[1]) + (red[2] + red[3]);\n"
-         "    // gradients of the small tensors: element r = sum_b d[du(r)][b] * y[yu(r)][b] (a bias: y = 1), rows in order\n";
-    s += "    for (uint32_t r = tid; r < RS; r += 256u) {\n";
-    s += ""
-         "        const uint32_t du = GEN_DU[r], yu = GEN_YU[r];\n"
-         "        const gen_f4* const dr = reinterpret_cast<const gen_f4*>(T + (size_t)du * BS);\n"
-         "        const gen_f4* const yr = reinterpret_cast<const gen_f4*>(T + (size_t)(yu == 0xFFFFu ? du : yu) * BS);\n"
-         "        float sm = 0.0f;\n"
-         "        if (yu == 0xFFFFu) {\n"
-         "            for (uint32_t q = 0; q < A.B_pad / 4u; ++q) { const gen_f4 dv = dr[q]; sm += dv.x; sm += dv.y; sm += dv.z; sm += dv.w; }\n"
-         "        } else {\n"
-         "            for (uint32_t q = 0; q < A.B_pad / 4u; ++q) {\n"
-         "                const gen_f4 dv = dr[q], yv = yr[q];\n"
-         "                sm += dv.x * yv.x; sm += dv.y * yv.y; sm += dv.z * yv.z; sm += dv.w * yv.w;\n"
-         "            }\n"
-         "        }\n"
-         "        A.gsm[(size_t)n * RS + r] = sm;\n"
-         "    }\n";
-    // a learnable sigma: its C per-sample sums are C more elements of this kind (a thread each, rows in order, 16-byte LDS reads, no LDS of
-    // their own), taken from the LAST thread down — with Rs <= 192 a wave that has no element of the small tensors, so that no wave runs
-    // both kinds one after the other.  The tile holds y_c - z_c (in the place of z_c, which no element reads) and d_c = wgt u / sigma_c of
-    // the last layer, and d_c (y_c - z_c) = wgt u^2: the loop of a weight element, instruction for instruction (four conditional
-    // subtractions of wgt per iteration made this one 17 us of a 94 us launch at config 4's scale, profiles/r16); rows behind the
-    // minibatch have d_c = 0, and sum_b wgt = wgt B leaves once, behind the loop
-    if (p->scale_learn)
-        s += fmt("    for (uint32_t c = 255u - tid; c < %uu; c += 256u) {\n"
-                 "        const gen_f4* const dr = reinterpret_cast<const gen_f4*>(T + (size_t)(AW + %uu + c) * BS);\n"
-                 "        const gen_f4* const rr = reinterpret_cast<const gen_f4*>(T + (size_t)(%uu + c) * BS);\n", LL.rows, yl, yl) +
-             "        const float wv = n < A.n_local ? A.lik_weight * (A.f_weight ? A.f_weight[n] : 1.0f) : 0.0f;\n"
-             "        float sm = 0.0f;\n"
-             "        for (uint32_t q = 0; q < A.B_pad / 4u; ++q) {\n"
-             "            const gen_f4 dv = dr[q], rv = rr[q];\n"
-             "            sm += dv.x * rv.x; sm += dv.y * rv.y; sm += dv.z * rv.z; sm += dv.w * rv.w;\n"
-             "        }\n" +
-             fmt("        A.gsig[(size_t)c * A.n_pad + n] = (sm - wv * (float)A.B) / A.lab[(size_t)A.B_pad * %uu + c];\n"
-                 "    }\n", LL.rows);
-    s += "}\n";
-    return s;
+struct BnnMidArgsSig { BnnMidArgs a; float* gsig; };
+
+// the network as bnn_source.h reads it
+static_assert(bsvi_bnn_source::MAX_LAYERS == BNN_MAX_LAYERS, "bnn_source.h holds as many layers as bnn_create admits");
+static bsvi_bnn_source::Net bnn_source_net(const bsvi_bnn* p) {
+    bsvi_bnn_source::Net N;
+    N.n_layers = p->d.n_layers;
+    for (uint32_t l = 0; l < N.n_layers; ++l) { N.layer[l] = p->layers[l]; N.act_off[l] = p->act_off[l]; }
+    N.R1 = p->R1; N.Rs = p->Rs; N.act_floats = (uint32_t)p->act_floats; N.C = p->C; N.B_pad = p->B_pad;
+    N.likelihood = p->d.likelihood; N.family = p->family; N.scale_learn = p->scale_learn; N.heads = p->heads;
+    memcpy(&N.head_a_bits, &p->head_a, 4); memcpy(&N.head_b_bits, &p->head_b, 4);
+    const char* e = getenv("BSVI_BNN_CAUCHY_LOG");
+    N.cauchy_log1p = e && !strcmp(e, "log1p");
+    return N;
 }
 
 static size_t bnn_mid_lds_bytes(const bsvi_bnn* p) { return bsvi_bnn_select::mid_lds_bytes(p->Rs, p->act_floats, p->B_pad); }
@@ -1440,55 +988,34 @@ static bsvi_bnn_select::BnnMiddle bnn_middle_for(const bsvi_bnn* p, bool mid_off
     sw.mid_off = mid_off; sw.jit_off = jit_off;
     return bsvi_bnn_select::middle(p->Rs, p->act_floats, p->B_pad, p->exact, sw);
 }
-// bnn_mid_gen compiled on first use; false: the separate launches serve (BSVI_BNN_MID=0, data that is not exactly bf16, a tile beyond
-// LDS, a failed compile)
-static bool bnn_mid_ready(const bsvi_bnn* p) {
+// a generated kernel (mid: bnn_mid_gen, else bnn_upper_gen, asked once bnn_mid_gen does not serve), compiled on first use.  false: what
+// stands behind it serves — the separate launches for bnn_mid_gen (BSVI_BNN_MID=0, data that is not exactly bf16, a tile beyond LDS),
+// the static bnn_upper for bnn_upper_gen (BSVI_BNN_JIT=0, small tensors beyond the register file), and for either a failed compile
+static bool bnn_gen_ready(const bsvi_bnn* p, const bool mid) {
     std::lock_guard<std::mutex> lock(p->jit_mu);
-    if (p->mid_state) return p->mid_state > 0;
-    p->mid_state = -1;
-    const char* e = getenv("BSVI_BNN_MID");
-    if (bnn_middle_for(p, e && e[0] == '0', false) != bsvi_bnn_select::MID_GEN) return false;
-    const std::string src = bnn_mid_source(p);
-    if (const char* dump = getenv("BSVI_BNN_SOURCE_DUMP")) {
-        if (FILE* f = fopen((std::string(dump) + ".mid").c_str(), "w")) { fputs(src.c_str(), f); fclose(f); }
-    }
-    std::vector<char> code;
-    std::string log;
-    if (bsvi_spec::obtain(src, code, log, nullptr)) {
-        if (getenv("BSVI_DEBUG")) fprintf(stderr, "bsvi: the generated bnn_mid did not compile:\n%s\n", log.c_str());
-        return false;
-    }
-    hipError_t err = hipModuleLoadData(&p->mid_module, code.data());
-    if (err == hipSuccess) err = hipModuleGetFunction(&p->mid_fn, p->mid_module, "bnn_mid_gen");
-    if (err == hipSuccess) err = hipFuncSetAttribute((const void*)p->mid_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bnn_mid_lds_bytes(p));
-    if (err != hipSuccess) { (void)hipGetLastError(); p->mid_fn = nullptr; return false; }
-    p->mid_state = 1;
-    return true;
-}
-
-// the generated kernel, compiled on first use; false: bnn_upper serves (BSVI_BNN_JIT=0, networks whose small tensors would not fit the
-// register file, a failed compile)
-static bool bnn_upper_ready(const bsvi_bnn* p) {
-    std::lock_guard<std::mutex> lock(p->jit_mu);
-    if (p->jit_state) return p->jit_state > 0;
-    p->jit_state = -1;
-    const char* e = getenv("BSVI_BNN_JIT");
-    if (bnn_middle_for(p, true, e && e[0] == '0') != bsvi_bnn_select::UPPER_GEN) return false;      // (asked once bnn_mid_gen does not serve)
-    std::vector<char> code;
-    std::string log;
-    const std::string src = bnn_upper_source(p);
+    BnnGen& g = mid ? p->mid_gen : p->upper_gen;
+    if (g.state) return g.state > 0;
+    g.state = -1;
+    const char* e = getenv(mid ? "BSVI_BNN_MID" : "BSVI_BNN_JIT");
+    const bool off = e && e[0] == '0';
+    if (bnn_middle_for(p, mid ? off : true, mid ? false : off) != (mid ? bsvi_bnn_select::MID_GEN : bsvi_bnn_select::UPPER_GEN)) return false;
+    const bsvi_bnn_source::Net net = bnn_source_net(p);
+    const std::string src = mid ? bsvi_bnn_source::mid_source(net) : bsvi_bnn_source::upper_source(net);
     if (const char* dump = getenv("BSVI_BNN_SOURCE_DUMP")) {      // tools: the generated translation unit
-        if (FILE* f = fopen(dump, "w")) { fputs(src.c_str(), f); fclose(f); }
+        if (FILE* f = fopen((std::string(dump) + (mid ? ".mid" : "")).c_str(), "w")) { fputs(src.c_str(), f); fclose(f); }
     }
+    std::vector<char> code;
+    std::string log;
     if (bsvi_spec::obtain(src, code, log, nullptr)) {
-        if (getenv("BSVI_DEBUG")) fprintf(stderr, "bsvi: the generated bnn_upper did not compile:\n%s\n", log.c_str());
+        if (getenv("BSVI_DEBUG")) fprintf(stderr, "bsvi: the generated %s did not compile:\n%s\n", mid ? "bnn_mid" : "bnn_upper", log.c_str());
         return false;
     }
-    hipError_t err = hipModuleLoadData(&p->jit_module, code.data());
-    if (err == hipSuccess) err = hipModuleGetFunction(&p->jit_fn, p->jit_module, "bnn_upper_gen");
-    if (err == hipSuccess) err = hipFuncSetAttribute((const void*)p->jit_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bsvi_bnn_select::upper_gen_lds_bytes(p->Rs));
-    if (err != hipSuccess) { (void)hipGetLastError(); p->jit_fn = nullptr; return false; }
-    p->jit_state = 1;
+    const size_t lds = mid ? bnn_mid_lds_bytes(p) : bsvi_bnn_select::upper_gen_lds_bytes(p->Rs);
+    hipError_t err = hipModuleLoadData(&g.module, code.data());
+    if (err == hipSuccess) err = hipModuleGetFunction(&g.fn, g.module, mid ? "bnn_mid_gen" : "bnn_upper_gen");
+    if (err == hipSuccess) err = hipFuncSetAttribute((const void*)g.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (err != hipSuccess) { (void)hipGetLastError(); g.fn = nullptr; return false; }
+    g.state = 1;
     return true;
 }
 
@@ -1669,7 +1196,7 @@ extern "C" int bsvi_bnn_set_likelihood_family(bsvi_bnn* p, uint32_t kind) {
         return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_likelihood_family: the handle is a classifier's (the family is that of a model made by bsvi_bnn_create_normal*)");
     if (kind != BSVI_DIST_NORMAL && kind != BSVI_DIST_LAPLACE && kind != BSVI_DIST_CAUCHY)
         return fail(BSVI_ERR_UNSUPPORTED, "bsvi_bnn_set_likelihood_family: the likelihood is Normal, Laplace or Cauchy");
-    if (p->launched.load() || p->jit_state || p->mid_state)
+    if (p->launched.load() || p->upper_gen.state || p->mid_gen.state)
         return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_likelihood_family: the model was launched already (set the family before the first launch)");
     p->family = kind;
     return BSVI_OK;
@@ -1727,8 +1254,8 @@ extern "C" void bsvi_bnn_destroy(bsvi_bnn* p) {
     if (!p) return;
     if (p->dev_blob) (void)hipFree(p->dev_blob);
     if (p->lat_blob) (void)hipFree(p->lat_blob);
-    if (p->jit_module) (void)hipModuleUnload(p->jit_module);
-    if (p->mid_module) (void)hipModuleUnload(p->mid_module);
+    if (p->upper_gen.module) (void)hipModuleUnload(p->upper_gen.module);
+    if (p->mid_gen.module) (void)hipModuleUnload(p->mid_gen.module);
     delete p;
 }
 
@@ -1738,9 +1265,24 @@ extern "C" int bsvi_bnn_exact_data(const bsvi_bnn* p) { return (p && p->exact) ?
 // as a launch would compile them, and one that did not compile reports what serves in its place
 extern "C" int bsvi_bnn_middle(const bsvi_bnn* p) {
     if (!p) return -1;
-    if (bnn_mid_ready(p)) return bsvi_bnn_select::MID_GEN;
-    if (bnn_upper_ready(p)) return bsvi_bnn_select::UPPER_GEN;
+    if (bnn_gen_ready(p, true)) return bsvi_bnn_select::MID_GEN;
+    if (bnn_gen_ready(p, false)) return bsvi_bnn_select::UPPER_GEN;
     return p->upper_lds ? bsvi_bnn_select::UPPER_LDS : bsvi_bnn_select::UPPER_MEM;
+}
+
+// the <MIXED, LATENT> instantiation a handle's launches take: latent prior scales (Q.n_latents; a predict call fills none: its draw
+// takes no prior), else some row's prior Laplace or Cauchy, else the all-Normal kernels
+static void bnn_launch_draw(const bsvi_bnn* p, const BParams& Q, const uint32_t row_chunks, hipStream_t s) {
+    const dim3 grid(row_chunks, (Q.n_pad + 3u) / 4u);
+    if (Q.n_latents) hipLaunchKernelGGL((bnn_draw<true, true>), grid, dim3(256), 0, s, Q);
+    else if (p->mixed) hipLaunchKernelGGL(bnn_draw<true>, grid, dim3(256), 0, s, Q);
+    else hipLaunchKernelGGL(bnn_draw<false>, grid, dim3(256), 0, s, Q);
+}
+static void bnn_launch_row_sums(const bsvi_bnn* p, const BParams& Q, hipStream_t s) {
+    const dim3 grid(((Q.R + 3) / 4 + 3) / 4);
+    if (Q.n_latents) hipLaunchKernelGGL((bnn_row_sums<true, true>), grid, dim3(256), 0, s, Q);
+    else if (p->mixed) hipLaunchKernelGGL(bnn_row_sums<true>, grid, dim3(256), 0, s, Q);
+    else hipLaunchKernelGGL(bnn_row_sums<false>, grid, dim3(256), 0, s, Q);
 }
 
 struct BnnLayout {
@@ -1854,11 +1396,9 @@ static int bnn_launch(const bsvi_bnn* p, const BParams& Q, const BnnLayout& L, h
     p->launched.store(true);
     const uint32_t lat_blocks = (Q.n_latents * Q.n_pad + 255u) / 256u;      // (none without latent prior scales)
     hipLaunchKernelGGL(bnn_head_gather, dim3(Q.B_pad * gy + head_blocks + lat_blocks), dim3(256), 0, s, Q, gy, head_blocks);
-    if (Q.n_latents) hipLaunchKernelGGL((bnn_draw<true, true>), dim3(L.row_chunks, (Q.n_pad + 3u) / 4u), dim3(256), 0, s, Q);
-    else if (p->mixed) hipLaunchKernelGGL(bnn_draw<true>, dim3(L.row_chunks, (Q.n_pad + 3u) / 4u), dim3(256), 0, s, Q);
-    else hipLaunchKernelGGL(bnn_draw<false>, dim3(L.row_chunks, (Q.n_pad + 3u) / 4u), dim3(256), 0, s, Q);
+    bnn_launch_draw(p, Q, L.row_chunks, s);
     int rc;
-    const bool mid = bnn_mid_ready(p);
+    const bool mid = bnn_gen_ready(p, true);
     if (mid) rc = bsvi_xgemm_nt_t(Q.Xb_bf, nullptr, Q.Wp, (long)Q.NC * Q.Kp, Q.a1T, (int)Q.B_pad, (int)Q.B_pad, (int)Q.NC, (int)Q.Kp, s);      // a1 as [(h, n)][b]
     else if (Q.exact) rc = bsvi_xgemm_nt(Q.Xb_bf, nullptr, Q.Wp, (long)Q.NC * Q.Kp, Q.a1T, (int)Q.NC, (int)Q.B_pad, (int)Q.NC, (int)Q.Kp, s);
     else rc = bsvi_gemm_f32(0, Q.Xb, (int)Q.P_ld, Q.W1f, (int)Q.P_ld, Q.a1T, (int)Q.NC, (int)Q.B_pad, (int)Q.NC, (int)Q.P, s);
@@ -1868,11 +1408,11 @@ static int bnn_launch(const bsvi_bnn* p, const BParams& Q, const BnnLayout& L, h
         const BnnMidArgsSig M{{Q.Wsm, Q.a1T, Q.lab, Q.gsm, Q.lik, Q.dlogp, Q.n_local, Q.n_pad, Q.B, Q.B_pad, Q.NC, Q.lik_weight, Q.f_weight}, Q.gsig};
         size_t size = p->scale_learn ? sizeof M : sizeof M.a;      // (the kernel of a constant sigma declares the first part alone)
         void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, (void*)&M, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-        HIP_TRY(hipModuleLaunchKernel(p->mid_fn, Q.n_pad, 1, 1, 256, 1, 1, (unsigned)bnn_mid_lds_bytes(p), s, nullptr, config));
+        HIP_TRY(hipModuleLaunchKernel(p->mid_gen.fn, Q.n_pad, 1, 1, 256, 1, 1, (unsigned)bnn_mid_lds_bytes(p), s, nullptr, config));
     } else {
         const dim3 ugrid(Q.n_pad / 64, (Q.B_pad + 7) / 8);
         const size_t wl_bytes = bsvi_bnn_select::upper_lds_bytes(p->Rs, p->act_floats);
-        if (bnn_upper_ready(p)) {
+        if (bnn_gen_ready(p, false)) {
             // (no LDS beyond the staging tile and registers only: several workgroups per CU — two rows per wave as above)
             BnnUpperArgsSig US{{Q.Wsm, Q.a1T, Q.lab, Q.acts, Q.deltas, Q.liknb, Q.da1T, Q.dlogp, Q.n_local, Q.n_pad, Q.B, Q.B_pad, Q.NC, 2u, Q.exact, Q.lik_weight, Q.f_weight}, Q.sigt};
             BnnUpperArgs& U = US.a;
@@ -1881,7 +1421,7 @@ static int bnn_launch(const bsvi_bnn* p, const BParams& Q, const BnnLayout& L, h
             size_t size = p->scale_learn ? sizeof US : sizeof U;
             void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &US, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
             const uint32_t gy = (Q.B_pad + 4u * U.rows_per_wave - 1u) / (4u * U.rows_per_wave);
-            HIP_TRY(hipModuleLaunchKernel(p->jit_fn, Q.n_pad / 64, gy, 1, 256, 1, 1, (unsigned)bsvi_bnn_select::upper_gen_lds_bytes(p->Rs), s, nullptr, config));
+            HIP_TRY(hipModuleLaunchKernel(p->upper_gen.fn, Q.n_pad / 64, gy, 1, 256, 1, 1, (unsigned)bsvi_bnn_select::upper_gen_lds_bytes(p->Rs), s, nullptr, config));
         }
         else if (p->upper_lds) hipLaunchKernelGGL(bnn_upper<true>, ugrid, dim3(256), wl_bytes, s, Q);
         else hipLaunchKernelGGL(bnn_upper<false>, ugrid, dim3(256), 0, s, Q);
@@ -1897,12 +1437,8 @@ static int bnn_launch(const bsvi_bnn* p, const BParams& Q, const BnnLayout& L, h
     if (Q.exact) rc = bsvi_xgemm_nt(Q.XbT_bf, nullptr, Q.dlogp, (long)Q.NC * Q.B_pad, Q.GT, (int)Q.NC, (int)Q.P, (int)Q.NC, (int)Q.B_pad, s);
     else rc = bsvi_gemm_f32(1, Q.da1T, (int)Q.B_pad, Q.Xb, (int)Q.P_ld, Q.GT, (int)Q.P_ld, (int)Q.NC, (int)Q.P, (int)Q.B_pad, s);
     if (rc) return rc;
-    if (Q.n_latents) {
-        hipLaunchKernelGGL((bnn_row_sums<true, true>), dim3(((Q.R + 3) / 4 + 3) / 4), dim3(256), 0, s, Q);
-        hipLaunchKernelGGL(bnn_latent_terms, dim3(Q.n_pad / 256u + (Q.n_pad % 256u ? 1u : 0u)), dim3(256), 0, s, Q);
-    }
-    else if (p->mixed) hipLaunchKernelGGL(bnn_row_sums<true>, dim3(((Q.R + 3) / 4 + 3) / 4), dim3(256), 0, s, Q);
-    else hipLaunchKernelGGL(bnn_row_sums<false>, dim3(((Q.R + 3) / 4 + 3) / 4), dim3(256), 0, s, Q);
+    bnn_launch_row_sums(p, Q, s);
+    if (Q.n_latents) hipLaunchKernelGGL(bnn_latent_terms, dim3(Q.n_pad / 256u + (Q.n_pad % 256u ? 1u : 0u)), dim3(256), 0, s, Q);
     hipLaunchKernelGGL(bnn_epilogue, dim3(1), dim3(1024), 0, s, Q, L.row_blocks);
     if (Q.n_latents) hipLaunchKernelGGL(bnn_latent_grads, dim3(Q.n_latents), dim3(256), 0, s, Q);
     if (Q.n_uniform_grad) hipLaunchKernelGGL(bnn_uniform_grads, dim3((Q.n_uniform_grad + 255) / 256), dim3(256), 0, s, Q);
@@ -2293,8 +1829,7 @@ extern "C" int bsvi_bnn_predict(const bsvi_bnn* p, const bsvi_bnn_predict_args* 
     const uint32_t head_n = std::max(Q.R, Q.C);
     hipLaunchKernelGGL(bnn_predict_head, dim3((head_n + 255) / 256), dim3(256), 0, s, Q, V);
     // (the prior partials of the draw are written and never read: the MIXED instantiation all the same, so that the two stay one kernel each)
-    if (p->mixed) hipLaunchKernelGGL(bnn_draw<true>, dim3(L.row_chunks, (Q.n_pad + 3u) / 4u), dim3(256), 0, s, Q);
-    else hipLaunchKernelGGL(bnn_draw<false>, dim3(L.row_chunks, (Q.n_pad + 3u) / 4u), dim3(256), 0, s, Q);
+    bnn_launch_draw(p, Q, L.row_chunks, s);
     HIP_TRY(hipGetLastError());
     const uint32_t gy = (std::max(Q.Kp, Q.P_ld) + 255) / 256;
     for (uint32_t m0 = 0; m0 < a->n_rows; m0 += L.rows_pass) {

@@ -1,6 +1,6 @@
 // bnn_select.h — which kernel serves the middle of a Bayesian-neural-network iteration (upper layers, likelihood, reverse sweep), and the
 // LDS each of them asks for: ONE pure function from the network's size to the kind.  Host only: no HIP, no getenv —
-// bnn_kernel.inc fills the input (bnn_mid_ready, bnn_upper_ready, bnn_create); tests/c_abi/bnn_select_table.cpp walks the table without a GPU.
+// bnn_kernel.inc fills the input (bnn_gen_ready, bnn_create); tests/c_abi/bnn_select_table.cpp walks the table without a GPU.
 // A kernel that does not compile is not this header's business: the fallbacks stay where the compile is tried.
 #pragma once
 #include <stddef.h>
