@@ -69,6 +69,10 @@ int compile(const std::string& src, std::vector<char>& code, std::string& log);
 int obtain(const std::string& src, std::vector<char>& code, std::string& log, int* origin);
 int last_origin();
 int last_variant();     // variant of this thread's last launch of a specialised kernel, -1: none yet
+// the optimizer a launch of the owners' loop with this configuration is compiled for (spec_main.h SPEC_OPT_LITERAL; 0: the generic
+// object), and what this thread's last launch of a specialised kernel took
+int opt_literal(const bsvi_opt_cfg* cfg);
+int last_opt_literal();
 std::string cache_directory();
 std::string compiler_identity();
 // bytes of workspace a launch over n_local samples needs behind the interpreter's region

@@ -2394,6 +2394,8 @@ extern "C" int bsvi_jit_load(const char* source, size_t* code_bytes, int* origin
 
 extern "C" int bsvi_jit_last_origin(void) { return bsvi_spec::last_origin(); }
 extern "C" int bsvi_spec_last_variant(void) { return bsvi_spec::last_variant(); }
+extern "C" int bsvi_spec_opt_literal(const bsvi_opt_cfg* cfg) { return bsvi_spec::opt_literal(cfg); }
+extern "C" int bsvi_spec_last_opt_literal(void) { return bsvi_spec::last_opt_literal(); }
 
 extern "C" size_t bsvi_jit_cache_dir(char* buf, size_t capacity) {
     const std::string dir = bsvi_spec::cache_directory();

@@ -84,14 +84,29 @@ __device__ __forceinline__ float spec_utransform_grad(uint32_t t, float x) {
     const float soft = x > 20.0f ? 1.0f : s;
     return t == BSVI_UT_IDENTITY ? 1.0f : (t == BSVI_UT_SOFTPLUS ? soft : s * (1.0f - s));
 }
+// An entry's three values go to its homes.  SPEC_HOME(k) is what a writer keeps of entry k (the owners' rows hold it in the place
+// of k): k itself in the compact layout; SPEC_QUADS: the homes of U and of the pair (1 / U, log U) in float offsets, 16 bits each,
+// from the generated map — two stores, as in the compact layout.
+#if SPEC_QUADS
+__constant__ uint32_t spec_q_homes[SPEC_N_UNIFORM] = SPEC_Q_HOMES;
+#define SPEC_HOME(k) spec_q_homes[k]
+__device__ __forceinline__ void spec_store_uniform(uint32_t home, float u) {
+    float* const pair = spec_lds + (home >> 16);
+    spec_lds[home & 0xFFFFu] = u;
+    pair[0] = spec_rcp(u);
+    pair[1] = spec_log(u);
+}
+#else
+#define SPEC_HOME(k) (k)
 __device__ __forceinline__ void spec_store_uniform(uint32_t k, float u) {
     spec_lds[k] = u;
     spec_lds[SPEC_OFF_UR + k] = spec_rcp(u);
     spec_lds[SPEC_OFF_UL + k] = spec_log(u);
 }
+#endif
 __device__ __forceinline__ void spec_publish_uniform(const uint32_t* TAB, uint32_t k, float x) {
     const uint32_t w1 = TAB[4 * k + 1];
-    spec_store_uniform(k, __uint_as_float(TAB[4 * k + 2]) + __uint_as_float(TAB[4 * k + 3]) * utransform_common(w1 & 0xFFu, x));
+    spec_store_uniform(SPEC_HOME(k), __uint_as_float(TAB[4 * k + 2]) + __uint_as_float(TAB[4 * k + 3]) * utransform_common(w1 & 0xFFu, x));
 }
 
 // The most uniform entries a parameter of this program owns, 1 or 2 (specialize.cpp): the owners' code handles that many.
@@ -295,7 +310,7 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
     T.lane = lane;
     T.n = blockIdx.x * nthreads + tid;
     T.active = false; T.nc = 0; T.nidx = 0;
-    T.vz = T.n >> 31;
+    T.vz = SPEC_VZ(T.n);
     T.tile = wave * SPEC_TR_FLOATS + lane;
     const uint32_t sample_base = SPEC_A->sample_base;
     const uint32_t n_chunks = (SPEC_A->n_local + G * nthreads - 1u) / (G * nthreads);
@@ -345,7 +360,7 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
         if (h_uni2) TAB[tid + nthreads] = r_uni2;
         if (h_ptr) TAB[SPEC_TAB_PTR + tid] = r_ptr;
         if (h_pos) { TAB[SPEC_TAB_POS + tid] = r_pos; TAB[SPEC_TAB_IDX + tid] = r_idx; }
-        if (h_obs) spec_lds[SPEC_N_UNIFORM + tid] = r_obs;
+        if (h_obs) spec_lds[SPEC_OBS0 + tid] = r_obs;
         if (h_par) {
             PS[tid] = r_par;
             if (step) {
@@ -357,7 +372,7 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
         for (uint32_t i = tid + 2u * nthreads; i < 4u * SPEC_N_UNIFORM; i += nthreads) TAB[i] = uniform[i];
         for (uint32_t i = tid + nthreads; i < SPEC_N_PARAMS + 1u; i += nthreads) TAB[SPEC_TAB_PTR + i] = pu_ptr[i];
         for (uint32_t j = tid + nthreads; j < SPEC_N_POS; j += nthreads) { TAB[SPEC_TAB_POS + j] = pu_pos[j]; TAB[SPEC_TAB_IDX + j] = pu_idx[j]; }
-        for (uint32_t i = tid + nthreads; i < SPEC_N_OBS; i += nthreads) spec_lds[SPEC_N_UNIFORM + i] = obs[i];
+        for (uint32_t i = tid + nthreads; i < SPEC_N_OBS; i += nthreads) spec_lds[SPEC_OBS0 + i] = obs[i];
         for (uint32_t i = tid + nthreads; i < SPEC_N_PARAMS; i += nthreads) {
             PS[i] = params[i];
             if (step) {
@@ -458,6 +473,23 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
 #else
 #define SPEC_PLAIN_SGD 0
 #endif
+// The optimizer as a literal (SPEC_OPT_LITERAL, a define the LAUNCH puts in front of the variant's source: specialize.cpp,
+// opt_literal): the kind and the on/off options cannot change inside a launch, so a code object of its own has them as
+// constants — the other kinds' arms are not compiled, nothing is dispatched and no arm's registers are merged.  The arithmetic
+// is the same functions on a configuration whose launch-invariant words are constants; learning rate, betas and eps stay data.
+//   0 (or not defined)  generic: every kind, dispatched on cfg
+//   1                   SGD without momentum, weight decay, maximize or nesterov
+//   2                   Adam without amsgrad, weight decay or maximize
+#if defined(SPEC_OPT_LITERAL) && (SPEC_OPT_LITERAL < 0 || SPEC_OPT_LITERAL > 2)
+#error "SPEC_OPT_LITERAL: 0, 1 and 2 exist"
+#endif
+#if SPEC_LEAN_OWNERS && defined(SPEC_OPT_LITERAL) && SPEC_OPT_LITERAL == 1
+#define SPEC_OPT_FIX(c) do { (c).kind = BSVI_OPT_SGD; (c).momentum = 0.0f; (c).weight_decay = 0.0f; (c).nesterov = 0u; (c).maximize = 0u; } while (0)
+#elif SPEC_LEAN_OWNERS && defined(SPEC_OPT_LITERAL) && SPEC_OPT_LITERAL == 2
+#define SPEC_OPT_FIX(c) do { (c).kind = BSVI_OPT_ADAM; (c).weight_decay = 0.0f; (c).amsgrad = 0u; (c).maximize = 0u; } while (0)
+#else      // (generic; a kernel without the lean owners' loop has no literal form: the define changes nothing there)
+#define SPEC_OPT_FIX(c) do { } while (0)
+#endif
 #if defined(SPEC_TAIL_MUST_BE_OFF) && (SPEC_DEFER_BOOK || SPEC_PLAIN_SGD)
 #error "the tail's arrangements are compiled into a kernel that keeps the previous epilogue"
 #endif
@@ -501,7 +533,7 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
                 if (e < own.n) {
                     const uint32_t k = TAB[SPEC_TAB_IDX + j0 + e];
                     own.pos[e] = TAB[SPEC_TAB_POS + j0 + e];
-                    own.k[e] = k;
+                    own.k[e] = SPEC_HOME(k);
                     own.tr[e] = TAB[4 * k + 1] & 0xFFu;
                     own.a[e] = __uint_as_float(TAB[4 * k + 2]);
                     own.b[e] = __uint_as_float(TAB[4 * k + 3]);
@@ -571,7 +603,7 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
         _Pragma("unroll") for (uint32_t q = 0; q < ((B) + 63u) / 64u; ++q) {                                        \
             const uint32_t b = lane + 64u * q;                                                                      \
             if (b < (B)) {                                                                                          \
-                _Pragma("unroll") for (uint32_t e = 0; e < (r); ++e) spec_lds[SPEC_N_UNIFORM + (o) + b * (r) + e] = Gv.v[(base) + q * (r) + e]; \
+                _Pragma("unroll") for (uint32_t e = 0; e < (r); ++e) spec_lds[SPEC_OBS0 + (o) + b * (r) + e] = Gv.v[(base) + q * (r) + e]; \
             }                                                                                                       \
         }
         SPEC_MB_SOURCES(SPEC_MB_STORE)
@@ -715,7 +747,8 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
             if (owners) {
                 // ---- beside the bodies: what depends on this iteration's theta and the step count only, then set 0
                 SPEC_RELOAD_ARGS();
-                const bsvi_opt_cfg cfg = SPEC_A->cfg;
+                bsvi_opt_cfg cfg = SPEC_A->cfg;
+                SPEC_OPT_FIX(cfg);
 #pragma unroll
                 for (uint32_t e = 0; e < SPEC_OWN_ENTRIES; ++e) fac[e] = own.b[e] * spec_utransform_grad(own.tr[e], own.theta);
                 if (cfg.kind == BSVI_OPT_ADAM) bias = optimizer_adam_bias(cfg, own.p1, own.p2);     // (kept when the step is taken)
@@ -753,6 +786,7 @@ extern "C" __global__ void __launch_bounds__(SPEC_BOUND_THREADS) SPEC_VGPR_ATTR 
                 asm volatile("" : "+s"(e_cfg.kind), "+s"(e_cfg.lr), "+s"(e_cfg.momentum), "+s"(e_cfg.dampening), "+s"(e_cfg.weight_decay),
                              "+s"(e_cfg.nesterov), "+s"(e_cfg.beta1), "+s"(e_cfg.beta2), "+s"(e_cfg.eps), "+s"(e_cfg.amsgrad), "+s"(e_cfg.maximize));
 #endif
+                SPEC_OPT_FIX(e_cfg);
 #if SPEC_PLAIN_SGD
                 plain_sgd = __builtin_amdgcn_readfirstlane((e_cfg.kind == BSVI_OPT_SGD && e_cfg.momentum == 0.0f && e_cfg.weight_decay == 0.0f
                                                             && !e_cfg.maximize) ? 1 : 0) != 0;

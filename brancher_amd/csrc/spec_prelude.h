@@ -125,9 +125,28 @@ __device__ __forceinline__ PhiloxKey spec_key(const SpecBody& A, const SpecLane&
 #ifndef SPEC_ACCUMULATE_CHUNKS
 #define SPEC_ACCUMULATE_CHUNKS 0
 #endif
+// SPEC_QUADS (specialize.cpp, BSVI_SPEC_QUADS; one of the trimmed kernels' items, see below): the three tables are one, laid out by
+// the generated map (SPEC_QUADS_MAP: SPEC_Q_HOMES, SPEC_QV_*) —
+//   Q    [SPEC_Q_GROUPS][4]             {U[c], U[s], 1/U[s], log U[s]} of a Normal record with location offset c and scale s
+//   then the U no group holds, then the (1/U, log U) pairs no group holds: 3 * SPEC_N_UNIFORM floats with the groups
+//   OBS  [SPEC_N_OBS]                   the observed data, from the next 16-byte boundary (SPEC_OBS0)
+// and the body reads a group, and four observations, with one 16-byte load.  It is how the body reads the table, so it goes
+// with the shared constants' switch; SPEC_DEBUG_NO_QUADS is its own (BSVI_SPEC_DEFINES).
+#if defined(SPEC_TRIM) && defined(SPEC_QUADS_MAP) && !defined(SPEC_DEBUG_NO_SHARED_CONST) && !defined(SPEC_DEBUG_NO_QUADS)
+#define SPEC_QUADS 1
+#else
+#define SPEC_QUADS 0
+#endif
 #define SPEC_MAX_WAVES (SPEC_MAX_THREADS / 64)
 #define SPEC_U_PAD ((SPEC_N_UNIFORM + SPEC_N_OBS + 3) / 4 * 4)
 #define SPEC_NU_PAD ((SPEC_N_UNIFORM + 3) / 4 * 4)
+#if SPEC_QUADS
+#define SPEC_OBS0 ((3 * SPEC_N_UNIFORM + 3) / 4 * 4)
+#define SPEC_TABLE_FLOATS ((SPEC_OBS0 + SPEC_N_OBS + 3) / 4 * 4)
+#else
+#define SPEC_OBS0 SPEC_N_UNIFORM
+#define SPEC_TABLE_FLOATS (SPEC_U_PAD + 2 * SPEC_NU_PAD)
+#endif
 #ifndef SPEC_TILE
 #define SPEC_TILE 0
 #endif
@@ -145,7 +164,7 @@ __device__ __forceinline__ PhiloxKey spec_key(const SpecBody& A, const SpecLane&
 #define SPEC_SCR_FLOATS (4 * (SPEC_N_POS + 2) + 4)
 #define SPEC_OFF_UR SPEC_U_PAD
 #define SPEC_OFF_UL (SPEC_OFF_UR + SPEC_NU_PAD)
-#define SPEC_OFF_WS (SPEC_OFF_UL + SPEC_NU_PAD)
+#define SPEC_OFF_WS SPEC_TABLE_FLOATS
 #define SPEC_OFF_RED (SPEC_OFF_WS + SPEC_MAX_WAVES * SPEC_WS_PAD)
 #define SPEC_OFF_PS (SPEC_OFF_RED + SPEC_RED_FLOATS)
 #define SPEC_OFF_TAB (SPEC_OFF_PS + 5 * SPEC_NP_PAD)
@@ -161,9 +180,34 @@ __shared__ __attribute__((aligned(16))) float spec_lds[SPEC_LDS_FLOATS];
 // scalar register (ds_read + v_readfirstlane): ~90 of them on top of the argument block overflow the 102 SGPRs and
 // spill through v_writelane / v_readlane.  Adding the per-lane zero keeps the entries in vector registers; the reads
 // still broadcast, and adjacent entries still merge into ds_read2 / ds_read_b128.
+// SPEC_QUADS: the per-lane zero is a multiple of four floats, so that a group's address is provably 16-byte aligned; an entry
+// resolves to its home through the generated per-entry defines — a component of its group's registers (SPEC_QG; loaded by the
+// SPEC_QLOAD the generator puts in front of the first statement that reads it) or a compact home (SPEC_QM).
+typedef float spec_f4 __attribute__((ext_vector_type(4)));
+#if SPEC_QUADS
+#define SPEC_QPASTE_(p, k) p##k
+#define SPEC_QPASTE(p, k) SPEC_QPASTE_(p, k)              // (k may be SPEC_SAME(k, k0): expanded before it is pasted)
+#define SPEC_U(k) SPEC_QPASTE(SPEC_QV_U_, k)
+#define SPEC_UR(k) SPEC_QPASTE(SPEC_QV_R_, k)
+#define SPEC_UL(k) SPEC_QPASTE(SPEC_QV_L_, k)
+#define SPEC_QG(g, c) spec_q##g.c
+#define SPEC_QO(j, c) spec_o##j.c
+#define SPEC_QM(h) spec_lds[(h) + T.vz]
+#define SPEC_QVAR(g) spec_f4 spec_q##g
+#define SPEC_OVAR(j) spec_f4 spec_o##j
+#define SPEC_QLOAD(g) spec_q##g = *reinterpret_cast<const spec_f4*>(&spec_lds[4 * (g) + T.vz])
+#define SPEC_OLOAD(j) spec_o##j = *reinterpret_cast<const spec_f4*>(&spec_lds[SPEC_OBS0 + 4 * (j) + T.vz])
+#define SPEC_VZ(n) (((n) >> 31) << 2)
+#else
 #define SPEC_U(k) spec_lds[(k) + T.vz]
 #define SPEC_UR(k) spec_lds[SPEC_OFF_UR + (k) + T.vz]
 #define SPEC_UL(k) spec_lds[SPEC_OFF_UL + (k) + T.vz]
+#define SPEC_QVAR(g)
+#define SPEC_OVAR(j)
+#define SPEC_QLOAD(g)
+#define SPEC_OLOAD(j)
+#define SPEC_VZ(n) ((n) >> 31)
+#endif
 
 
 // ---- the trimmed kernels (specialize.cpp, BSVI_SPEC_TRIM): work the result does not need, off the sample waves.  Each item has
@@ -172,6 +216,7 @@ __shared__ __attribute__((aligned(16))) float spec_lds[SPEC_LDS_FLOATS];
 //      a and b): the body reads k0, once, where it read twenty copies (the likelihood terms' measure_noise at config 1).
 //  SPEC_ENT_NOISE    the scale gradient of a sampled node with an entropy term only: fma(zb, eps, w / S).  It was
 //      (0 + w / S) + zb * eps, one rounding as well, with the 0 + x an instruction of its own.
+//  SPEC_QUADS        the layout of the table above: a Normal record's four table values, and four observations, are one 16-byte read.
 //  SPEC_FLUSH_MASK   SPEC_TILE: SPEC_DU stores a lane's contribution as it is and spec_du_flush leaves the idle lanes' columns out,
 //      instead of a select in front of every store in every wave (only a shard's last wave has idle lanes).
 #if defined(SPEC_TRIM) && !defined(SPEC_DEBUG_NO_SHARED_CONST)
@@ -189,8 +234,6 @@ __shared__ __attribute__((aligned(16))) float spec_lds[SPEC_LDS_FLOATS];
 #else
 #define SPEC_FLUSH_MASK 0
 #endif
-
-typedef float spec_f4 __attribute__((ext_vector_type(4)));
 
 // Contribution of this lane to position `pos` (a literal).  Two schemes, chosen per program by the generator:
 //

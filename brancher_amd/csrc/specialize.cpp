@@ -89,11 +89,12 @@ struct EmitOptions {
     bool fold = true;           // literal constants folded (the lean body)
     bool trim = false;          // SPEC_TRIM (spec_prelude.h)
     bool two_pass = true;       // long BlackBox programs run their sinks twice (BSVI_SPEC_TWO_PASS)
+    bool quads = false;         // SPEC_QUADS (spec_prelude.h; with trim only): table values grouped by the record that reads them
 };
 
 class Emitter {
 public:
-    Emitter(const bsvi_program_desc& d, const EmitOptions& o) : d_(d), diag_(o.diag), fold_(o.fold), trim_(o.trim) {
+    Emitter(const bsvi_program_desc& d, const EmitOptions& o) : d_(d), diag_(o.diag), fold_(o.fold), trim_(o.trim), quads_(o.trim && o.quads) {
         keep_eps_ = d.n_noise <= kKeepEpsRows;
         // (trim_) constant entries that repeat an earlier one — same value bits, transform, a and b: the table publishes the same
         // three numbers for both, every iteration — are read at the earlier one's index (SPEC_SAME, spec_prelude.h)
@@ -130,6 +131,10 @@ public:
         if (d.estimator == BSVI_EST_BLACKBOX && !two_pass_) reschedule_ = false;
         du_total_.assign(d.n_uniform_grad, 0);
         du_seen_.assign(d.n_uniform_grad, 0);
+        reload_ = d.n_code > kFenceAboveCode;
+        group_u_.assign(d.n_uniform, -1);
+        group_rl_.assign(d.n_uniform, -1);
+        slot_u_.assign(d.n_uniform, 0);
     }
 
     bool run(std::string& why) {
@@ -139,6 +144,7 @@ public:
         counting_ = false;
         body_.clear();
         fwd_groups_.clear(); rev_groups_.clear(); node_rows_.clear();
+        place_homes();
         walk();
         // entries nothing contributed to still own a position (their gradient is 0)
         for (uint32_t k = 0; k < d_.n_uniform_grad; ++k)
@@ -168,8 +174,30 @@ public:
         return s;
     }
     const std::vector<uint32_t>& order() const { return order_; }     // position -> uniform entry
+    // ---- SPEC_QUADS (spec_prelude.h): the homes of the table's values in LDS, as defines in front of spec_prelude.h.  Empty
+    //      when no record of the program forms a group: the program keeps the compact layout.
+    uint32_t n_quads() const { return n_quads_; }
+    std::string quads_defines() const {
+        if (!n_quads_) return std::string();
+        std::string s = "// SPEC_QUADS: the values one Normal record reads — location offset, scale, 1 / scale, log scale — are one 16-byte group\n";
+        s += fmt("#define SPEC_QUADS_MAP 1\n#define SPEC_Q_GROUPS %u\n", n_quads_);
+        s += "// per entry, in float offsets: the home of U | the home of 1 / U << 16 (log U follows it)\n#define SPEC_Q_HOMES {";
+        for (uint32_t k = 0; k < d_.n_uniform; ++k) s += fmt("%s0x%08xu", k ? ", " : "", home_u_[k] | (home_rl_[k] << 16));
+        s += "}\n";
+        const char* const comp = "xyzw";
+        for (uint32_t k = 0; k < d_.n_uniform; ++k) {
+            if (group_u_[k] >= 0) s += fmt("#define SPEC_QV_U_%u SPEC_QG(%d, %c)\n", k, group_u_[k], comp[slot_u_[k]]);
+            else s += fmt("#define SPEC_QV_U_%u SPEC_QM(%u)\n", k, home_u_[k]);
+            if (group_rl_[k] >= 0) s += fmt("#define SPEC_QV_R_%u SPEC_QG(%d, z)\n#define SPEC_QV_L_%u SPEC_QG(%d, w)\n", k, group_rl_[k], k, group_rl_[k]);
+            else s += fmt("#define SPEC_QV_R_%u SPEC_QM(%u)\n#define SPEC_QV_L_%u SPEC_QM(%u)\n", k, home_rl_[k], k, home_rl_[k] + 1u);
+        }
+        for (uint32_t i = 0; i < d_.n_obs; ++i) s += fmt("#define SPEC_QV_U_%u SPEC_QO(%u, %c)\n", d_.n_uniform + i, i / 4u, comp[i & 3u]);
+        return s;
+    }
     std::string declarations() const {
         std::string s;
+        for (uint32_t g : used_quads_) s += fmt("    SPEC_QVAR(%u);\n", g);
+        for (uint32_t j : used_obs4_) s += fmt("    SPEC_OVAR(%u);\n", j);
         for (uint32_t i = 0; i < d_.n_slots; ++i) s += fmt("    float v_%u = 0.0f, a_%u = 0.0f;\n", i, i);
         if (!direct_du_) for (uint32_t k = 0; k < d_.n_uniform_grad; ++k) if (du_total_[k]) s += fmt("    float du_%u = 0.0f;\n", k);
         for (uint32_t g : all_groups_) s += fmt("    float pn_%u_0 = 0.0f, pn_%u_1 = 0.0f, pn_%u_2 = 0.0f, pn_%u_3 = 0.0f;\n", g, g, g, g);
@@ -180,7 +208,19 @@ public:
 
 private:
     const bsvi_program_desc& d_;
-    bool diag_, fold_, trim_;
+    bool diag_, fold_, trim_, quads_;
+    // SPEC_QUADS.  A group is claimed in the counting walk by the first Normal record whose location offset c (or the one table
+    // value its location is) and scale s are table entries no group holds yet: {U[c], U[s], 1/U[s], log U[s]}.  Every other value
+    // keeps a compact home behind the groups: the remaining U, then the remaining (1/U, log U) pairs, neighbours for every entry;
+    // the observations follow on a 16-byte boundary (spec_prelude.h).
+    uint32_t n_quads_ = 0;
+    std::vector<int> group_u_, group_rl_;           // entry -> the group that holds its U / its (1/U, log U), or -1
+    std::vector<uint32_t> slot_u_, home_u_, home_rl_;
+    // the body loads a group into a register quadruple (SPEC_QLOAD) in front of the first statement that reads one of its values —
+    // of every record again in long programs, which must not hold table values across the body (walk(): the fences)
+    bool reload_ = false;
+    mutable std::set<uint32_t> have_quads_, have_obs4_, used_quads_, used_obs4_;
+    mutable std::vector<std::string> pending_;
     std::vector<uint32_t> same_as_;       // uniform entry -> the first entry that publishes the same constant (itself otherwise)
     bool keep_eps_ = true, counting_ = true, direct_du_ = false, reschedule_ = true, two_pass_ = false;
     int sink_mode_ = 0;         // two_pass_: 1 = a sink's value only (forward sweep), 2 = its adjoints only (reverse sweep); 0 = both
@@ -195,7 +235,54 @@ private:
         memcpy(&I, d_.code + 8 * (size_t)pc, 32);
         return I;
     }
-    void line(const std::string& s) { if (!counting_) { body_ += "    "; body_ += s; body_ += "\n"; } }
+    void line(const std::string& s) {
+        if (counting_) return;
+        for (const std::string& load : pending_) { body_ += "    "; body_ += load; body_ += "\n"; }
+        pending_.clear();
+        body_ += "    "; body_ += s; body_ += "\n";
+    }
+    void claim(const Insn& I, uint32_t e) {
+        if (!quads_ || !counting_) return;
+        // (the location's own table value: its offset c — or, where the location folds to one operand, a * 1 + 0, that operand)
+        const int la = literal(I.a, e), lb = literal(I.b, e), lc = literal(I.c, e);
+        if (lc == 0 && la != 1 && lb != 1) return;
+        const Opnd c = resolve(lc != 0 ? I.c : (lb == 1 ? I.a : I.b), e), s = resolve(I.s, e);
+        if (c.lane || s.lane || c.idx >= d_.n_uniform || s.idx >= d_.n_uniform || c.idx == s.idx) return;
+        if (same_as_[c.idx] != c.idx || same_as_[s.idx] != s.idx) return;                     // (shared constants stay compact)
+        if (group_u_[c.idx] >= 0 || group_u_[s.idx] >= 0 || group_rl_[s.idx] >= 0) return;   // a value has one home
+        const int g = (int)n_quads_++;
+        group_u_[c.idx] = g; slot_u_[c.idx] = 0;
+        group_u_[s.idx] = g; slot_u_[s.idx] = 1;
+        group_rl_[s.idx] = g;
+    }
+    void place_homes() {
+        home_u_.assign(d_.n_uniform, 0);
+        home_rl_.assign(d_.n_uniform, 0);
+        uint32_t next = 4u * n_quads_;
+        for (uint32_t k = 0; k < d_.n_uniform; ++k) home_u_[k] = group_u_[k] >= 0 ? 4u * (uint32_t)group_u_[k] + slot_u_[k] : next++;
+        for (uint32_t k = 0; k < d_.n_uniform; ++k) {
+            if (group_rl_[k] >= 0) { home_rl_[k] = 4u * (uint32_t)group_rl_[k] + 2u; continue; }
+            home_rl_[k] = next;
+            next += 2u;
+        }
+        have_quads_.clear(); have_obs4_.clear(); used_quads_.clear(); used_obs4_.clear(); pending_.clear();
+    }
+    // a table value is about to be read: its group's load goes in front of the statement (line())
+    void touch(int group) const {
+        if (counting_ || !n_quads_ || group < 0 || have_quads_.count((uint32_t)group)) return;
+        have_quads_.insert((uint32_t)group); used_quads_.insert((uint32_t)group);
+        pending_.push_back(fmt("SPEC_QLOAD(%d);", group));
+    }
+    void touch_u(uint32_t idx) const {
+        if (counting_ || !n_quads_) return;
+        if (idx < d_.n_uniform) { touch(group_u_[same_as_[idx]]); return; }
+        const uint32_t j = (idx - d_.n_uniform) / 4u;                                         // observations: four to a load
+        if (have_obs4_.count(j)) return;
+        have_obs4_.insert(j); used_obs4_.insert(j);
+        pending_.push_back(fmt("SPEC_OLOAD(%u);", j));
+    }
+    void touch_rl(uint32_t idx) const { if (idx < d_.n_uniform) touch(group_rl_[same_as_[idx]]); }
+    void next_record() { if (reload_) { have_quads_.clear(); have_obs4_.clear(); } }
 
     // ---- operands (include/bsvi.h: byte_offset | walks<<30 | per_lane<<31)
     struct Opnd { bool lane; uint32_t idx; };
@@ -207,6 +294,7 @@ private:
     }
     std::string val(uint32_t o, uint32_t e) const {
         const Opnd p = resolve(o, e);
+        if (!p.lane) touch_u(p.idx);
         return p.lane ? fmt("v_%u", p.idx) : fmt("SPEC_U(%s)", entry(p.idx).c_str());
     }
     // the index a table read is emitted with (observations, parameters and first occurrences: their own)
@@ -275,10 +363,12 @@ private:
     // 1/S and log S of a Normal node's scale: companions of the uniform table when S is lane-uniform
     std::string rcp_of(uint32_t o, uint32_t e) const {
         const Opnd p = resolve(o, e);
+        if (!p.lane) touch_rl(p.idx);
         return p.lane ? fmt("spec_rcp(v_%u)", p.idx) : fmt("SPEC_UR(%s)", entry(p.idx).c_str());
     }
     std::string log_of(uint32_t o, uint32_t e) const {
         const Opnd p = resolve(o, e);
+        if (!p.lane) touch_rl(p.idx);
         return p.lane ? fmt("spec_log(v_%u)", p.idx) : fmt("SPEC_UL(%s)", entry(p.idx).c_str());
     }
 
@@ -326,6 +416,7 @@ private:
         if (op == BSVI_OP_NAFF) {
             if (!nodes) return;
             ++visits_;
+            claim(I, e);
             if (counting_) return;
             line("{");
             line(fmt("  const float loc = %s;", affine(I.a, I.b, I.c, e).c_str()));
@@ -402,6 +493,7 @@ private:
     // ---- a model log-prob term N(value | A*B + C, S) finished in the forward sweep (elbo_kernel.hip naff_sink)
     void naff_sink(const Insn& I, uint32_t e) {
         ++visits_;
+        claim(I, e);
         const std::string loc = affine(I.a, I.b, I.c, e);
         if (sink_mode_ == 1) {      // the value alone
             line(fmt("T.f += %s * spec_naff_lp(%s, %s, %s, %s);", flit(I.imm0).c_str(), val(I.dst, e).c_str(), loc.c_str(),
@@ -539,6 +631,7 @@ private:
         return v;
     }
     void emit_forward(const Item& R) {          // forward sweep of a record; a sink also runs its reverse step here
+        next_record();
         if (!R.bracket) {
             const Insn I = insn(R.first);
             if (R.sink && (I.w0 & 0xFFu) == BSVI_OP_NAFF) { naff_sink(I, 0); return; }
@@ -555,6 +648,7 @@ private:
         }
     }
     void emit_reverse(const Item& R) {          // reverse sweep of a (non-sink) record
+        next_record();
         if (!R.bracket) { backward(insn(R.first), 0); return; }
         for (uint32_t e = R.n_elems; e-- > 0 && visits_ <= kMaxVisits;) {
             for (uint32_t j = 0; j < R.n; ++j) forward(insn(R.first + j), e, false);      // re-materialise the temps
@@ -740,6 +834,10 @@ struct Spec {
     std::vector<uint32_t> mb_geometry;                    // n x {obs_offset, batch, row_floats, dataset_size, group}
     std::string mb_defines;
     Variant mb_variant[V_COUNT];
+    // the owners' loop (V_OWNERS, one entry per parameter) compiled for one optimizer: code objects of their own, by literal - 1
+    // (opt_literal), made at the first launch that takes them from the variant's source behind "#define SPEC_OPT_LITERAL n"
+    bool lean_owners = false;
+    Variant opt_variant[2], mb_opt_variant[2];
     bool mb_launch_prepared = false;
     uint32_t launch_seq = 0;
     std::mutex mu;
@@ -757,14 +855,15 @@ static bool tiled(uint32_t n_pos, int geom) {     // SPEC_TILE (spec_prelude.h, 
     if (geom == GEOM_MANY && (!many_tile || many_waves() > 2)) return false;
     return n_pos <= 64;
 }
-static uint32_t lds_floats(uint32_t n_params, uint32_t n_uniform, uint32_t n_obs, uint32_t n_pos, uint32_t max_threads, int geom) {
-    // mirrors the SPEC_OFF_* layout of spec_prelude.h
+static uint32_t lds_floats(uint32_t n_params, uint32_t n_uniform, uint32_t n_obs, uint32_t n_pos, uint32_t max_threads, int geom, bool quads) {
+    // mirrors the SPEC_OFF_* layout of spec_prelude.h (quads: SPEC_TABLE_FLOATS of the grouped table — never more than the compact one)
     const uint32_t W = max_threads / 64;
     const uint32_t u_pad = (n_uniform + n_obs + 3) / 4 * 4, nu_pad = (n_uniform + 3) / 4 * 4;
+    const uint32_t table = quads ? ((3 * n_uniform + 3) / 4 * 4 + n_obs + 3) / 4 * 4 : u_pad + 2 * nu_pad;
     const uint32_t ws_pad = tiled(n_pos, geom) ? (n_pos + 3) / 4 * 4 + 4 : 4 * n_pos + 4;
     const uint32_t np_pad = (n_params + 3) / 4 * 4 + 4, tab = (4 * n_uniform + (2 * n_params + 1) + 2 * n_pos + 3) / 4 * 4 + 4;
     const uint32_t own = 20 * (n_params < max_threads ? n_params : max_threads), scr = 4 * (n_pos + 2) + 4;     // SPEC_OWN_WORDS
-    return u_pad + 2 * nu_pad + W * ws_pad + (2 * W + 8) + 5 * np_pad + tab + own + scr + (tiled(n_pos, geom) ? W * 64 * 68 : 0);
+    return table + W * ws_pad + (2 * W + 8) + 5 * np_pad + tab + own + scr + (tiled(n_pos, geom) ? W * 64 * 68 : 0);
 }
 
 // the switches read when a program is created (comparisons and measurements: each generates the sources as they were)
@@ -775,6 +874,8 @@ struct CreateSwitches {
                                                                     // the loss bookkeeping beside the next bodies, plain SGD as a step of its own
     bool trim = switch_on("BSVI_SPEC_TRIM");                        // the trimmed kernels (every variant; spec_prelude.h SPEC_TRIM): repeated constant entries
                                                                     // read once, no zero-add in the reverse step of an entropy-only node, idle lanes masked in the flush
+    bool quads = switch_on("BSVI_SPEC_QUADS");                      // with trim: the table's values grouped by the record that reads them, one 16-byte
+                                                                    // read per group and per four observations (every variant; spec_prelude.h SPEC_QUADS)
     bool two_pass = switch_on("BSVI_SPEC_TWO_PASS");                // long BlackBox programs run their sinks twice (Emitter)
     const char* slp = getenv("BSVI_JIT_SLP");                       // 1 / 0 forces the SLP vectorizer on / off for every program
     const char* regalloc = getenv("BSVI_JIT_REGALLOC");             // greedy / basic forces one register allocator for every program
@@ -804,10 +905,18 @@ Spec* create(const bsvi_program_desc& d, std::string& why) {
     }
     // launch bounds: a sample keeps its slot values and its noise in registers; 512 threads leave 256 registers per
     // lane, 256 threads the whole 512-entry file (MI355X_MICROARCH.md, register files)
+    // (the grouped table, if a record of the program forms a group: the lean body decides — a size, not a layout)
+    bool quads = false;
+    if (sw.trim && sw.quads) {
+        EmitOptions o = plain;
+        o.fold = sw.lean_body; o.trim = true; o.quads = true;
+        Emitter E(d, o);
+        quads = E.run(why) && E.n_quads() > 0;
+    }
     const uint32_t live = 2 * d.n_slots + (d.n_noise <= kKeepEpsRows ? d.n_noise : 0) + (d.n_uniform_grad <= kAccumulateEntries ? d.n_uniform_grad : 0) + 40;
     auto fit = [&](uint32_t threads, Geom& g) {
         g.max_threads = threads;
-        g.lds_bytes = lds_floats(d.n_params, d.n_uniform, d.n_obs, s->n_pos, threads, (int)(&g - s->geom)) * 4u;
+        g.lds_bytes = lds_floats(d.n_params, d.n_uniform, d.n_obs, s->n_pos, threads, (int)(&g - s->geom), quads) * 4u;
         return g.lds_bytes <= 160u * 1024u;
     };
     bool ok = (live <= 232 && fit(512, s->geom[GEOM_ONE])) || fit(256, s->geom[GEOM_ONE]);
@@ -828,7 +937,7 @@ Spec* create(const bsvi_program_desc& d, std::string& why) {
         const Geom& G = s->geom[gi];
         const bool diag = form == FORM_DIAGNOSTIC, old = form == FORM_PREVIOUS;
         EmitOptions o = plain;
-        o.diag = diag; o.fold = sw.lean_body && !old; o.trim = sw.trim;
+        o.diag = diag; o.fold = sw.lean_body && !old; o.trim = sw.trim; o.quads = quads;
         Emitter E(d, o);
         if (!E.run(why)) return false;
         src += "// generated by libbsvi (specialize.cpp) from a model program: do not edit\n";
@@ -860,6 +969,7 @@ Spec* create(const bsvi_program_desc& d, std::string& why) {
         // (the out-of-line transforms — exp, log, tanh, sqrt, square — are calls: programs without them compile none)
         src += fmt("#define SPEC_RARE_TRANSFORMS %d\n#define SPEC_UT_MASK 0x%xu\n", rare_transforms ? 1 : 0, ut_mask);
         if (!old) src += fmt("#define SPEC_OWN_ENTRIES %u\n", own_entries);
+        src += E.quads_defines();
         src += "#include \"spec_prelude.h\"\n";
         src += "namespace bsvi {\n";
         src += "__device__ __forceinline__ void spec_draw(const SpecBody& A, const SpecLane& T, SpecNoise& Z) {\n";
@@ -881,6 +991,7 @@ Spec* create(const bsvi_program_desc& d, std::string& why) {
         if (!generate(kBases[b].geometry, kBases[b].form, base[b])) { delete s; return nullptr; }
     }
     s->exchange_ok = true;
+    s->lean_owners = own_entries == 1;                    // (spec_main.h, SPEC_LEAN_OWNERS)
     for (int v = 0; v < V_COUNT; ++v) {
         const VariantRow& row = kVariants[v];
         if (base[row.base].empty()) continue;
@@ -950,6 +1061,8 @@ void destroy(Spec* s) {
     if (!s) return;
     for (Variant& v : s->variant) if (v.module) (void)hipModuleUnload(v.module);
     for (Variant& v : s->mb_variant) if (v.module) (void)hipModuleUnload(v.module);
+    for (Variant& v : s->opt_variant) if (v.module) (void)hipModuleUnload(v.module);
+    for (Variant& v : s->mb_opt_variant) if (v.module) (void)hipModuleUnload(v.module);
     if (s->dev) (void)hipFree(s->dev);
     delete s;
 }
@@ -1175,6 +1288,7 @@ static void store(const std::string& key, const std::vector<char>& code) {
 
 // what the last ensure_compiled of this thread did (bsvi_jit_cache_stats): tests and tools read it
 static thread_local int t_last_source = 0;      // 0 none yet, 1 hiprtc, 2 process cache, 3 disk cache
+static thread_local int t_last_opt_literal = 0; // the optimizer literal of that launch's code object (opt_literal; 0: the generic object)
 static thread_local int t_last_variant = -1;    // the kernel variant of this thread's last launch (bsvi_spec_last_variant): tests read it
 
 // the code object of a translation unit: this process's cache, the disk cache, or hiprtc (and then both caches)
@@ -1210,6 +1324,7 @@ int obtain(const std::string& text, std::vector<char>& code, std::string& log, i
 
 int last_origin() { return t_last_source; }
 int last_variant() { return t_last_variant; }
+int last_opt_literal() { return t_last_opt_literal; }
 std::string cache_directory() { return disk_cache::enabled() ? disk_cache::directory() : std::string(); }
 std::string compiler_identity() { return disk_cache::compiler_identity(); }
 
@@ -1259,6 +1374,17 @@ static Selection choose(const Spec* s, uint32_t n_local, int mode, bool diagnost
     return select(in);
 }
 
+// The optimizer a launch of the owners' loop is compiled for (spec_main.h, SPEC_OPT_LITERAL): a function of the configuration
+// and of BSVI_SPEC_OPT_LITERAL (read at every launch; 0: the generic object always) alone.
+//   1  SGD without momentum, weight decay, maximize or nesterov      2  Adam without amsgrad, weight decay or maximize
+//   0  everything else: SGD with options, Adam with options, AdamW, RMSprop, Adagrad, Adamax
+int opt_literal(const bsvi_opt_cfg* cfg) {
+    if (!cfg || !switch_on("BSVI_SPEC_OPT_LITERAL")) return 0;
+    if (cfg->kind == BSVI_OPT_SGD && cfg->momentum == 0.0f && cfg->weight_decay == 0.0f && !cfg->maximize && !cfg->nesterov) return 1;
+    if (cfg->kind == BSVI_OPT_ADAM && cfg->weight_decay == 0.0f && !cfg->amsgrad && !cfg->maximize) return 2;
+    return 0;
+}
+
 void geometry(const Spec* s, uint32_t n_local, int mode, uint32_t* n_blocks, uint32_t* n_threads, uint32_t* lds_bytes) {
     const Selection g = choose(s, n_local, mode);
     if (n_blocks) *n_blocks = g.blocks;
@@ -1291,14 +1417,27 @@ int launch(Spec* s, const bsvi_program* p, const Launch& L) {
     int v = g.variant;
     uint32_t blocks = g.blocks, threads = g.threads;
     uint32_t seq;
+    Variant* K = nullptr;                    // the code object launched: the variant's, or its form for one optimizer
+    int literal = 0;
     {
         std::lock_guard<std::mutex> lock(s->mu);
         if (gather) s->mb_launch_prepared = true;
         if (g.status != SELECT_OK) return bsvi_fail(BSVI_ERR_UNSUPPORTED, g.reason);
-        // (the single fallback: a draw-wave kernel that does not compile becomes the base kernel without the extra waves)
-        if (g.fallback_variant >= 0 && ensure_compiled(table[v]) != BSVI_OK) { v = g.fallback_variant; threads = g.fallback_threads; }
-        const int rc = ensure_compiled(table[v]);
-        if (rc) return rc;
+        // (the optimizer as a literal: a sub-key of the variant's module, compiled instead of the generic object — which is
+        //  compiled only if the literal one is not to be had)
+        if (v == V_OWNERS && L.mode == MODE_LOOP && s->lean_owners && !table[v].src.empty() && !table[v].failed && (literal = opt_literal(L.cfg)) != 0) {
+            Variant& O = (gather ? s->mb_opt_variant : s->opt_variant)[literal - 1];
+            if (O.src.empty()) O.src = fmt("#define SPEC_OPT_LITERAL %d\n", literal) + table[v].src;
+            if (ensure_compiled(O) == BSVI_OK) K = &O;
+            else literal = 0;
+        }
+        if (!K) {
+            // (the single fallback: a draw-wave kernel that does not compile becomes the base kernel without the extra waves)
+            if (g.fallback_variant >= 0 && ensure_compiled(table[v]) != BSVI_OK) { v = g.fallback_variant; threads = g.fallback_threads; }
+            const int rc = ensure_compiled(table[v]);
+            if (rc) return rc;
+            K = &table[v];
+        }
         seq = s->launch_seq++;
     }
     if (blocks > 1 && !L.workspace) return bsvi_fail(BSVI_ERR_INVALID, "workspace_dev is null");
@@ -1328,13 +1467,13 @@ int launch(Spec* s, const bsvi_program* p, const Launch& L) {
     if (blocks > 1) {
         // every workgroup of the in-kernel loop over several workgroups must be resident (workgroup 0 waits for the others in every
         // iteration): never more than the occupancy of THIS code object allows — fewer workgroups walk more chunks each
-        int per_cu = table[v].per_cu;
+        int per_cu = K->per_cu;
         if (!per_cu) {
-            if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, table[v].fn, (int)threads, 0) != hipSuccess || per_cu <= 0) {
+            if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, K->fn, (int)threads, 0) != hipSuccess || per_cu <= 0) {
                 (void)hipGetLastError();
                 per_cu = -1;                 // (no answer: the selection's register / LDS estimate stands)
             }
-            table[v].per_cu = per_cu;
+            K->per_cu = per_cu;
         }
         if (per_cu > 0 && blocks > (uint32_t)per_cu * s->n_cus) blocks = (uint32_t)per_cu * s->n_cus;
         if (L.mode == MODE_LOOP) {
@@ -1347,9 +1486,10 @@ int launch(Spec* s, const bsvi_program* p, const Launch& L) {
     }
     size_t size = sizeof A;
     void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &A, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-    const hipError_t e = hipModuleLaunchKernel(table[v].fn, blocks, 1, 1, threads, 1, 1, 0, (hipStream_t)a->stream, nullptr, config);
+    const hipError_t e = hipModuleLaunchKernel(K->fn, blocks, 1, 1, threads, 1, 1, 0, (hipStream_t)a->stream, nullptr, config);
     if (e != hipSuccess) return bsvi_fail(BSVI_ERR_HIP, std::string("hipModuleLaunchKernel (specialised kernel): ") + hipGetErrorString(e));
     t_last_variant = v;
+    t_last_opt_literal = literal;
     return BSVI_OK;
 }
 

@@ -135,6 +135,8 @@ EXPORTS = {
     "bsvi_jit_load": (C.c_int, [C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "bsvi_jit_last_origin": (C.c_int, []),
     "bsvi_spec_last_variant": (C.c_int, []),
+    "bsvi_spec_opt_literal": (C.c_int, [C.POINTER(OptCfg)]),
+    "bsvi_spec_last_opt_literal": (C.c_int, []),
     "bsvi_jit_cache_dir": (C.c_size_t, [C.c_char_p, C.c_size_t]),
     "bsvi_jit_compiler_identity": (C.c_size_t, [C.c_char_p, C.c_size_t]),
     "bsvi_program_engine": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),

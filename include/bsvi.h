@@ -428,6 +428,11 @@ int bsvi_jit_load(const char* source, size_t* code_bytes, int* origin);
 int bsvi_jit_last_origin(void);
 /* the kernel variant of this thread's last launch of a specialised kernel (specialize.cpp, Spec::variant; -1: none yet): tests */
 int bsvi_spec_last_variant(void);
+/* The optimizer the owners' training loop (variant 6) is compiled for under this configuration — a code object of its own with the
+ * kind and its on/off options as constants: 1 plain SGD, 2 plain Adam, 0 the generic object (every other configuration, and
+ * always when BSVI_SPEC_OPT_LITERAL=0, read at every launch); and what this thread's last launch took.  Host only: tests */
+int bsvi_spec_opt_literal(const bsvi_opt_cfg* cfg);
+int bsvi_spec_last_opt_literal(void);
 size_t bsvi_jit_cache_dir(char* buf, size_t capacity);
 size_t bsvi_jit_compiler_identity(char* buf, size_t capacity);
 int bsvi_program_engine(const bsvi_program* prog, uint32_t n_local, int mode, uint32_t* n_blocks, uint32_t* n_threads,
