@@ -43,6 +43,7 @@ ACTIVATIONS = dict(tanh=1, relu=2, sigmoid=3, softplus=4)
 NO_BIAS = 0xFFFFFFFF
 MAX_LAYERS = 8                                                         # BNN_MAX_LAYERS (csrc/bnn_kernel.inc)
 MIDDLE_PATHS = ("mid_gen", "upper_gen", "upper_lds", "upper_mem")      # bsvi_bnn_select::BnnMiddle (csrc/bnn_select.h)
+FIRST_LAYER_PATHS = ("per_sample", "shared")                           # bsvi_bnn_shared_first
 PREDICT_PATHS = ("global", "lds")                                      # bsvi_bnn_predict_lds
 # the families of the loc-scale regression likelihood (bsvi_bnn_set_likelihood_family): the name a refusal gives the observed variable
 LIKELIHOOD_FAMILIES = {D.DIST_NORMAL: "Normal", D.DIST_LAPLACE: "Laplace", D.DIST_CAUCHY: "Cauchy"}
@@ -61,6 +62,9 @@ class BnnProgram:
     # order of their first tensor; then `row_latent` (a byte per row, NO_LATENT for none) and `latent_uniform` [4][T] (q loc, q scale,
     # prior loc, prior scale) exist, and the noise has a row per latent behind the weights' (n_noise = n_rows + T)
     scale_latents = ()
+    # point estimates: `row_point` (a byte per row: 1 — the row is not random in the posterior, w = its q loc entry; bsvi_bnn_set_point_rows)
+    # and `point` of every entry of `tensors`; entropy_weight is 0 when every row is a point (MAP)
+    row_point = None
 
     def summary(self):
         s = dict(kind="bnn", layers=[(l["rows"], l["cols"], l["activation"]) for l in self.layers], n_rows=self.n_rows,
@@ -71,6 +75,8 @@ class BnnProgram:
             if self.family != D.DIST_NORMAL:
                 s["family"] = LIKELIHOOD_FAMILIES[self.family].lower()
         s["priors"] = {t["name"]: t.get("prior", "normal") for t in self.tensors}
+        if any(t.get("point") for t in self.tensors):
+            s["point"] = [t["name"] for t in self.tensors if t["point"]]
         if self.scale_latents:
             s["scale_latents"] = {l["name"]: [(name, b) for name, b in l["tensors"]] for l in self.scale_latents}
         return s
@@ -258,8 +264,10 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
                     scale_vars.append(t)
     scale_names = {t.name for t in scale_vars}
     q_weights = [v for v in q_random if v.name not in scale_names]
-    if not q_weights or any(v.distribution.kind != D.DIST_NORMAL for v in q_weights):
-        raise LoweringError("bnn path: the posterior must be mean-field Normal variables")
+    for v in q_weights:
+        if v.distribution.kind != D.DIST_NORMAL:
+            raise LoweringError("bnn path: the posterior must be mean-field Normal variables (or RootVariables named like the network's "
+                                "tensors: point estimates): %r is %s" % (v.name, type(v.distribution).__name__.replace("Distribution", "")))
     # the likelihood: a Categorical / Binomial(1) over logits, or — regression — an OBSERVED Normal, Laplace or Cauchy whose loc is the chain
     liks = [v for v in p_random if v.distribution.kind in (D.DIST_CATEGORICAL, D.DIST_BINOMIAL, D.DIST_BERNOULLI)
             or (v.distribution.kind in LIKELIHOOD_FAMILIES and v.is_observed)]
@@ -311,6 +319,24 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     names = [v.name for v in latents]
     if len(set(names)) != len(names):
         raise LoweringError("bnn path: a latent tensor is used by two layers")
+    # point estimates (inference.py:251-275, by name as everywhere): a RootVariable of the posterior model that carries the name of a
+    # network tensor makes that tensor a point — w = the root's value for every sample, no entropy and no log q (the reference gives a
+    # root the log-probability 0), its prior as before; learnable=False: a frozen tensor, a constant entry.  Every tensor a point: MAP
+    q_point = {v.name: v for v in q_flat if isinstance(v, RootVariable) and v.name in names}
+    read_by_q = {id(a) for v in q_random for a in v.ancestors}
+    for v in q_flat:
+        if isinstance(v, RootVariable) and v.name in scale_names:
+            raise LoweringError("bnn path: the posterior member %r is a RootVariable named like a scale latent: the posterior of a scale "
+                                "latent must be a LogNormal variable (a point estimate of a prior scale is not implemented)" % v.name)
+    for v in getattr(posterior, "_input_variables", ()):
+        if isinstance(v, RootVariable) and v.name not in names and id(v) not in read_by_q:
+            raise LoweringError("bnn path: the posterior member %r is neither a Normal variable nor a RootVariable named like a tensor of "
+                                "the network (%s)" % (v.name, ", ".join(names)))
+    for v in q_weights:
+        if v.name in q_point:
+            raise LoweringError("bnn path: the posterior holds a RootVariable and a random variable both named %r" % v.name)
+    if not q_weights and not q_point:
+        raise LoweringError("bnn path: the posterior must be mean-field Normal variables")
     # latent prior scales of the network's tensors: tensor -> (latent, multiplier); every refusal names the variable and the cause
     scale_of, taus = {}, []
     for v in latents:
@@ -319,6 +345,11 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
             scale_of[v.name] = (tau, b)
             if all(tau is not o for o in taus):
                 taus.append(tau)
+    for name in q_point:
+        if name in scale_of:
+            raise LoweringError("bnn path: the point tensor %r has a prior scale that reads the scale latent %r (a point estimate under a "
+                                "latent prior scale is not implemented: give the tensor a Normal posterior or a constant prior scale)"
+                                % (name, scale_of[name][0].name))
     for tau in taus:
         q_tau = L.q_by_name.get(tau.name)
         if tau.distribution.kind != D.DIST_LOGNORMAL:
@@ -340,7 +371,7 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
         raise LoweringError("bnn path: the model has %d scale latents, the kernels serve at most %d" % (len(taus), MAX_SCALE_LATENTS))
     others = [v for v in p_random if v is not k and v not in latents and v.distribution.kind != D.DIST_EMPIRICAL
               and all(v is not t for t in taus)]
-    if others or sorted(names + [t.name for t in taus]) != sorted(v.name for v in q_random):
+    if others or sorted(names + [t.name for t in taus]) != sorted([v.name for v in q_random] + list(q_point)):
         raise LoweringError("bnn path: every latent of the network needs a Normal posterior of the same name, and nothing else may be latent")
     for v in latents:
         # (loc / scale families on the whole real line: a Normal posterior covers their support — LogNormal, Beta and the rest do not)
@@ -402,9 +433,26 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
         order = [v for v in order if v is not Wl and v is not bl] + [Wl, head[3]] + ([bl, head[4]] if bl is not None else [])
     tensors, row0, entries = [], 0, []
     for v in order:
-        q = L.q_by_name[v.name]
-        ql, qs = row_params(q, L.q_value)
         pl, ps = row_params(v, L.p_value, scale_of[v.name][1] if v.name in scale_of else None)
+        if v.name in q_point:
+            # the q loc is the root's own entries (identity; parameters if it is learnable, else constants), the q scale the constant 0
+            # (as lower_dense): never read as a scale — `row_point` tells the kernels
+            root = q_point[v.name]      # (its value is stored behind the sample and datapoint axes, as every root's)
+            raw = tuple(int(d) for d in np.shape(root.parameter.numpy() if root.learnable else root.value))[2:]
+            if len(raw) != 2:
+                raise LoweringError("bnn path: the RootVariable %r has shape %r: the value of a tensor is a matrix [rows, cols] or a column "
+                                    "[rows, 1]" % (v.name, raw))
+            leaf = L.q_value(q_point[v.name])
+            is_param, k0 = L.uniform_entries(leaf, "identity", 0.0, 1.0)
+            ql = (is_param, k0, int(np.prod(leaf.shape)), leaf.shape)
+            _, z0 = L.const_operand(0.0)
+            qs = (False, z0, 1, (1, 1, 1))
+            for ent in (pl, ps):
+                if ent[2] > 1 and tuple(int(d) for d in ent[3]) != tuple(int(d) for d in leaf.shape):
+                    raise LoweringError("bnn path: the RootVariable %r has shape %r but the tensor it names is %r"
+                                        % (v.name, tuple(int(d) for d in leaf.shape[1:]), tuple(int(d) for d in ent[3][1:])))
+        else:
+            ql, qs = row_params(L.q_by_name[v.name], L.q_value)
         shape = tuple(int(s) for s in ql[3])
         if len(shape) != 3 or shape[0] != 1:
             raise LoweringError("bnn path: %r must be a matrix [rows, cols] or a column [rows, 1]" % v.name)
@@ -412,7 +460,8 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
         for ent in (ql, qs, pl, ps):
             if ent[2] not in (1, size):
                 raise LoweringError("bnn path: a parameter of %r has an unsupported shape" % v.name)
-        tensors.append(dict(name=v.name, row0=row0, rows=shape[1], cols=shape[2], size=size, prior=PRIOR_KINDS[v.distribution.kind]))
+        tensors.append(dict(name=v.name, row0=row0, rows=shape[1], cols=shape[2], size=size, prior=PRIOR_KINDS[v.distribution.kind],
+                            point=v.name in q_point))
         entries.append((ql, qs, pl, ps))
         row0 += size
     R = row0
@@ -482,6 +531,8 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     # the prior of every row (bsvi_bnn_set_row_priors): one kind per tensor
     kind_of = {name: kind for kind, name in PRIOR_KINDS.items()}
     prog.row_prior = np.concatenate([np.full(t["size"], kind_of[t["prior"]], dtype=np.uint8) for t in tensors])
+    # point-estimated rows (bsvi_bnn_set_point_rows): one byte per row
+    prog.row_point = np.concatenate([np.full(t["size"], 1 if t["point"] else 0, dtype=np.uint8) for t in tensors])
     prog.layers, prog.tensors, prog.n_rows = layers, tensors, R
     prog.n_features, prog.n_classes, prog.dataset_size, prog.batch_size = P, width, DS, int(ind_x.batch_size)
     prog.likelihood = lik
@@ -497,7 +548,8 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     prog.labels = np.ascontiguousarray(Ym, dtype=np.float32)
     prog.indices_name = ind_x.name
     prog.x_name, prog.likelihood_name = x_var.name, k.name       # (engine.posterior_sample: the variables a prediction is keyed by)
-    prog.lik_weight, prog.prior_weight, prog.entropy_weight = 1.0, 1.0, 1.0
+    # (every row a point: the loss is -log p(theta, minibatch), inference.MAP)
+    prog.lik_weight, prog.prior_weight, prog.entropy_weight = 1.0, 1.0, (0.0 if prog.row_point.all() else 1.0)
     prog.n_noise = R
     if taus:
         index = {t.name: i for i, t in enumerate(taus)}
@@ -572,6 +624,15 @@ class CompiledBnn:
             raise native.NativeError("bsvi_bnn_middle returned %d" % kind)
         return MIDDLE_PATHS[kind]
 
+    def first_layer_path(self):
+        """how the two products with the minibatch are taken (csrc/bnn_select.h, shared_first: from the point rows and BSVI_BNN_SHARED1
+        as they stand at the first launch or call of this): "shared" — weights1 is a point estimate, the same matrix for every sample, so
+        the first product is taken once and the second after the sum over the samples — or "per_sample" (both products per sample, as for any network)"""
+        kind = int(self.lib.bsvi_bnn_shared_first(self.handle))
+        if kind not in (0, 1):
+            raise native.NativeError("bsvi_bnn_shared_first returned %d" % kind)
+        return FIRST_LAYER_PATHS[kind]
+
     def __init__(self, joint_model, posterior_model, estimator="pathwise", device=None, program=None):
         from brancher_amd import engine
         self.device = device or engine._device()
@@ -602,6 +663,10 @@ class CompiledBnn:
             self._keep["latent_uniform"] = lu = np.ascontiguousarray(p.latent_uniform, dtype=np.uint32)
             native.check(lib.bsvi_bnn_set_scale_latents(handle, len(p.scale_latents), row_latent.ctypes.data_as(C.c_void_p), row_latent.size,
                                                         lu.ctypes.data_as(C.c_void_p)))
+        row_point = getattr(p, "row_point", None)
+        if row_point is not None and np.any(row_point):    # (without the call no row is a point)
+            row_point = np.ascontiguousarray(row_point, dtype=np.uint8)
+            native.check(lib.bsvi_bnn_set_point_rows(handle, row_point.ctypes.data_as(C.c_void_p), row_point.size))
         self._exact_data = bool(lib.bsvi_bnn_exact_data(handle))
         dev = self.device
         self.n_params = p.n_params
@@ -677,9 +742,11 @@ class CompiledBnn:
 
     def noise_from_named(self, named, n):
         """{variable name: [N, 1, rows, cols]}  ->  [n_noise, N] (the latent vector's row order; a scale latent, [N, 1, 1, 1], is row
-        n_rows + t behind the weights')"""
+        n_rows + t behind the weights'; a point tensor has no draw: its name is not asked for and its rows stay 0)"""
         out = np.zeros((self.program.n_noise, n), dtype=np.float32)
         for t in self.program.tensors:
+            if t.get("point"):
+                continue
             a = np.asarray(named[t["name"]], dtype=np.float32)
             out[t["row0"]:t["row0"] + t["size"]] = a.reshape(a.shape[0], -1).T
         for i, l in enumerate(self.program.scale_latents):
@@ -687,9 +754,10 @@ class CompiledBnn:
         return out
 
     def named_noise(self, noise, n):
-        """[n_rows, N] -> {variable name: [N, 1, rows, cols]} (what the oracle takes)"""
+        """[n_rows, N] -> {variable name: [N, 1, rows, cols]} (what the oracle takes; the point tensors, which have no draw, are left out)"""
         noise = np.asarray(noise)
-        named = {t["name"]: noise[t["row0"]:t["row0"] + t["size"]].T.reshape(n, 1, t["rows"], t["cols"]) for t in self.program.tensors}
+        named = {t["name"]: noise[t["row0"]:t["row0"] + t["size"]].T.reshape(n, 1, t["rows"], t["cols"]) for t in self.program.tensors
+                 if not t.get("point")}
         if noise.shape[0] > self.program.n_rows:          # (the draw of a training launch; `predict` reports the weights' rows alone)
             for i, l in enumerate(self.program.scale_latents):
                 named[l["name"]] = noise[self.program.n_rows + i].reshape(n, 1, 1, 1)

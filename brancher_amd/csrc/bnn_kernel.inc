@@ -42,6 +42,22 @@
 //   bnn_row_sums    per row: sum_n eps G, sum_n G, sum_n eps, sum_n eps^2 (fixed order)
 //   bnn_row_sums (its last part) / bnn_epilogue / bnn_uniform_grads / dense_param_kernel      closed-form prior and entropy terms, the value, chain rule
 // The two products carry the flops (2 x 2 N H_1 P B); everything else is elementwise or tiny and written for clarity.
+//
+// Point-estimated rows (bsvi_bnn_set_point_rows: the reference's RootVariable members of a posterior model, inference.MAP when every
+// row is one): a byte per row; a point row has w = its q loc entry for every sample, no draw, no log q, no entropy and no score term, and
+// its prior as any row of its kind.  The POINT instantiations of bnn_draw and bnn_row_sums read the byte (the normal of such a row is
+// taken as 0: every formula of the row then holds as it stands, and bnn_row_terms / bnn_row_terms_sums leave out the terms in s); the
+// Philox counters of the other rows do not move.  A model without a point row launches the instantiations it launched.
+// The shared first layer (bnn_select.h, shared_first; BSVI_BNN_SHARED1=0 switches it off): with EVERY row of weights1 a point, all samples
+// share weights1, and an iteration is
+//   bnn_head_gather, bnn_draw    as above, without the N copies of weights1 (a chunk of weights1 rows takes its prior sum once)
+//   bnn_first_shared             a1s[h][b] = sum_p x[b][p] W1[h][p], once (a wave per (b, h))
+//   bnn_first_broadcast          a1s laid out as the a1 the middle kernel reads (its text and its launch are untouched)
+//   the middle kernel            as above
+//   bnn_da1_partial / _total     dbar[h][b] = sum_n d f / d a1[(h, n)][b], a fixed order in two steps, no atomics
+//   bnn_second_shared            GT1[h][p] = sum_b dbar[h][b] x[b][p]: ONE second product, behind the sum over the samples
+//   bnn_rows_shared              weights1's row terms from GT1;  bnn_row_sums takes the other rows (quad0)
+// and the epilogue as above.  The workspace holds no copy of weights1 per sample and no per-sample GT then.
 // The text of the two generated kernels, bnn_upper_gen and bnn_mid_gen, lives in bnn_source.h (host only: tests/test_bnn_source_cpu.py
 // holds it to recorded digests without a GPU); this file fills its input (bnn_source_net) and compiles what it writes (bnn_gen_ready).
 
@@ -110,6 +126,17 @@ struct BParams {
     const uint8_t* row_latent; const uint32_t* lat_uniform; const uint32_t* lat_count;
     float* lat_l; float* lat_itau; float* lat_eps; float* lat_D; float* lat_z; float* lat_upart;
     double* lat_f; double* lat_q; double* lat_b;
+    // point-estimated rows (bsvi_bnn_set_point_rows; null: none): a byte per row, padded with 0 to a whole quad.  A row whose byte is set is
+    // not random in the posterior: w = its q loc entry for every sample, no draw, no log q and no entropy term.  Read by the POINT
+    // instantiations of bnn_draw and bnn_row_sums alone.  Behind every other member, as `family` is
+    const uint8_t* row_point;
+    // the shared first layer (bnn_select.h, shared_first; 0: both products per sample): every row of weights1 is a point row, so
+    // a1s [H1][B_pad] = W1 x is taken once (bnn_first_shared) and broadcast into a1T (bnn_first_broadcast), d f / d a1 is summed over the
+    // samples in a fixed order — dpart [n_pad / 64][H1][B_pad] the sums of 64 samples (bnn_da1_partial), dbar [H1][B_pad] theirs
+    // (bnn_da1_total) — and GT1 [H1][P] = dbar x (bnn_second_shared) goes into weights1's row terms directly (bnn_rows_shared); quad0: the
+    // first row quad bnn_row_sums still takes (R1 / 4 then, else 0)
+    uint32_t shared1, quad0;
+    float* a1s; float* dpart; float* dbar; float* GT1;
 };
 
 __device__ __forceinline__ float bnn_act(uint32_t act, float v) {
@@ -299,18 +326,45 @@ __global__ void __launch_bounds__(256) bnn_head_gather(const BParams Q, const ui
 // sample, and the wave holds u of every such row: it leaves sum_(r under t) (u psi - 1) of its chunk per latent present in the chunk (a wave
 // sum per latent, lat_upart; zero for the others), which bnn_latent_terms adds in chunk order.  (u psi - 1, not u psi: the terms are
 // centred, so the sum over 15 680 rows does not carry their count in its leading bits.)
-template <bool MIXED, bool LATENT = false>
+// POINT (with MIXED; bsvi_bnn_set_point_rows): the normal of a point row is taken as 0 whatever was drawn or handed in, so w = mu exactly,
+// the row adds nothing to the sample's log q sum and reports 0 in noise_out; its prior term is that of any row of its kind.  The Philox
+// call of a quad is the one it was: the other rows of the quad keep their normals.
+template <bool MIXED, bool LATENT = false, bool POINT = false>
 __global__ void __launch_bounds__(256) bnn_draw(const BParams Q) {
     const uint32_t chunk = blockIdx.x, lane = threadIdx.x & 63u, n = blockIdx.y * 4u + (threadIdx.x >> 6), g = chunk * 64u + lane;
     if (n >= Q.n_pad) return;
     const bool live = n < Q.n_local;
     const uint32_t quads = (Q.R + 3u) / 4u;
     float pv = 0.0f, qv = 0.0f;
+    if (POINT && !LATENT && Q.shared1 && !Q.noise_out && (chunk + 1u) * 256u <= Q.R1) {
+        // the shared first layer: every row of this chunk is a point row of weights1, so its prior sum is the same for every sample —
+        // one wave takes it and writes it to all of them (no copies of weights1 leave: the first product reads the q loc entries).
+        // (Not with scale latents: every chunk then leaves its lat_upart, zeros for a chunk of point rows, behind the sample loop below.)
+        if (blockIdx.y != 0u || threadIdx.x >= 64u) return;
+        const uint32_t kinds = *reinterpret_cast<const uint32_t*>(Q.row_kind + 4u * (size_t)g);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const size_t r = 4u * (size_t)g + j;
+            const float u = (Q.rowp[r] - Q.rowp[2 * (size_t)Q.R + r]) / Q.rowp[3 * (size_t)Q.R + r];
+            pv += bnn_prior_value((kinds >> (8 * j)) & 0xFFu, u);
+        }
+        pv = wave_sum(pv);
+        for (uint32_t m = lane; m < Q.n_pad; m += 64u) {
+            Q.pv_part[(size_t)chunk * Q.n_pad + m] = m < Q.n_local ? pv : 0.0f;
+            Q.qv_part[(size_t)chunk * Q.n_pad + m] = 0.0f;
+        }
+        return;
+    }
     float up[4] = {0.0f, 0.0f, 0.0f, 0.0f};      // LATENT: u psi - 1 of the quad's rows, and their latents (a byte per row)
     uint32_t lats = 0xFFFFFFFFu;
     if (g < quads) {
         float e[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (live) bnn_eps4(Q, n, g, e);
+        const uint32_t points = POINT ? *reinterpret_cast<const uint32_t*>(Q.row_point + 4u * (size_t)g) : 0u;      // (a byte per row)
+        if (live && !(POINT && points == 0x01010101u)) bnn_eps4(Q, n, g, e);      // (a quad of four point rows draws nothing)
+        if (POINT) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) e[j] = ((points >> (8 * j)) & 0xFFu) ? 0.0f : e[j];
+        }
         if (LATENT) lats = *reinterpret_cast<const uint32_t*>(Q.row_latent + 4u * (size_t)g);
         uint16_t hi[4] = {0, 0, 0, 0}, mid[4] = {0, 0, 0, 0}, lo[4] = {0, 0, 0, 0};
         float w4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -360,7 +414,7 @@ __global__ void __launch_bounds__(256) bnn_draw(const BParams Q) {
             if (Q.exact) dense_split3(w4[j], hi[j], mid[j], lo[j]);
         }
         const uint32_t r0 = 4u * g;
-        if (r0 < Q.R1) {                          // (P is a multiple of 4: a quad of weights1 stays in one row h)
+        if (r0 < Q.R1 && !(POINT && Q.shared1)) {      // (P is a multiple of 4: a quad of weights1 stays in one row h)
             const uint32_t h = r0 / Q.P, p = r0 - h * Q.P;
             const size_t nc = (size_t)h * Q.n_pad + n;
             if (Q.exact) {
@@ -596,7 +650,7 @@ __global__ void __launch_bounds__(256) bnn_sig_rows(const BParams Q) {
 
 // one row: gradients with respect to its four uniform entries (the formulas of dense_rows_body) and its sample-independent terms of f
 __device__ __forceinline__ void bnn_row_terms(const BParams& Q, const uint32_t r, const float ds_lik, const float dmu_lik, const float S1,
-                                              const float S2, const float N, double& hconst, double& qconst) {
+                                              const float S2, const float N, double& hconst, double& qconst, const bool point = false) {
     // (N: the number of samples, or sum_n a_n of caller-weighted gradients; S1, S2 weighted alike)
     const float mu = Q.rowp[r], s = Q.rowp[Q.R + r], mu0 = Q.rowp[2 * (size_t)Q.R + r], s0 = Q.rowp[3 * (size_t)Q.R + r];
     const float delta = mu - mu0, is2 = 1.0f / (s0 * s0);
@@ -604,7 +658,8 @@ __device__ __forceinline__ void bnn_row_terms(const BParams& Q, const uint32_t r
     const float sum_dw_e = -(delta * S1 + s * S2) * is2;                    // sum_n d log p / d W * eps
     const float sum_sq = N * delta * delta + 2.0f * delta * s * S1 + s * s * S2;   // sum_n (W - mu0)^2
     Q.rowg[r] = dmu_lik + Q.prior_weight * sum_dw;
-    Q.rowg[Q.R + r] = ds_lik + Q.prior_weight * sum_dw_e + Q.entropy_weight * N / s;
+    // (a point row: s = 0 and S1 = S2 = 0 — the closed form above holds as it stands; no entropy, no log s, no log q)
+    Q.rowg[Q.R + r] = point ? 0.0f : ds_lik + Q.prior_weight * sum_dw_e + Q.entropy_weight * N / s;
     Q.rowg[2 * (size_t)Q.R + r] = -Q.prior_weight * sum_dw;
     Q.rowg[3 * (size_t)Q.R + r] = Q.prior_weight * (sum_sq * is2 / s0 - N / s0);
     // (in double precision from the parameters on: with one scale shared by all rows — every untrained model — the single-
@@ -612,8 +667,8 @@ __device__ __forceinline__ void bnn_row_terms(const BParams& Q, const uint32_t r
     //  the sample-independent terms of f are R terms of O(1) whose sum cancels against the per-sample ones: kept in double
     //  precision from here to the per-sample f)
     const double sd = bnn_uniform_value_d(Q, Q.row_uniform[Q.R + r]), s0d = bnn_uniform_value_d(Q, Q.row_uniform[3 * (size_t)Q.R + r]);
-    hconst = (double)Q.prior_weight * (-log(s0d) - 0.91893853320467274178) + (double)Q.entropy_weight * (1.41893853320467274178 + log(sd));
-    qconst = -log(sd) - 0.91893853320467274178;
+    hconst = (double)Q.prior_weight * (-log(s0d) - 0.91893853320467274178) + (point ? 0.0 : (double)Q.entropy_weight * (1.41893853320467274178 + log(sd)));
+    qconst = point ? 0.0 : -log(sd) - 0.91893853320467274178;
 }
 
 // ... of a row without that closed form in sum eps, sum eps^2: from the per-sample sums of bnn_row_sums<true>,
@@ -626,18 +681,19 @@ __device__ __forceinline__ void bnn_row_terms(const BParams& Q, const uint32_t r
 // b_r — log p = g(u) - log b_r - l with u = (w - mu0) / (b_r tau), d log p / d b_r = -(w - mu0) t / b_r - 1 / b_r: T2's identity with b_r in
 // the place of s0, and -log b_r in the constant where -log s0 stands; the per-sample -l is the latent's (bnn_latent_terms)
 __device__ __forceinline__ void bnn_row_terms_sums(const BParams& Q, const uint32_t r, const uint32_t kind, const float ds_lik, const float dmu_lik,
-                                                   const float T0, const float T1, const float N, double& hconst, double& qconst) {
+                                                   const float T0, const float T1, const float N, double& hconst, double& qconst,
+                                                   const bool point = false) {
     const float mu = Q.rowp[r], s = Q.rowp[Q.R + r], mu0 = Q.rowp[2 * (size_t)Q.R + r], s0 = Q.rowp[3 * (size_t)Q.R + r];
     const float T2 = -((mu - mu0) * T0 + s * T1 + N) / s0;
     Q.rowg[r] = dmu_lik + Q.prior_weight * T0;
-    Q.rowg[Q.R + r] = ds_lik + Q.prior_weight * T1 + Q.entropy_weight * N / s;
+    Q.rowg[Q.R + r] = point ? 0.0f : ds_lik + Q.prior_weight * T1 + Q.entropy_weight * N / s;
     Q.rowg[2 * (size_t)Q.R + r] = -Q.prior_weight * T0;
     Q.rowg[3 * (size_t)Q.R + r] = Q.prior_weight * T2;
     // (double precision, for bnn_row_terms' reason)  Laplace: -log(2 s0); Cauchy: -log(pi) - log(s0); Normal: -log(s0) - 1/2 log 2 pi
     const double sd = bnn_uniform_value_d(Q, Q.row_uniform[Q.R + r]), s0d = bnn_uniform_value_d(Q, Q.row_uniform[3 * (size_t)Q.R + r]);
     const double pconst = kind == BSVI_DIST_LAPLACE ? -log(2.0 * s0d) : (kind == BSVI_DIST_CAUCHY ? -1.14472988584940017414 - log(s0d) : -log(s0d) - 0.91893853320467274178);
-    hconst = (double)Q.prior_weight * pconst + (double)Q.entropy_weight * (1.41893853320467274178 + log(sd));
-    qconst = -log(sd) - 0.91893853320467274178;
+    hconst = (double)Q.prior_weight * pconst + (point ? 0.0 : (double)Q.entropy_weight * (1.41893853320467274178 + log(sd)));
+    qconst = point ? 0.0 : -log(sd) - 0.91893853320467274178;
 }
 
 // per row quad (one wave, lanes = samples): sum_n eps G, sum_n G, sum_n eps, sum_n eps^2, then the rows' gradients and constants.  grid: ceil(quads / 4), block 256: a wave per quad
@@ -649,16 +705,19 @@ __device__ __forceinline__ void bnn_row_terms_sums(const BParams& Q, const uint3
 // three kinds take T0 and T1 with 1 / (b_r tau) inside the sum (the Normal: t = -u / s0) — the same eight accumulators, one load of
 // 1 / tau per sample where the quad's rows share a latent (every quad inside a tensor), else one per row; rows under no latent keep
 // what MIXED gives them.
-template <bool MIXED, bool LATENT = false>
+// POINT (with MIXED; bsvi_bnn_set_point_rows): the normal of a point row is 0 as in bnn_draw, so w = mu in the sums of its prior's kind, and
+// its row terms carry no entropy, no log s and no log q (bnn_row_terms / bnn_row_terms_sums, point); its scale gradient item is 0.
+template <bool MIXED, bool LATENT = false, bool POINT = false>
 __global__ void __launch_bounds__(256) bnn_row_sums(const BParams Q) {
-    const uint32_t quads = (Q.R + 3u) / 4u, g = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u, r0 = 4u * g;
+    const uint32_t quads = (Q.R + 3u) / 4u, g = (POINT ? Q.quad0 : 0u) + blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u, r0 = 4u * g;
     if (g >= quads) return;
     float acc[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) acc[k] = 0.0f;
     float asum = 0.0f;
     float tacc[8], rp[4][4], is0[4];
-    uint32_t kinds = 0u, lats = 0xFFFFFFFFu;
+    uint32_t kinds = 0u, lats = 0xFFFFFFFFu, points = 0u;
+    if (POINT) points = *reinterpret_cast<const uint32_t*>(Q.row_point + (size_t)r0);
     if (LATENT) lats = *reinterpret_cast<const uint32_t*>(Q.row_latent + (size_t)r0);
     const bool lat_shared = LATENT && lats == (lats & 0xFFu) * 0x01010101u, lat_any = LATENT && lats != 0xFFFFFFFFu;
     if (MIXED) {
@@ -673,8 +732,12 @@ __global__ void __launch_bounds__(256) bnn_row_sums(const BParams Q) {
         for (int j = 0; j < 4; ++j) is0[j] = 1.0f / rp[3][j];          // (once per row: the loop below multiplies)
     }
     for (uint32_t n = lane; n < Q.n_local; n += 64u) {
-        float e[4];
-        bnn_eps4(Q, n, g, e);
+        float e[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (!(POINT && points == 0x01010101u)) bnn_eps4(Q, n, g, e);      // (a quad of four point rows draws nothing)
+        if (POINT) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) e[j] = ((points >> (8 * j)) & 0xFFu) ? 0.0f : e[j];
+        }
         const float aw = Q.f_weight ? Q.f_weight[n] : 1.0f;      // (G carries a_n already: the seeds were scaled)
         asum += aw;
         float it[4] = {1.0f, 1.0f, 1.0f, 1.0f};      // LATENT: 1 / tau of the sample for the quad's rows (1 for a row under no latent)
@@ -749,13 +812,161 @@ __global__ void __launch_bounds__(256) bnn_row_sums(const BParams Q) {
             kind = (kinds >> (8u * lane)) & 0xFFu;
         }
         const bool under_latent = LATENT && ((lats >> (8u * lane)) & 0xFFu) != 0xFFu;
-        if (under_latent || (MIXED && kind != BSVI_DIST_NORMAL)) bnn_row_terms_sums(Q, r, kind, ds_lik, dmu_lik, T0, T1, Nw, hconst, qconst);
-        else bnn_row_terms(Q, r, ds_lik, dmu_lik, S1, S2, Nw, hconst, qconst);
+        const bool point = POINT && ((points >> (8u * lane)) & 0xFFu) != 0u;
+        if (under_latent || (MIXED && kind != BSVI_DIST_NORMAL)) bnn_row_terms_sums(Q, r, kind, ds_lik, dmu_lik, T0, T1, Nw, hconst, qconst, point);
+        else bnn_row_terms(Q, r, ds_lik, dmu_lik, S1, S2, Nw, hconst, qconst, point);
     }
     double h4 = 0.0, q4 = 0.0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) { h4 += __shfl(hconst, j, 64); q4 += __shfl(qconst, j, 64); }
     if (lane == 0u) { Q.hpart[g] = h4; Q.hpart[quads + g] = q4; }
+}
+
+// ---- the shared first layer (BParams::shared1): weights1 is a point estimate, the same matrix for every sample ------------------------
+// x of the minibatch at (b, p): the exact pieces' operand (bf16, exact) or the f32 one
+__device__ __forceinline__ float bnn_xb(const BParams& Q, const uint32_t b, const uint32_t p) {
+    return Q.exact ? __uint_as_float((uint32_t)Q.Xb_bf[(size_t)b * Q.Kp + p] << 16) : Q.Xb[(size_t)b * Q.P_ld + p];
+}
+
+// a1s[h][b] = sum_p x[b][p] W1[h][p], W1 the q loc entries of weights1 (rowp's first R1 floats).  f32 FMAs on exact operands, the wave's
+// partial sums joined by wave_sum: the rule of data_path() (exact bf16 data times an f32 weight, accumulated in f32) without the pieces.
+// One wave per (minibatch row, row of W1), lanes along p; consecutive waves share the minibatch row.  (With a wave per minibatch row and
+// the rows of W1 one after another, the launch was 74 us at 784-20-10 and 512 rows: 512 waves, each a chain of H1 dependent sums.)
+// grid: ceil(B_pad H1 / 4), block 256
+__global__ void __launch_bounds__(256) bnn_first_shared(const BParams Q) {
+    const uint32_t lane = threadIdx.x & 63u, w = blockIdx.x * 4u + (threadIdx.x >> 6), b = w / Q.H1, h = w - b * Q.H1;
+    if (b >= Q.B_pad) return;
+    float s = 0.0f;
+    if (b < Q.B) {
+#pragma unroll 4
+        for (uint32_t p = lane; p < Q.P; p += 64u) s = fmaf(bnn_xb(Q, b, p), Q.rowp[(size_t)h * Q.P + p], s);
+    }
+    s = wave_sum(s);
+    if (lane == 0u) Q.a1s[(size_t)h * Q.B_pad + b] = s;      // (pad rows of the minibatch: 0, as a row of zeros gives)
+}
+
+// a1s laid out as the a1 the middle kernels read: MID — bnn_mid_gen's [(h, n)][b], else [B_pad][(h, n)]; the pad samples 0, as the
+// product of their zero weights is.  One thread per four consecutive values (16-byte stores): grid: ceil(B_pad NC / 1024), block 256
+template <bool MID>
+__global__ void __launch_bounds__(256) bnn_first_broadcast(const BParams Q) {
+    const size_t i = ((size_t)blockIdx.x * 256u + threadIdx.x) * 4u;
+    if (i >= (size_t)Q.B_pad * Q.NC) return;
+    xf_f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (MID) {                                   // (B_pad is a multiple of 32: four consecutive b of one (h, n))
+        const uint32_t hn = (uint32_t)(i / Q.B_pad), b = (uint32_t)(i - (size_t)hn * Q.B_pad), h = hn / Q.n_pad, n = hn - h * Q.n_pad;
+        if (n < Q.n_local) v = *reinterpret_cast<const xf_f32x4*>(Q.a1s + (size_t)h * Q.B_pad + b);
+    } else {                                     // (n_pad is a multiple of 64: four consecutive n of one (b, h))
+        const uint32_t b = (uint32_t)(i / Q.NC), hn = (uint32_t)(i - (size_t)b * Q.NC), h = hn / Q.n_pad, n = hn - h * Q.n_pad;
+        const float a = Q.a1s[(size_t)h * Q.B_pad + b];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = n + j < Q.n_local ? a : 0.0f;
+    }
+    *reinterpret_cast<xf_f32x4*>(Q.a1T + i) = v;
+}
+
+// d f / d a1 summed over 64 samples: dpart[seg][h][b] = sum_(n in 64 seg .. 64 seg + 63, n < n_local) da1[(h, n)][b], from the operand of
+// the second product as the middle kernel left it — three bf16 pieces whose sum is the f32 value exactly, or f32.  [(h, n)][b] has b
+// fastest: a lane takes four consecutive b (8-byte loads of each piece | one 16-byte load), wave w the samples 16 w .. 16 w + 15 of the
+// segment one after another with all their loads in flight, and the four waves are joined in order: a fixed order of additions, no
+// atomics.  grid: ceil(B_pad / 256) x H1 x n_pad / 64, block 256
+__global__ void __launch_bounds__(256) bnn_da1_partial(const BParams Q) {
+    __shared__ float part[4][64][4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, b = (blockIdx.x * 64u + lane) * 4u, h = blockIdx.y, seg = blockIdx.z;
+    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (b < Q.B_pad) {
+        const size_t plane = (size_t)Q.NC * Q.B_pad;
+#pragma unroll
+        for (uint32_t k = 0; k < 16u; ++k) {
+            const uint32_t n = seg * 64u + wave * 16u + k;
+            if (n >= Q.n_local) continue;
+            const size_t at = ((size_t)h * Q.n_pad + n) * Q.B_pad + b;
+            if (Q.exact) {
+                const xf_u32x2 hi = *reinterpret_cast<const xf_u32x2*>(Q.dlogp + at), mid = *reinterpret_cast<const xf_u32x2*>(Q.dlogp + plane + at),
+                               lo = *reinterpret_cast<const xf_u32x2*>(Q.dlogp + 2 * plane + at);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t sh = (j & 1) ? 0u : 16u, w = (uint32_t)j >> 1;      // (element j: the low half of word j / 2 first)
+                    const float v = (__uint_as_float((hi[w] << sh) & 0xFFFF0000u) + __uint_as_float((mid[w] << sh) & 0xFFFF0000u))
+                                    + __uint_as_float((lo[w] << sh) & 0xFFFF0000u);
+                    acc[j] += v;
+                }
+            } else {
+                const xf_f32x4 v = *reinterpret_cast<const xf_f32x4*>(Q.da1T + at);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[j] += v[j];
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) part[wave][lane][j] = acc[j];
+    __syncthreads();
+    if (wave == 0u && b < Q.B_pad) {
+        xf_f32x4 v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = (part[0][lane][j] + part[1][lane][j]) + (part[2][lane][j] + part[3][lane][j]);
+        *reinterpret_cast<xf_f32x4*>(Q.dpart + ((size_t)seg * Q.H1 + h) * Q.B_pad + b) = v;
+    }
+}
+
+// ... and the segments in order: dbar[h][b].  grid: ceil(H1 B_pad / 256), block 256
+__global__ void __launch_bounds__(256) bnn_da1_total(const BParams Q) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x, n_hb = Q.H1 * Q.B_pad;
+    if (i >= n_hb) return;
+    float s = 0.0f;
+    for (uint32_t seg = 0; seg < Q.n_pad / 64u; ++seg) s += Q.dpart[(size_t)seg * n_hb + i];
+    Q.dbar[i] = s;
+}
+
+// GT1[h][p] = sum_b dbar[h][b] x[b][p]: sum_n of the per-sample second product, taken after the sum over the samples.  Lanes along p, the
+// sixteen waves of a workgroup take a slice of the minibatch each and are joined in order.  grid: ceil(P / 64) x H1, block 1024
+__global__ void __launch_bounds__(1024) bnn_second_shared(const BParams Q) {
+    __shared__ float part[16][64];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, p = blockIdx.x * 64u + lane, h = blockIdx.y;
+    const uint32_t per = (Q.B + 15u) / 16u, b0 = wave * per, b1 = min(b0 + per, Q.B);
+    float s = 0.0f;
+    if (p < Q.P) {
+#pragma unroll 8
+        for (uint32_t b = b0; b < b1; ++b) s = fmaf(Q.dbar[(size_t)h * Q.B_pad + b], bnn_xb(Q, b, p), s);
+    }
+    part[wave][lane] = s;
+    __syncthreads();
+    if (wave == 0u && p < Q.P) {
+        float t = 0.0f;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) t += part[w][lane];
+        Q.GT1[(size_t)h * Q.P + p] = t;
+    }
+}
+
+// the row terms of weights1 from GT1: what bnn_row_sums leaves for a quad of point rows, without a loop over the samples — sum_n G is
+// GT1, every sum with eps is 0, and the prior's per-sample t is the same for every sample (T0 = N t, T1 = 0).  One thread per row of
+// weights1; the constants of a quad's four rows (P is a multiple of 4: four lanes of one wave) are added in row order.
+// grid: ceil(R1 / 256), block 256
+__global__ void __launch_bounds__(256) bnn_rows_shared(const BParams Q) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u, quads = (Q.R + 3u) / 4u;
+    double hconst = 0.0, qconst = 0.0;
+    if (r < Q.R1) {
+        float Nw = (float)Q.n_local;
+        if (Q.f_weight) {
+            Nw = 0.0f;
+            for (uint32_t n = 0; n < Q.n_local; ++n) Nw += Q.f_weight[n];
+        }
+        const uint32_t kind = Q.row_kind[r];
+        const float G = Q.GT1[r];
+        if (kind != BSVI_DIST_NORMAL) {
+            const float is0 = 1.0f / Q.rowp[3 * (size_t)Q.R + r], dw = Q.rowp[r] - Q.rowp[2 * (size_t)Q.R + r], u = dw * is0;
+            const float sg = dw > 0.0f ? 1.0f : (dw < 0.0f ? -1.0f : 0.0f);
+            const float t = (kind == BSVI_DIST_LAPLACE ? -sg : -2.0f * u / (1.0f + u * u)) * is0;
+            bnn_row_terms_sums(Q, r, kind, 0.0f, G, Nw * t, 0.0f, Nw, hconst, qconst, true);
+        } else {
+            bnn_row_terms(Q, r, 0.0f, G, 0.0f, 0.0f, Nw, hconst, qconst, true);
+        }
+        Q.sums[r] = 0.0f; Q.sums[(size_t)Q.R + r] = G; Q.sums[2 * (size_t)Q.R + r] = 0.0f; Q.sums[3 * (size_t)Q.R + r] = 0.0f;
+    }
+    double h4 = 0.0, q4 = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { h4 += __shfl(hconst, (int)(lane & ~3u) + j, 64); q4 += __shfl(qconst, (int)(lane & ~3u) + j, 64); }
+    if ((lane & 3u) == 0u && r < Q.R1) { Q.hpart[r / 4u] = h4; Q.hpart[quads + r / 4u] = q4; }
 }
 
 // latent prior scales, one thread per sample: the chunks' sums of u psi - 1 in chunk order, then per latent, with z = (l - m0) / s0,
@@ -936,6 +1147,13 @@ struct bsvi_bnn {
     void* lat_blob = nullptr;
     const uint8_t* row_latent = nullptr; const uint32_t* lat_uniform = nullptr; const uint32_t* lat_count = nullptr;
     std::vector<uint32_t> row_uniform_host;      // [4][R], kept for that call
+    // point-estimated rows (bsvi_bnn_set_point_rows; null: none): a byte per row in a blob of its own; the POINT instantiations of
+    // bnn_draw / bnn_row_sums
+    uint8_t* row_point = nullptr;
+    std::vector<uint8_t> row_point_host;
+    // the shared first layer (bnn_select.h, shared_first): 0 not asked yet, 1 shared, -1 both products per sample.  Decided once, from
+    // the point rows and BSVI_BNN_SHARED1 as they stand when the workspace is sized or the first launch is made (bnn_shared_first)
+    mutable std::atomic<int> shared_state{0};
     mutable std::atomic<bool> launched{false};      // a launch was made: the priors stay as they are
     uint64_t act_floats = 0, delta_floats = 0;      // per (sample, minibatch row)
     uint32_t act_off[BNN_MAX_LAYERS] = {};
@@ -979,6 +1197,17 @@ static bsvi_bnn_source::Net bnn_source_net(const bsvi_bnn* p) {
     const char* e = getenv("BSVI_BNN_CAUCHY_LOG");
     N.cauchy_log1p = e && !strcmp(e, "log1p");
     return N;
+}
+
+// does weights1 take the shared first layer?  (the switch is read where BSVI_BNN_MID is: at the first question, and kept)
+static bool bnn_shared_first(const bsvi_bnn* p) {
+    int st = p->shared_state.load();
+    if (!st) {
+        const char* e = getenv("BSVI_BNN_SHARED1");
+        st = bsvi_bnn_select::shared_first(p->row_point ? p->row_point_host.data() : nullptr, p->R1, e && e[0] == '0') ? 1 : -1;
+        p->shared_state.store(st);
+    }
+    return st > 0;
 }
 
 static size_t bnn_mid_lds_bytes(const bsvi_bnn* p) { return bsvi_bnn_select::mid_lds_bytes(p->Rs, p->act_floats, p->B_pad); }
@@ -1250,16 +1479,50 @@ extern "C" int bsvi_bnn_set_scale_latents(bsvi_bnn* p, uint32_t n_latents, const
     return BSVI_OK;
 }
 
+// point-estimated rows (include/bsvi.h).  Before the first launch only: the launches choose their instantiations of bnn_draw /
+// bnn_row_sums from what stands here.  A call whose bytes are all 0 leaves the handle as it was made: the kernels of a model without points
+extern "C" int bsvi_bnn_set_point_rows(bsvi_bnn* p, const uint8_t* row_point, uint32_t n_rows) {
+    if (!p || !row_point) return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_point_rows: null argument");
+    if (n_rows != p->R) return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_point_rows: n_rows is not the model's number of rows");
+    if (p->launched.load()) return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_point_rows: the model was launched already (set the point rows before the first launch)");
+    bool any = false;
+    for (uint32_t r = 0; r < n_rows; ++r) {
+        if (row_point[r] > 1u) return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_point_rows: a byte is 0 (a random row) or 1 (a point row)");
+        // (the q scale of a point row is never read as a scale: an entry with a gradient there would take the score term's -f / s)
+        if (row_point[r] && p->row_uniform_host[(size_t)p->R + r] < p->d.n_uniform_grad)
+            return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_point_rows: the q scale entry of a point row must be a constant");
+        any = any || row_point[r] != 0u;
+    }
+    if (p->row_point) { (void)hipFree(p->row_point); p->row_point = nullptr; }
+    p->row_point_host.clear();
+    p->shared_state.store(0);
+    if (!any) return BSVI_OK;
+    std::vector<uint8_t> bytes(((size_t)n_rows + 3) / 4 * 4, (uint8_t)0u);      // (the pad bytes of the last quad: no point)
+    memcpy(bytes.data(), row_point, n_rows);
+    void* blob = nullptr;
+    hipError_t e = hipMalloc(&blob, bytes.size());
+    if (e == hipSuccess) e = hipMemcpy(blob, bytes.data(), bytes.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { if (blob) (void)hipFree(blob); return fail(BSVI_ERR_HIP, std::string("bsvi_bnn_set_point_rows: ") + hipGetErrorString(e)); }
+    p->row_point = (uint8_t*)blob;
+    p->row_point_host.assign(row_point, row_point + n_rows);
+    return BSVI_OK;
+}
+
 extern "C" void bsvi_bnn_destroy(bsvi_bnn* p) {
     if (!p) return;
     if (p->dev_blob) (void)hipFree(p->dev_blob);
     if (p->lat_blob) (void)hipFree(p->lat_blob);
+    if (p->row_point) (void)hipFree(p->row_point);
     if (p->upper_gen.module) (void)hipModuleUnload(p->upper_gen.module);
     if (p->mid_gen.module) (void)hipModuleUnload(p->mid_gen.module);
     delete p;
 }
 
 extern "C" int bsvi_bnn_exact_data(const bsvi_bnn* p) { return (p && p->exact) ? 1 : 0; }
+
+// 1: the launches of this handle take the shared first layer (every row of weights1 a point row, BSVI_BNN_SHARED1 not 0); 0: both
+// products per sample; -1 for a null handle
+extern "C" int bsvi_bnn_shared_first(const bsvi_bnn* p) { return p ? (bnn_shared_first(p) ? 1 : 0) : -1; }
 
 // the middle kernel the next launch runs (bnn_launch asks the same questions in the same order): the generated kernels are compiled here
 // as a launch would compile them, and one that did not compile reports what serves in its place
@@ -1270,17 +1533,23 @@ extern "C" int bsvi_bnn_middle(const bsvi_bnn* p) {
     return p->upper_lds ? bsvi_bnn_select::UPPER_LDS : bsvi_bnn_select::UPPER_MEM;
 }
 
-// the <MIXED, LATENT> instantiation a handle's launches take: latent prior scales (Q.n_latents; a predict call fills none: its draw
+// the <MIXED, LATENT, POINT> instantiation a handle's launches take: point rows (Q.row_point; with or without latents), else latent prior scales (Q.n_latents; a predict call fills none: its draw
 // takes no prior), else some row's prior Laplace or Cauchy, else the all-Normal kernels
 static void bnn_launch_draw(const bsvi_bnn* p, const BParams& Q, const uint32_t row_chunks, hipStream_t s) {
     const dim3 grid(row_chunks, (Q.n_pad + 3u) / 4u);
-    if (Q.n_latents) hipLaunchKernelGGL((bnn_draw<true, true>), grid, dim3(256), 0, s, Q);
+    if (Q.row_point && Q.n_latents) hipLaunchKernelGGL((bnn_draw<true, true, true>), grid, dim3(256), 0, s, Q);
+    else if (Q.row_point) hipLaunchKernelGGL((bnn_draw<true, false, true>), grid, dim3(256), 0, s, Q);
+    else if (Q.n_latents) hipLaunchKernelGGL((bnn_draw<true, true>), grid, dim3(256), 0, s, Q);
     else if (p->mixed) hipLaunchKernelGGL(bnn_draw<true>, grid, dim3(256), 0, s, Q);
     else hipLaunchKernelGGL(bnn_draw<false>, grid, dim3(256), 0, s, Q);
 }
 static void bnn_launch_row_sums(const bsvi_bnn* p, const BParams& Q, hipStream_t s) {
-    const dim3 grid(((Q.R + 3) / 4 + 3) / 4);
-    if (Q.n_latents) hipLaunchKernelGGL((bnn_row_sums<true, true>), grid, dim3(256), 0, s, Q);
+    const uint32_t n_quads = (Q.R + 3) / 4 - Q.quad0;      // (the shared first layer: weights1's quads are bnn_rows_shared's)
+    if (!n_quads) return;
+    const dim3 grid((n_quads + 3) / 4);
+    if (Q.row_point && Q.n_latents) hipLaunchKernelGGL((bnn_row_sums<true, true, true>), grid, dim3(256), 0, s, Q);
+    else if (Q.row_point) hipLaunchKernelGGL((bnn_row_sums<true, false, true>), grid, dim3(256), 0, s, Q);
+    else if (Q.n_latents) hipLaunchKernelGGL((bnn_row_sums<true, true>), grid, dim3(256), 0, s, Q);
     else if (p->mixed) hipLaunchKernelGGL(bnn_row_sums<true>, grid, dim3(256), 0, s, Q);
     else hipLaunchKernelGGL(bnn_row_sums<false>, grid, dim3(256), 0, s, Q);
 }
@@ -1289,6 +1558,7 @@ struct BnnLayout {
     size_t rowp, idx, lab, Xb, Xb_bf, XbT_bf, W1f, Wp, Wsm, a1T, acts, deltas, liknb, da1T, dlogp, GT, gsm, lik, pv, qv, sums, rowg, hpart, partial, fs, total;
     size_t sigt, gsig, gsd;
     size_t lat_l, lat_itau, lat_eps, lat_D, lat_z, lat_upart, lat_f, lat_q, lat_b;
+    size_t a1s, dpart, dbar, GT1;
     uint32_t n_pad, NC, row_chunks, row_blocks;
 };
 static BnnLayout bnn_layout(const bsvi_bnn* p, uint32_t n_local) {
@@ -1305,12 +1575,15 @@ static BnnLayout bnn_layout(const bsvi_bnn* p, uint32_t n_local) {
     L.lab = take(((size_t)p->B_pad * p->LC + (p->d.likelihood == BSVI_LIK_NORMAL ? 2u * (size_t)p->C : 0u)) * 4);
     L.Xb = take(p->exact ? 0 : (size_t)p->B_pad * p->P_ld * 4);
     L.Xb_bf = take(p->exact ? (size_t)p->B_pad * p->Kp * 2 : 0); L.XbT_bf = take(p->exact ? (size_t)p->P * p->B_pad * 2 : 0);
-    L.W1f = take(p->exact ? 0 : (size_t)L.NC * p->P_ld * 4); L.Wp = take(p->exact ? 3 * (size_t)L.NC * p->Kp * 2 : 0);
+    // (the shared first layer keeps no per-sample copies of weights1 and no per-sample second product: its four small arrays stand
+    //  behind everything else)
+    const bool shared = bnn_shared_first(p);
+    L.W1f = take(p->exact || shared ? 0 : (size_t)L.NC * p->P_ld * 4); L.Wp = take(p->exact && !shared ? 3 * (size_t)L.NC * p->Kp * 2 : 0);
     L.Wsm = take((size_t)L.n_pad * (p->Rs ? p->Rs : 1) * 4);
     L.a1T = take((size_t)p->B_pad * L.NC * 4);
     L.acts = take(nb * p->act_floats * 4); L.deltas = take(nb * p->delta_floats * 4); L.liknb = take(nb * 4);
     L.da1T = take(p->exact ? 0 : (size_t)L.NC * p->B_pad * 4); L.dlogp = take(p->exact ? 3 * (size_t)L.NC * p->B_pad * 2 : 0);
-    L.GT = take(p->exact ? (size_t)p->P * L.NC * 4 : (size_t)L.NC * p->P_ld * 4);
+    L.GT = take(shared ? 0 : p->exact ? (size_t)p->P * L.NC * 4 : (size_t)L.NC * p->P_ld * 4);
     L.gsm = take((size_t)L.n_pad * (p->Rs ? p->Rs : 1) * 4); L.lik = take((size_t)L.n_pad * 4);
     L.pv = take((size_t)L.row_chunks * L.n_pad * 4); L.qv = take((size_t)L.row_chunks * L.n_pad * 4);
     L.sums = take(4 * (size_t)p->R * 4); L.rowg = take(4 * ((size_t)p->R + p->n_latents) * 4); L.hpart = take(2 * (size_t)L.row_blocks * 8);
@@ -1323,6 +1596,10 @@ static BnnLayout bnn_layout(const bsvi_bnn* p, uint32_t n_local) {
         L.lat_l = take(tn); L.lat_itau = take(tn); L.lat_eps = take(tn); L.lat_D = take(tn); L.lat_z = take(tn);
         L.lat_upart = take((size_t)L.row_chunks * tn);
         L.lat_f = take((size_t)L.n_pad * 8); L.lat_q = take((size_t)L.n_pad * 8); L.lat_b = take((size_t)L.n_pad * 8);
+    }
+    if (shared) {
+        const size_t hb = (size_t)p->H1 * p->B_pad * 4;
+        L.a1s = take(hb); L.dpart = take((size_t)(L.n_pad / 64u) * hb); L.dbar = take(hb); L.GT1 = take((size_t)p->R1 * 4);
     }
     L.total = o + 256;
     return L;
@@ -1380,7 +1657,11 @@ static int bnn_fill(const bsvi_bnn* p, const bsvi_bnn_args* a, BParams& Q, BnnLa
     Q.sums = (float*)(ws + L.sums); Q.rowg = (float*)(ws + L.rowg); Q.hpart = (double*)(ws + L.hpart); Q.partial = (float*)(ws + L.partial);
     Q.fs = (float*)(ws + L.fs); Q.row_chunks = L.row_chunks;
     if (p->scale_learn) { Q.sigt = (float*)(ws + L.sigt); Q.gsig = (float*)(ws + L.gsig); Q.gsd = (double*)(ws + L.gsd); }
-    Q.row_kind = p->row_kind;
+    Q.row_kind = p->row_kind; Q.row_point = p->row_point;
+    if (bnn_shared_first(p)) {
+        Q.shared1 = 1u; Q.quad0 = p->R1 / 4u;
+        Q.a1s = (float*)(ws + L.a1s); Q.dpart = (float*)(ws + L.dpart); Q.dbar = (float*)(ws + L.dbar); Q.GT1 = (float*)(ws + L.GT1);
+    }
     if (p->n_latents) {
         Q.n_latents = p->n_latents; Q.row_latent = p->row_latent; Q.lat_uniform = p->lat_uniform; Q.lat_count = p->lat_count;
         Q.lat_l = (float*)(ws + L.lat_l); Q.lat_itau = (float*)(ws + L.lat_itau); Q.lat_eps = (float*)(ws + L.lat_eps);
@@ -1399,7 +1680,15 @@ static int bnn_launch(const bsvi_bnn* p, const BParams& Q, const BnnLayout& L, h
     bnn_launch_draw(p, Q, L.row_chunks, s);
     int rc;
     const bool mid = bnn_gen_ready(p, true);
-    if (mid) rc = bsvi_xgemm_nt_t(Q.Xb_bf, nullptr, Q.Wp, (long)Q.NC * Q.Kp, Q.a1T, (int)Q.B_pad, (int)Q.B_pad, (int)Q.NC, (int)Q.Kp, s);      // a1 as [(h, n)][b]
+    if (Q.shared1) {
+        // weights1 is the same for every sample: the first product once, broadcast in the layout the middle kernel reads
+        rc = BSVI_OK;
+        hipLaunchKernelGGL(bnn_first_shared, dim3((Q.B_pad * Q.H1 + 3u) / 4u), dim3(256), 0, s, Q);
+        const dim3 bgrid((uint32_t)(((size_t)Q.B_pad * Q.NC / 4u + 255u) / 256u));
+        if (mid) hipLaunchKernelGGL(bnn_first_broadcast<true>, bgrid, dim3(256), 0, s, Q);
+        else hipLaunchKernelGGL(bnn_first_broadcast<false>, bgrid, dim3(256), 0, s, Q);
+    }
+    else if (mid) rc = bsvi_xgemm_nt_t(Q.Xb_bf, nullptr, Q.Wp, (long)Q.NC * Q.Kp, Q.a1T, (int)Q.B_pad, (int)Q.B_pad, (int)Q.NC, (int)Q.Kp, s);      // a1 as [(h, n)][b]
     else if (Q.exact) rc = bsvi_xgemm_nt(Q.Xb_bf, nullptr, Q.Wp, (long)Q.NC * Q.Kp, Q.a1T, (int)Q.NC, (int)Q.B_pad, (int)Q.NC, (int)Q.Kp, s);
     else rc = bsvi_gemm_f32(0, Q.Xb, (int)Q.P_ld, Q.W1f, (int)Q.P_ld, Q.a1T, (int)Q.NC, (int)Q.B_pad, (int)Q.NC, (int)Q.P, s);
     if (rc) return rc;
@@ -1434,7 +1723,15 @@ static int bnn_launch(const bsvi_bnn* p, const BParams& Q, const BnnLayout& L, h
         hipLaunchKernelGGL(bnn_lik, dim3(Q.n_pad / 64), dim3(256), 0, s, Q);
         if (Q.scale_learn) hipLaunchKernelGGL(bnn_sig_rows, dim3(Q.n_pad / 64, Q.C), dim3(256), 0, s, Q);
     }
-    if (Q.exact) rc = bsvi_xgemm_nt(Q.XbT_bf, nullptr, Q.dlogp, (long)Q.NC * Q.B_pad, Q.GT, (int)Q.NC, (int)Q.P, (int)Q.NC, (int)Q.B_pad, s);
+    if (Q.shared1) {
+        // the sum over the samples first (two steps, a fixed order), then ONE second product, and weights1's row terms from it
+        hipLaunchKernelGGL(bnn_da1_partial, dim3((Q.B_pad + 255u) / 256u, Q.H1, Q.n_pad / 64u), dim3(256), 0, s, Q);
+        hipLaunchKernelGGL(bnn_da1_total, dim3((Q.H1 * Q.B_pad + 255u) / 256u), dim3(256), 0, s, Q);
+        hipLaunchKernelGGL(bnn_second_shared, dim3((Q.P + 63u) / 64u, Q.H1), dim3(1024), 0, s, Q);
+        hipLaunchKernelGGL(bnn_rows_shared, dim3((Q.R1 + 255u) / 256u), dim3(256), 0, s, Q);
+        rc = BSVI_OK;
+    }
+    else if (Q.exact) rc = bsvi_xgemm_nt(Q.XbT_bf, nullptr, Q.dlogp, (long)Q.NC * Q.B_pad, Q.GT, (int)Q.NC, (int)Q.P, (int)Q.NC, (int)Q.B_pad, s);
     else rc = bsvi_gemm_f32(1, Q.da1T, (int)Q.B_pad, Q.Xb, (int)Q.P_ld, Q.GT, (int)Q.P_ld, (int)Q.NC, (int)Q.P, (int)Q.B_pad, s);
     if (rc) return rc;
     bnn_launch_row_sums(p, Q, s);
@@ -1789,7 +2086,7 @@ extern "C" int bsvi_bnn_predict(const bsvi_bnn* p, const bsvi_bnn_predict_args* 
     Q.pv_part = (float*)(ws + L.part); Q.qv_part = Q.pv_part + (size_t)L.row_chunks * L.n_pad;
     Q.Xb = (float*)(ws + L.X); Q.Xb_bf = (uint16_t*)(ws + L.X);
     Q.row_chunks = L.row_chunks;
-    Q.row_kind = p->row_kind;
+    Q.row_kind = p->row_kind; Q.row_point = p->row_point;
     p->launched.store(true);
 
     BnnPredict V;

@@ -40,6 +40,17 @@ inline BnnMiddle middle(uint32_t Rs, uint64_t act_floats, uint32_t B_pad, bool e
     return upper_lds_bytes(Rs, act_floats) <= LDS_LIMIT ? UPPER_LDS : UPPER_MEM;
 }
 
+// ---- the first layer of a network whose weights1 is a point estimate (bsvi_bnn_set_point_rows): every sample then sees the same
+// weights1, so the first product is taken once and broadcast, and the second after the sum over the samples ("shared"); else both
+// products run per sample as for any network.  row_point: the point byte of every row (null: no row is a point), of which the first
+// R1 = H1 P are weights1's; shared_off: BSVI_BNN_SHARED1=0.  b1 and every other tensor may be anything.
+inline bool shared_first(const uint8_t* row_point, uint32_t R1, bool shared_off) {
+    if (shared_off || !row_point || !R1) return false;
+    for (uint32_t r = 0; r < R1; ++r)
+        if (!row_point[r]) return false;
+    return true;
+}
+
 // ---- the posterior-predictive pass (bsvi_bnn_predict): forward only, so a thread keeps TWO activation buffers of the widest layer
 // (ping-pong) instead of every layer's activations and deltas.  max_width: the widest layer's output (the largest layers[l].rows).
 // bnn_predict_fwd<true>: the staging tile [Rs][65] of the workgroup's 64 samples, then the two buffers [2 max_width][256]

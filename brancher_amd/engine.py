@@ -1381,8 +1381,11 @@ def _bnn_posterior_sample(model, compiled, number_samples, input_values):
     loc, scale = bnn.row_parameters(p, compiled.params.detach().cpu().numpy())
     eps = res["noise"].cpu().numpy()
     weights = (loc.astype(np.float32)[:, None] + scale.astype(np.float32)[:, None] * eps).astype(np.float32)
-    for name, value in compiled.named_noise(weights, N).items():
-        out[by_name[name]] = torch.from_numpy(np.ascontiguousarray(value)).to(dev)
+    # (every tensor, the point estimates too — the scale of their rows is 0, so their sample is the root's value for every sample, as the
+    #  reference tiles it; `named_noise` leaves them out: they have no draw)
+    for t in p.tensors:
+        value = weights[t["row0"]:t["row0"] + t["size"]].T.reshape(N, 1, t["rows"], t["cols"])
+        out[by_name[t["name"]]] = torch.from_numpy(np.ascontiguousarray(value)).to(dev)
     # the roots above the likelihood, not looking past a variable the caller gave
     seen, stack = set(), [lik_var]
     while stack:

@@ -857,10 +857,28 @@ def _bnn_features(rng, data, dataset_size, n_features):
     raise ValueError("data is 'integers' or 'normal'")
 
 
+def _bnn_posterior(api, point, names):
+    """the posterior member of a network tensor: its mean-field Normal, or — the tensor named in `point` (a tuple of tensor names, or
+    "all") — a learnable RootVariable of the same name whose value is what the Normal's loc would have been: a point estimate
+    (`inference.MAP` when every tensor is one).  A name that is no tensor of the network is refused."""
+    if isinstance(point, str) and point != "all":
+        raise ValueError("point is a tuple of tensor names or \"all\"")
+    chosen = set(names) if point == "all" else set(point)
+    unknown = sorted(chosen - set(names))
+    if unknown:
+        raise ValueError("point names %s: the tensors of this network are %s" % (", ".join(unknown), ", ".join(names)))
+
+    def member(loc, scale, name):
+        if name in chosen:
+            return api.RootVariable(loc, name, learnable=True)
+        return api.NormalVariable(loc, scale, name, learnable=True)
+    return member
+
+
 def build_bayesian_neural_network(api, dataset_size=48, batch_size=30, n_features=784, n_hidden=20, n_classes=10, seed=0,
                                   prior_scale=10., q_scale=0.2, q_scale1=None, q_loc_scale=0.0, pixels="uint8",
                                   activation="tanh", hidden2=0, widths=None, activations=None, teacher=None, prior="normal", prior_loc=0.,
-                                  scale_latent=None, scale_latent_prior=(0., 1.), scale_latent_q=None):
+                                  scale_latent=None, scale_latent_prior=(0., 1.), scale_latent_q=None, point=()):
     """`tests/test_MNIST_bayesian_neural_network.py:20-60` of the reference: a one-hidden-layer network whose weight matrices AND
     biases are latent — weights1 [H, P], b1 [H, 1], weights2 [C, H], b2 [C, 1], priors N(0, 10), a mean-field Normal posterior
     over all four (scale 0.2) — `tanh(matmul(weights1, x) + b1)`, `matmul(weights2, hidden) + b2` as the logits of an observed
@@ -878,9 +896,13 @@ def build_bayesian_neural_network(api, dataset_size=48, batch_size=30, n_feature
     by tensor name ("weights1", "b1", ...: the tensors it leaves out are Normal); its parameters are then constants of the model under
     names of their own (`_bnn_prior`).  scale_latent: None | "layer" | "global" | a dict from latent name to tensor names — a
     hierarchical prior whose scales are LogNormal latents with a learnable LogNormal posterior (`_bnn_scale_latents`, `_bnn_prior`;
-    scale_latent_prior / scale_latent_q: their (loc, scale)).  Without these keywords every model is built draw for draw as before."""
+    scale_latent_prior / scale_latent_q: their (loc, scale)).  point: a tuple of tensor names, or "all" — those tensors are point
+    estimates: their posterior member is a learnable RootVariable of the tensor's name, starting at what the Normal's loc would have been
+    (with the default q_loc_scale = 0: zeros), so a deterministic trunk under a Bayesian last layer is point=("weights1", "b1") and
+    "all" is the network trained by `inference.MAP`.  Without these keywords every model is built draw for draw as before."""
     BF = api.BF
     n_features, n_classes, widths = _bnn_widths(widths, n_features, [n_hidden] + ([hidden2] if hidden2 else []), n_classes)
+    posterior_of = _bnn_posterior(api, point, [t % l for l in range(1, len(widths)) for t in ("weights%d", "b%d")])
     prior_of = _bnn_prior(api, prior, prior_loc, prior_scale, scale_latent, scale_latent_prior, scale_latent_q,
                           [t % l for l in range(1, len(widths)) for t in ("weights%d", "b%d")])
     if pixels in ("integers", "normal"):
@@ -907,10 +929,8 @@ def build_bayesian_neural_network(api, dataset_size=48, batch_size=30, n_feature
         pre = BF.matmul(w, layer) + b
         layer = getattr(BF, acts[l - 1])(pre) if l + 1 < len(widths) else pre
         sw = q_scale1 if (l == 1 and q_scale1 is not None) else q_scale
-        q_vars.append(api.NormalVariable(q_loc_scale * q_scale * rng.normal(0., 1., (rows, 1)), q_scale * np.ones((rows, 1)),
-                                         "b%d" % l, learnable=True))
-        q_vars.append(api.NormalVariable(q_loc_scale * sw * rng.normal(0., 1., (rows, cols)), sw * np.ones((rows, cols)),
-                                         "weights%d" % l, learnable=True))
+        q_vars.append(posterior_of(q_loc_scale * q_scale * rng.normal(0., 1., (rows, 1)), q_scale * np.ones((rows, 1)), "b%d" % l))
+        q_vars.append(posterior_of(q_loc_scale * sw * rng.normal(0., 1., (rows, cols)), sw * np.ones((rows, cols)), "weights%d" % l))
     # (n_classes = 1: a Bernoulli likelihood on one logit, `BinomialVariable(1, logits=...)` as in
     #  examples/minibatch_logistic_regression.py:27 — the labels are then 0 / 1)
     k = api.CategoricalVariable(logits=layer, name="k") if n_classes > 1 else api.BinomialVariable(1, logits=layer, name="k")
@@ -924,7 +944,7 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
                          sigma=0.5, data="integers", bias=True, seed=0, prior_scale=2., q_scale=0.1, q_scale1=None, q_loc_scale=0.5,
                          widths=None, activations=None, learnable_sigma=False, sigma_init=None, prior="normal", prior_loc=0.,
                          scale_head=None, scale_floor=0.05, likelihood="normal", scale_latent=None, scale_latent_prior=(0., 1.),
-                         scale_latent_q=None):
+                         scale_latent_q=None, point=()):
     """The regression model of the Bayesian-neural-network family: the network of `build_bayesian_neural_network` (latent weight
     matrices and biases under a mean-field Normal posterior) as the loc of an observed Normal,
     `y ~ NormalVariable(matmul(weights2, act(matmul(weights1, x) + b1)) + b2, sigma)`, the targets [DS, C, 1] an EmpiricalVariable that
@@ -944,6 +964,7 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
     are not used.  likelihood: "normal", "laplace" (median / L1 regression: an observed `LaplaceVariable`) or "cauchy" (the heavy-tailed
     fit: an observed `CauchyVariable`) — the family of y, with every form of the scale above; the teacher's noise is then drawn from that
     family at scale sigma.  scale_latent / scale_latent_prior / scale_latent_q: a hierarchical prior, as for
+    `build_bayesian_neural_network`.  point: a tuple of tensor names (the scale head's among them), or "all" — point estimates, as for
     `build_bayesian_neural_network`.  Without these keywords every model is built draw for draw as before."""
     BF = api.BF
     if likelihood not in ("normal", "laplace", "cauchy"):
@@ -962,6 +983,8 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
     prior_of = _bnn_prior(api, prior, prior_loc, prior_scale, scale_latent, scale_latent_prior, scale_latent_q,
                           [t % l for l in range(1, len(widths)) for t in (("weights%d", "b%d") if bias else ("weights%d",))]
                           + ((["weights_scale", "b_scale"] if bias else ["weights_scale"]) if scale_head else []))
+    posterior_of = _bnn_posterior(api, point, [t % l for l in range(1, len(widths)) for t in (("weights%d", "b%d") if bias else ("weights%d",))]
+                                  + ((["weights_scale", "b_scale"] if bias else ["weights_scale"]) if scale_head else []))
     rng = np.random.RandomState(seed)
     X = _bnn_features(rng, data, dataset_size, n_features)
     acts = _bnn_activations(activations, activation, len(widths) - 2)
@@ -1000,21 +1023,17 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
         pre = BF.matmul(w, layer)
         if bias:
             pre = pre + prior_of("b%d" % l, (rows, 1))
-            q_vars.append(api.NormalVariable(q_loc_scale * q_scale * rng.normal(0., 1., (rows, 1)), q_scale * np.ones((rows, 1)),
-                                             "b%d" % l, learnable=True))
+            q_vars.append(posterior_of(q_loc_scale * q_scale * rng.normal(0., 1., (rows, 1)), q_scale * np.ones((rows, 1)), "b%d" % l))
         trunk, layer = layer, (getattr(BF, acts[l - 1])(pre) if l + 1 < len(widths) else pre)
-        q_vars.append(api.NormalVariable(q_loc_scale * sw * rng.normal(0., 1., (rows, cols)), sw * np.ones((rows, cols)),
-                                         "weights%d" % l, learnable=True))
+        q_vars.append(posterior_of(q_loc_scale * sw * rng.normal(0., 1., (rows, cols)), sw * np.ones((rows, cols)), "weights%d" % l))
     if scale_head:
         rows, cols = n_outputs, widths[-2]
         sw = q_scale1 if len(widths) == 2 else q_scale
         raw = BF.matmul(prior_of("weights_scale", (rows, cols)), trunk)
         if bias:
             raw = raw + prior_of("b_scale", (rows, 1))
-            q_vars.append(api.NormalVariable(q_loc_scale * q_scale * rng.normal(0., 1., (rows, 1)), q_scale * np.ones((rows, 1)),
-                                             "b_scale", learnable=True))
-        q_vars.append(api.NormalVariable(q_loc_scale * sw * rng.normal(0., 1., (rows, cols)), sw * np.ones((rows, cols)),
-                                         "weights_scale", learnable=True))
+            q_vars.append(posterior_of(q_loc_scale * q_scale * rng.normal(0., 1., (rows, 1)), q_scale * np.ones((rows, 1)), "b_scale"))
+        q_vars.append(posterior_of(q_loc_scale * sw * rng.normal(0., 1., (rows, cols)), sw * np.ones((rows, cols)), "weights_scale"))
         y = Observed(layer, scale_floor + getattr(BF, scale_head)(raw), "y")
         model = api.ProbabilisticModel([y])
         y.observe(targets)

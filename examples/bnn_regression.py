@@ -16,6 +16,8 @@ MI355X:
     python examples/bnn_regression.py --likelihood laplace    # median (L1) regression: LaplaceVariable(chain, b, "y")
     python examples/bnn_regression.py --likelihood cauchy     # the heavy-tailed fit for data with outliers: CauchyVariable(chain, gamma, "y")
     python examples/bnn_regression.py --hierarchical     # a latent prior scale per layer: NormalVariable(0, tau1, "weights1"), tau1 LogNormal
+    python examples/bnn_regression.py --point weights1,b1     # a deterministic trunk under a Bayesian last layer: RootVariable("weights1"), ...
+    python examples/bnn_regression.py --map              # every tensor a point estimate, trained with inference.MAP()
 
 With --learn-sigma the model starts from a guess of 1.0 and learns the noise scale with the posterior (a learnable root `y_scale`
 behind a softplus in the joint model's parameter group, stepped from the second iteration on, as the reference steps it); the learned
@@ -32,6 +34,11 @@ error beside the RMSE, which those few dominate.  With --hierarchical the prior 
 a `LogNormalVariable(0, 1)`, scales the priors of weights1 and b1, `tau2` those of weights2 and b2, each under a learnable LogNormal
 posterior (the hierarchical BNN of the textbooks: per-layer shrinkage learned with the weights; it combines with --prior).  The run is
 the 64-8-1 network of --prior, for its reason, and prints the posterior medians exp(m_t) of the layers' scales after training.
+With --point the tensors named are not random in the posterior: its members for them are learnable `RootVariable`s of the tensors' names
+(the reference's idiom), trained as ordinary network weights under their prior, while the others keep their mean-field Normal —
+`--point weights1,b1` is the usual way to make a wide network affordably Bayesian, and with all of weights1 a point the engine takes both
+products with the minibatch once per iteration, not once per sample (`first_layer_path()` prints "shared").  With --map every tensor is
+a point and `inference.MAP()` trains the network: the loss is -log p(theta, minibatch) on one sample, no entropy.
 """
 import os
 import sys
@@ -71,6 +78,22 @@ if "--likelihood" in sys.argv[1:]:
     KW.update(likelihood=LIKELIHOOD)
 
 
+POINT = ()
+if "--map" in sys.argv[1:]:
+    POINT = "all"
+elif "--point" in sys.argv[1:]:
+    POINT = tuple(n for n in (sys.argv[sys.argv.index("--point") + 1:] or [""])[0].split(",") if n)
+    if not POINT:
+        sys.exit("--point weights1,b1 (tensor names, comma-separated)")
+if POINT:
+    KW.update(point=POINT)
+
+
+def value_of(params, name):
+    """the posterior mean of a tensor: the loc of its Normal, or the value of its root"""
+    return params[name + "_loc"] if name + "_loc" in params else params[name]
+
+
 def dataset_of(variable):
     """[DS, rows] array behind an EmpiricalVariable"""
     a = np.asarray(variable.link.expressions()["dataset"].expr.attr.value, dtype=np.float64)
@@ -82,8 +105,8 @@ def posterior_mean_rmse(model):
     y = next(v for v in model.flatten() if v.name == "y")
     X, Y = dataset_of(next(v for v in model.flatten() if v.name == "x")), dataset_of(y.dataset)
     p = engine.compile_model(model).named_params()
-    hidden = np.tanh(X @ p["weights1_loc"].reshape(KW["n_hidden"], -1).T + p["b1_loc"].reshape(1, -1))
-    pred = hidden @ p["weights2_loc"].reshape(KW["n_outputs"], -1).T + p["b2_loc"].reshape(1, -1)
+    hidden = np.tanh(X @ value_of(p, "weights1").reshape(KW["n_hidden"], -1).T + value_of(p, "b1").reshape(1, -1))
+    pred = hidden @ value_of(p, "weights2").reshape(KW["n_outputs"], -1).T + value_of(p, "b2").reshape(1, -1)
     if LIKELIHOOD != "normal":
         print("    median |error| of the posterior-mean prediction: %.3f" % float(np.median(np.abs(pred - Y))))
     return float(np.sqrt(np.mean((pred - Y) ** 2)))
@@ -93,12 +116,16 @@ model = W.build_bnn_regression(W.native_api(), **KW)
 print("engine: %s, data path %s" % (type(engine.compile_model(model)).__name__, engine.compile_model(model).data_path()))
 if LIKELIHOOD != "normal":
     print("likelihood:", engine.compile_model(model).program.summary()["family"])
+if POINT:
+    print("point estimates: %s; first layer %s" % (", ".join(engine.compile_model(model).program.summary()["point"]),
+                                                  engine.compile_model(model).first_layer_path()))
 if PRIOR:
     print("priors:", engine.compile_model(model).program.summary()["priors"])
 print("RMSE of the posterior-mean prediction before training: %.3f (noise scale %s)"
       % (posterior_mean_rmse(model), "from the scale head" if SCALE_HEAD else "%.2f" % KW["sigma"]))
 t0 = time.time()
-inference.perform_inference(model, number_iterations=1500, number_samples=50, optimizer="Adam", lr=0.005)
+inference.perform_inference(model, number_iterations=1500, number_samples=50, optimizer="Adam", lr=0.005,
+                            inference_method=inference.MAP() if POINT == "all" else inference.ReverseKL())
 seconds = time.time() - t0
 loss = np.asarray(model.diagnostics["loss curve"])
 print("1500 iterations in %.2f s; loss %.1f -> %.1f" % (seconds, loss[:20].mean(), loss[-20:].mean()))

@@ -668,6 +668,25 @@ int bsvi_bnn_set_likelihood_family(bsvi_bnn* b, uint32_t kind);
  * function of (seed, offset, global sample, t).  bsvi_bnn_workspace_bytes grows for such handles only; bsvi_bnn_predict is unchanged
  * (the weights' posterior does not involve the latents: its noise stays [n_rows][N]).  No struct changes, the ABI version stays. */
 int bsvi_bnn_set_scale_latents(bsvi_bnn* b, uint32_t n_latents, const uint8_t* row_latent, uint32_t n_rows, const uint32_t* latent_uniform);
+/* POINT-ESTIMATED rows (the reference's RootVariable members of a posterior model; all rows: inference.MAP): row_point[r] is 1 for a row
+ * that is NOT random in the posterior, 0 for a row with its mean-field Normal.  For a point row and every sample w = the row's q loc
+ * entry exactly (a parameter entry if the value is learnable, a constant if it is frozen); its q scale entry must be a constant and is
+ * never read as a scale.  Such a row has no draw (noise_dev is not read for it, noise_out_dev reports 0; the Philox counters of the other
+ * rows do not move: row r still draws from (sample, r >> 2)), adds nothing to log q, has no entropy term  entropy_weight (1/2 + 1/2 log 2 pi
+ * + log s)  and no score term under the BlackBox estimator; its prior, Normal, Laplace or Cauchy, counts in f and in the gradient of its
+ * q loc and prior entries as for any row, evaluated at w.  A point row may not stand under a latent prior scale.  When every row is a
+ * point the caller sets entropy_weight = 0 and f is log p(w, minibatch): MAP.  Valid after any of the create calls and before the first
+ * launch: a null pointer, n_rows other than the model's, a byte above 1, a point row whose q scale entry has a gradient or a call after a
+ * launch is BSVI_ERR_INVALID.  Without the call (or with every byte 0) no row is a point, and such a model runs the kernels it ran;
+ * bsvi_bnn_predict uses the value for the point rows.  No struct changes, the ABI version stays. */
+int bsvi_bnn_set_point_rows(bsvi_bnn* b, const uint8_t* row_point, uint32_t n_rows);
+/* The SHARED FIRST LAYER: when every row of weights1 (the first H1 x n_features rows) is a point row, all samples see the same weights1;
+ * the launches then take the first product once (a1 = W1 x, broadcast to the samples), sum d f / d a1 over the samples in a fixed order
+ * (no atomics: results are the same bits from run to run) and take ONE second product; no per-sample copy of weights1 is written and
+ * bsvi_bnn_workspace_bytes shrinks accordingly.  b1 and the upper tensors may be random or points.  BSVI_BNN_SHARED1=0 (read once per
+ * handle, where BSVI_BNN_MID is) keeps both products per sample.  Returns 1 shared, 0 per sample, -1 for a null handle; the choice is
+ * csrc/bnn_select.h's shared_first.  bsvi_bnn_predict is unchanged. */
+int bsvi_bnn_shared_first(const bsvi_bnn* b);
 void bsvi_bnn_destroy(bsvi_bnn* b);
 size_t bsvi_bnn_workspace_bytes(const bsvi_bnn* b, uint32_t n_samples_local);
 int bsvi_bnn_exact_data(const bsvi_bnn* b);
