@@ -63,6 +63,15 @@ struct MvnArgs {
 #ifndef MVN_SPILL
 #define MVN_SPILL 0
 #endif
+// the accumulator of the gradient contraction (step 6)
+#ifndef MVN_GRAD_DOUBLE
+#define MVN_GRAD_DOUBLE 0
+#endif
+#if MVN_GRAD_DOUBLE
+typedef double mvn_gacc;
+#else
+typedef float mvn_gacc;
+#endif
 
 typedef float mvn_f4 __attribute__((ext_vector_type(4)));
 
@@ -88,6 +97,16 @@ __device__ __forceinline__ float mvn_block_sum(float v, float* red, int tid) {
     if ((tid & 63) == 0) red[tid >> 6] = v;
     __syncthreads();
     const float s = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();
+    return s;
+}
+// the same in double, for the one sum whose terms cancel to a small part of their size (step 6, MVN_GRAD_DOUBLE); `red` as above
+__device__ __forceinline__ double mvn_block_sum(double v, double* red, int tid) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if ((tid & 63) == 0) red[tid >> 6] = v;
+    __syncthreads();
+    const double s = (red[0] + red[1]) + (red[2] + red[3]);
     __syncthreads();
     return s;
 }
@@ -176,6 +195,11 @@ extern "C" __global__ void __launch_bounds__(MVN_THREADS) bsvi_mvn_kernel(const 
     __shared__ __attribute__((aligned(16))) float rdiag[VP];
     __shared__ float inputs[MVN_NIN_PAD];
     __shared__ float red[4];
+#if MVN_GRAD_DOUBLE
+    __shared__ double gred[4];
+#else
+    float* const gred = red;
+#endif
     const int tid = threadIdx.x, h = tid & 1, pr = tid >> 1;
     const uint32_t n = blockIdx.x;
     if (n >= G.n_local) return;
@@ -454,9 +478,14 @@ extern "C" __global__ void __launch_bounds__(MVN_THREADS) bsvi_mvn_kernel(const 
     MVN_STEP_END(5)
 
     // ---- 6: dlogp/ds_k = sum_{i >= j} m_ij (alpha_i alpha_j - S_ij) / 2 * dC_ij/ds_k   (m_ij = 2 off the diagonal: C is symmetric)
+    // The terms are far larger than their sum (S = C^-1 alternates in sign where dC/ds is smooth: at D = 1 024 and a jitter of 5e-2 the
+    // sum of |term| is 6e7 and the coefficient of the length-scale ~20).  MVN_GRAD_DOUBLE (mvn.cpp: D > 512) adds the D (D + 1) / 2
+    // products up in double: in single precision a thread's 2 050 additions alone were an error of 0.04 - 0.09 there, 4.5 - 5.9 x what
+    // torch's float32 result is off by (3.9 x at D = 515, 519 additions; at most 2.7 x up to D = 322).  Up to 512 the sum stays as it was.
     float gin[MVN_NIN_PAD];
+    mvn_gacc gacc[MVN_NIN_PAD];
 #pragma unroll
-    for (int k = 0; k < MVN_NIN_PAD; ++k) gin[k] = 0.0f;
+    for (int k = 0; k < MVN_NIN_PAD; ++k) { gin[k] = 0.0f; gacc[k] = 0; }
 #if MVN_NIN > 0
     for (int e = tid; e < NTRI; e += MVN_THREADS) {
         int i, j;
@@ -473,10 +502,10 @@ extern "C" __global__ void __launch_bounds__(MVN_THREADS) bsvi_mvn_kernel(const 
         const float gij = (i == j ? 0.5f : 1.0f) * (sij - dvec[i] * dvec[j]);
 #endif
 #pragma unroll
-        for (int k = 0; k < MVN_NIN; ++k) gin[k] += gij * dc[k];
+        for (int k = 0; k < MVN_NIN; ++k) gacc[k] += (mvn_gacc)gij * (mvn_gacc)dc[k];
     }
 #pragma unroll
-    for (int k = 0; k < MVN_NIN; ++k) gin[k] = mvn_block_sum(gin[k], red, tid);
+    for (int k = 0; k < MVN_NIN; ++k) gin[k] = (float)mvn_block_sum(gacc[k], gred, tid);
 #endif
 
     // ---- the surrogate's rows: coefficients of the slot inputs, of x (when latent), of the uniform inputs, then e

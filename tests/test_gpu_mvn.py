@@ -7,12 +7,25 @@ The yardstick of every check — torch's own float32 error — comes from tests/
 results on the CPU at 1, 2 and 4 threads (three summation orders), recorded by `python tests/test_gpu_mvn.py`, and the
 yardstick is the largest of their errors.  Computed live from one run, it followed the host's BLAS / LAPACK code path and
 thread count — the amplitude's coefficient moved between 1.2e-3 and 2.0e-3 of its scale at D = 515 and between 4.1e-4 and
-5.3e-4 at D = 256 — and with it the verdict on the same kernel result.  The double-precision truth is computed live."""
+5.3e-4 at D = 256 — and with it the verdict on the same kernel result.  The double-precision truth is computed live.
+
+The second half of the file checks EVERY row the kernel writes (slot inputs | x | uniform inputs | m | e) in all three forms, the
+Taylor1 value rows, the largest sizes the library takes, regrowth of the spill scratch and the non-finite results of the other two
+forms.  Its recorded yardsticks are tests/golden/mvn/torch_f32_rows.npz (`python tests/test_gpu_mvn.py --rows`; sizes up to 6 are
+computed live: no blocked LAPACK path there).  Measured on an MI355X, largest err / yardstick per row kind over forms and sizes:
+slot inputs 2.21, uniform inputs 3.54 (both precision form, D = 2: 1.9e-7 of the scale), x and m 3.10 (precision form, D = 130:
+7.8e-7 of the scale), log p 2.54; Taylor1: value and loc rows 1.92, the others below 1.  D = 1 021 / 1 024 with three samples:
+37.3 / 37.2 ms per launch, every row within 0.1 - 0.94 x torch's float32 error.  Those two sizes found the gradient contraction
+(step 6 of mvn_kernel.h) adding 2 050 products per thread in single precision: the length-scale's coefficient was 4.5 and 5.9 x
+torch's float32 error there (3.9 x at D = 515); beyond D = 512 the kernel now sums them in double: 0.10 and 0.41 x (0.48 x at 515).
+Up to 512 the sum is the single-precision one it was (at most 2.9 x over GP_CASES)."""
 import ctypes as C
 import json
 import os
 import sys
+import time
 import types
+import zipfile
 
 import numpy as np
 import pytest
@@ -94,11 +107,10 @@ def gp_inputs(D, latent_x, jitter, N=37):
     return node, sq, eye, ell, xs, params
 
 
-def gp_torch(D, latent_x, jitter, dtype):
+def gp_torch(D, latent_x, jitter, dtype, N=37):
     """torch: double precision as the truth, single precision (what the reference computes) as the yardstick — the covariance
     has a condition number of ~amp / jitter * D, so float32 results of ANY algorithm carry that many ulps"""
-    node, sq, eye, ell, xs, params = gp_inputs(D, latent_x, jitter)
-    N = ell.shape[0]
+    node, sq, eye, ell, xs, params = gp_inputs(D, latent_x, jitter, N)
     ell_t = ell.to(dtype).clone().requires_grad_(True)
     p2 = params[2].to(dtype).clone().requires_grad_(True)
     x_t = (xs.to(dtype).T.clone() if latent_x else torch.tensor(node.value).to(dtype).expand(N, D).clone()).requires_grad_(True)
@@ -116,12 +128,11 @@ def gp_torch(D, latent_x, jitter, dtype):
     return out
 
 
-def check_against_torch(D, latent_x, jitter, factor):
+def check_against_torch(D, latent_x, jitter, factor, N=37, recorded=recorded_f32, timed=False):
     from brancher_amd import native
     lib = native.load()
     dev = torch.device("cuda:0")
-    node, sq, eye, ell, xs, params = gp_inputs(D, latent_x, jitter)
-    N = ell.shape[0]
+    node, sq, eye, ell, xs, params = gp_inputs(D, latent_x, jitter, N)
     d, keep = native.mvn_desc(node)
     handle = C.c_void_p()
     native.check(lib.bsvi_mvn_create(C.byref(d), C.byref(handle)))
@@ -138,13 +149,22 @@ def check_against_torch(D, latent_x, jitter, factor):
     native.check(lib.bsvi_mvn_eval(handle, C.byref(args)))
     torch.cuda.synchronize()
     got = out.cpu().double().numpy()
+    if timed:           # the launch again, now that the kernel is compiled and loaded: the same rows, and its wall time on record
+        out.fill_(float("nan"))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        native.check(lib.bsvi_mvn_eval(handle, C.byref(args)))
+        torch.cuda.synchronize()
+        print("D = %d, %d samples: %.1f ms per launch" % (D, N, 1e3 * (time.perf_counter() - t0)))
+        assert np.array_equal(out.cpu().double().numpy(), got)
     lib.bsvi_mvn_destroy(handle)
 
-    ref, f32 = gp_torch(D, latent_x, jitter, torch.float64), recorded_f32(gp_case(D, latent_x, jitter))
+    ref, f32 = gp_torch(D, latent_x, jitter, torch.float64, N), recorded(gp_case(D, latent_x, jitter))
 
     def close(mine, key):
         scale = np.abs(ref[key]).max() + 1e-30
         err, yard = np.abs(mine - ref[key]).max() / scale, f32_error(f32, key, ref[key]) / scale
+        print("%s %s: err %.3g, torch float32 %.3g (x %.2f) of the scale %.3g" % (gp_case(D, latent_x, jitter), key, err, yard, err / (yard + 1e-300), scale))
         assert err <= max(factor * yard, 2e-6), (key, err, yard)
 
     row = 0
@@ -260,6 +280,282 @@ def test_not_positive_definite_gives_non_finite_rows():
     lib.bsvi_mvn_destroy(handle)
 
 
+# ---- every row of the surrogate: slot inputs | x | uniform inputs | m | e ------------------------------------------------------
+ROWS_FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mvn", "torch_f32_rows.npz")
+ROW_FORMS = ["covariance_matrix", "scale_tril", "precision_matrix"]
+ROW_DIMS = [1, 2, 3, 4, 6, 61, 130, 193]        # below one block of four, one block, padded (6, 61), a second trip (130), spill (193)
+ROW_LIVE_DIM = 6                                # up to here torch's float32 run is computed live (no blocked LAPACK path), beyond: the fixture
+TAYLOR_CASES = [(form, D) for form in ("covariance_matrix", "precision_matrix") for D in (6, 130)]
+LARGEST = [1021, 1024]
+ROW_KEYS = ("s0", "s1", "x", "u0", "u1", "m", "lp")
+ROW_WEIGHT, ROW_N = 0.37, 11
+ROW_SLOT_ROWS, ROW_VALUE_ROW0 = (1, 0), 3       # s0 is read from sample row 1, s1 from row 0, x from rows 3 .. 3 + D
+ROW_MARGIN = dict(covariance_matrix=0.3, precision_matrix=0.3, scale_tril=0.5)   # smallest eigenvalue / smallest diagonal entry of L
+
+
+def recorded_rows_f32(case):
+    """torch's float32 results of one case in ROWS_FIXTURE: one dict per thread count; what the recorder left out is the first count's"""
+    data = np.load(ROWS_FIXTURE)
+    first = {k[len(case) + 1:].split("/")[1]: data[k].astype(np.float64) for k in data.files if k.startswith("%s/t%d/" % (case, F32_THREADS[0]))}
+    assert first, case
+    runs = [first]
+    for threads in F32_THREADS[1:]:
+        runs.append({key: data["%s/t%d/%s" % (case, threads, key)].astype(np.float64) if "%s/t%d/%s" % (case, threads, key) in data.files else v
+                     for key, v in first.items()})
+    return runs
+
+
+def rows_case(form, D, value_param):
+    return "rows/%s/D%d%s" % (form, D, "_taylor1" if value_param else "")
+
+
+def rows_inputs(form, D, value_param=False, N=ROW_N):
+    """the node  M0 * s0 + M1 * u0 + M2 * (s1 * u1) + M3  with two slot inputs (0, 1) and two uniform inputs (2: a softplus with a and b
+    set, 3: an identity), a learnable loc (entries alternate identity / tanh over five parameters) and x latent — or, `value_param`,
+    the value entries of the Taylor1 program over five more parameters"""
+    from brancher_amd import lowering
+    rng = np.random.RandomState(7 * D + len(form))
+    B, UT = lowering.BINOP, lowering.UT
+    if form == "scale_tril":
+        m0, m1 = (np.tril(rng.normal(0.0, 0.3 / np.sqrt(D), (D, D)), -1) for _ in range(2))
+        m2, m3 = np.diag(rng.uniform(0.7, 1.3, D)), 0.5 * np.eye(D)
+    else:
+        x = np.sort(rng.uniform(-2.0, 2.0, D))
+        sq = (x[:, None] - x[None, :]) ** 2
+        m0, m1, m2, m3 = np.exp(-0.5 * sq / 0.3 ** 2), np.exp(-0.5 * sq / 1.0 ** 2), np.eye(D), gp_jitter(D) * np.eye(D)
+    mats = np.stack([m0, m1, m2, m3]).astype(np.float32)
+    code = [("MAT", 0, 0, 0, 0.0), ("INPUT", 0, 0, 0, 0.0), ("BIN", B["mul"], 0, 1, 0.0),           # 2 = M0 * s0
+            ("MAT", 0, 1, 0, 0.0), ("INPUT", 0, 2, 0, 0.0), ("BIN", B["mul"], 3, 4, 0.0),           # 5 = M1 * u0
+            ("INPUT", 0, 1, 0, 0.0), ("INPUT", 0, 3, 0, 0.0), ("BIN", B["mul"], 6, 7, 0.0),         # 8 = s1 * u1
+            ("MAT", 0, 2, 0, 0.0), ("BIN", B["mul"], 9, 8, 0.0), ("BIN", B["add"], 2, 5, 0.0),      # 10 = M2 * (s1 * u1), 11 = 2 + 5
+            ("BIN", B["add"], 11, 10, 0.0), ("MAT", 0, 3, 0, 0.0), ("BIN", B["add"], 12, 13, 0.0)]
+    params = rng.normal(0.0, 0.5, 16).astype(np.float32)
+    uni = np.zeros(2, dtype=lowering.UNIFORM_DTYPE)
+    a0, b0 = 0.1, 0.7
+    params[2] = np.log(np.expm1((rng.uniform(0.6, 1.4) - a0) / b0))      # u0 = 0.1 + 0.7 softplus(params[2]) in [0.6, 1.4]
+    params[4] = rng.uniform(0.6, 1.4)                                     # u1 = params[4]
+    uni[0], uni[1] = (2, UT["softplus"], 1, 0, a0, b0), (4, UT["identity"], 1, 0, 0.0, 1.0)
+
+    def entries(src0):
+        e = np.zeros(D, dtype=lowering.UNIFORM_DTYPE)
+        for i in range(D):
+            e[i] = (src0 + i % 5, UT["tanh"] if i % 2 else UT["identity"], 1, 0, rng.normal(0.0, 0.3), rng.uniform(0.5, 1.5))
+        return e
+
+    loc_entries = entries(6)
+    value_entries = entries(11) if value_param else None
+    g = torch.Generator().manual_seed(D)
+    s = (0.6 + 0.8 * torch.rand(2, N, generator=g)).float()
+    xs = torch.randn(D, N, generator=g).float() * 0.8
+    node = types.SimpleNamespace(code=code, mats=mats, loc=np.zeros(D, dtype=np.float32), value=np.zeros(D, dtype=np.float32) if value_param else None,
+                                 dim=D, uniform_inputs=uni, slot_inputs=list(ROW_SLOT_ROWS), weight=ROW_WEIGHT, form=form,
+                                 loc_entries=loc_entries, value_entries=value_entries)
+    return node, s, xs, torch.tensor(params)
+
+
+def entry_values(entries, params, dtype):
+    """a + b * transform(params[src]) of identity / softplus / tanh entries, in `dtype` from the float32 parameters"""
+    from brancher_amd import lowering
+    fn = {lowering.UT["identity"]: lambda v: v, lowering.UT["softplus"]: torch.nn.functional.softplus, lowering.UT["tanh"]: torch.tanh}
+    p = params.to(dtype)
+    return torch.stack([torch.tensor(e["a"]).to(dtype) + torch.tensor(e["b"]).to(dtype) * fn[int(e["transform"])](p[int(e["src"])]) for e in entries])
+
+
+def rows_torch(form, D, dtype, value_param=False, N=ROW_N):
+    """weight * log p per sample and its gradient in the VALUE of every input (per-sample copies of what the samples share), of x and of m"""
+    node, s, xs, params = rows_inputs(form, D, value_param, N)
+    leaf = lambda t: t.detach().clone().requires_grad_(True)
+    s_t = leaf(s.to(dtype))
+    u_t = leaf(entry_values(node.uniform_inputs, params, dtype)[:, None].expand(2, N))
+    m_t = leaf(entry_values(node.loc_entries, params, dtype)[None].expand(N, D))
+    x_t = leaf(entry_values(node.value_entries, params, dtype)[None].expand(N, D) if value_param else xs.to(dtype).T)
+    M = [torch.tensor(m).to(dtype)[None] for m in node.mats]
+    col = lambda v: v[:, None, None]
+    mat = M[0] * col(s_t[0]) + M[1] * col(u_t[0]) + M[2] * col(s_t[1] * u_t[1]) + M[3]
+    if dtype == torch.float64:       # the premise of the case: finite and positive definite / a positive diagonal, with room to spare
+        least = np.diagonal(mat.detach().numpy(), axis1=1, axis2=2).min() if form == "scale_tril" else np.linalg.eigvalsh(mat.detach().numpy()).min()
+        assert np.isfinite(mat.detach().numpy()).all() and least > ROW_MARGIN[form], (form, D, least)
+    kw = {form: torch.tril(mat) if form == "scale_tril" else mat}
+    lp = ROW_WEIGHT * torch.distributions.MultivariateNormal(m_t, **kw).log_prob(x_t)
+    lp.sum().backward()
+    num = lambda t: t.detach().double().numpy()
+    return dict(s0=num(s_t.grad[0]), s1=num(s_t.grad[1]), x=num(x_t.grad).T, u0=num(u_t.grad[0]), u1=num(u_t.grad[1]), m=num(m_t.grad).T, lp=num(lp),
+                values=dict(s0=num(s_t[0]), s1=num(s_t[1]), x=num(x_t).T, u0=num(u_t[0]), u1=num(u_t[1]), m=num(m_t).T))
+
+
+def rows_eval(lib, handle, d, node, s, xs, params, N):
+    """one evaluation: the sample matrix laid out as ROW_SLOT_ROWS / ROW_VALUE_ROW0 say, the output pre-filled with NaN"""
+    from brancher_amd import native
+    dev = torch.device("cuda:0")
+    n_out = int(lib.bsvi_mvn_rows_out(C.byref(d)))
+    samples = torch.zeros(ROW_VALUE_ROW0 + node.dim + 1, N)
+    samples[ROW_SLOT_ROWS[0]], samples[ROW_SLOT_ROWS[1]] = s[0], s[1]
+    samples[ROW_VALUE_ROW0:ROW_VALUE_ROW0 + node.dim] = xs
+    samples_d, params_d = samples.to(dev), params.to(dev)
+    out = torch.full((n_out, N), float("nan"), device=dev)
+    args = native.MvnArgs(params_dev=params_d.data_ptr(), samples_dev=samples_d.data_ptr(), rows_out_dev=out.data_ptr(),
+                          n_samples_local=N, value_row0=ROW_VALUE_ROW0, stream=None)
+    for k, row in enumerate(node.slot_inputs):
+        args.input_rows[k] = row
+    native.check(lib.bsvi_mvn_eval(handle, C.byref(args)))
+    torch.cuda.synchronize()
+    return out.cpu().double().numpy()
+
+
+def check_every_row(form, D, value_param):
+    from brancher_amd import native
+    lib = native.load()
+    node, s, xs, params = rows_inputs(form, D, value_param)
+    ref = rows_torch(form, D, torch.float64, value_param)
+    d, keep = native.mvn_desc(node)
+    handle = C.c_void_p()
+    native.check(lib.bsvi_mvn_create(C.byref(d), C.byref(handle)))
+    got = rows_eval(lib, handle, d, node, s, xs, params, ROW_N)
+    lib.bsvi_mvn_destroy(handle)
+    assert got.shape[0] == 2 + D + 2 + D + 1 == int(lib.bsvi_mvn_rows_out(C.byref(d)))
+    if D <= ROW_LIVE_DIM:
+        f32 = [rows_torch(form, D, torch.float32, value_param)]
+    else:
+        f32 = recorded_rows_f32(rows_case(form, D, value_param))
+    mine = dict(s0=got[0], s1=got[1], x=got[2:2 + D], u0=got[2 + D], u1=got[3 + D], m=got[4 + D:4 + 2 * D])
+    # e + sum_k g_k value_k = weight * log p, with the kernel's own coefficients
+    mine["lp"] = got[4 + 2 * D] + sum((mine[k] * ref["values"][k]).reshape(-1, ROW_N).sum(0) for k in ROW_KEYS[:-1])
+    failed = []
+    for key in ROW_KEYS:
+        scale = np.abs(ref[key]).max() + 1e-30
+        err, yard = np.abs(mine[key] - ref[key]).max() / scale, f32_error(f32, key, ref[key]) / scale
+        print("%s %s: err %.3g, torch float32 %.3g (x %.2f) of the scale %.3g" % (rows_case(form, D, value_param), key, err, yard, err / (yard + 1e-300), scale))
+        if not err <= max(4.0 * yard, 2e-6):
+            failed.append((key, err, yard))
+    assert not failed, (form, D, failed)
+
+
+@pytest.mark.parametrize("form", ROW_FORMS)
+@pytest.mark.parametrize("D", ROW_DIMS)
+def test_every_row_of_the_surrogate_matches_torch_double(form, D):
+    """All five kinds of rows in all three forms, two inputs of each kind (the offsets `row += MVN_NSI`, `row += D`, `row += MVN_NIN -
+    MVN_NSI` with another layout than the one above), a latent x (the -alpha rows) and a learnable loc (the +alpha rows, `linm`):
+    each coefficient row against autograd on the input values in double, and e + sum g * value = weight * log p."""
+    check_every_row(form, D, False)
+
+
+@pytest.mark.parametrize("form,D", TAYLOR_CASES)
+def test_taylor1_value_rows_match_torch_double(form, D):
+    """MVN_VALUE_PARAM: the value is a + b * transform(parameter) per element; its D rows are -weight * alpha and e takes them back"""
+    check_every_row(form, D, True)
+
+
+@pytest.mark.parametrize("D", LARGEST)
+def test_the_largest_sizes_the_library_accepts(D):
+    """the last size that is no whole block of four and the largest one, the matrix of a sample in device memory; three samples"""
+    check_against_torch(D, True, 5e-2, 4.0, N=3, recorded=recorded_rows_f32, timed=True)
+
+
+@pytest.mark.parametrize("D", [0, 1025])
+def test_sizes_outside_the_range_are_refused(D):
+    from brancher_amd import native
+    lib = native.load()
+    node, _, _ = gp_node(max(D, 1), True)
+    node.dim = D
+    d, keep = native.mvn_desc(node)
+    handle = C.c_void_p()
+    assert lib.bsvi_mvn_create(C.byref(d), C.byref(handle)) == -5 and not handle.value           # BSVI_ERR_RESOURCE, on the host
+
+
+def test_spill_scratch_regrown_between_launches_gives_a_fresh_handles_rows():
+    """D = 193 keeps the matrix of a sample in a scratch block sized for the largest launch so far: 5 samples, then 37 (the block is
+    freed and allocated again), then 5 in the larger block.  The kernel has no atomics: each result is bit for bit a fresh handle's."""
+    from brancher_amd import native
+    lib = native.load()
+    D = 193
+
+    def launch(handle, d, N):
+        node, s, xs, params = rows_inputs("covariance_matrix", D, False, N)
+        return rows_eval(lib, handle, d, node, s, xs, params, N)
+
+    def create():
+        d, keep = native.mvn_desc(rows_inputs("covariance_matrix", D)[0])
+        handle = C.c_void_p()
+        native.check(lib.bsvi_mvn_create(C.byref(d), C.byref(handle)))
+        return handle, d, keep
+
+    fresh = {}
+    for N in (5, 37):
+        handle, d, keep = create()
+        fresh[N] = launch(handle, d, N)
+        lib.bsvi_mvn_destroy(handle)
+        assert np.isfinite(fresh[N]).all()
+    handle, d, keep = create()
+    for N in (5, 37, 5):
+        assert np.array_equal(launch(handle, d, N), fresh[N]), N
+    lib.bsvi_mvn_destroy(handle)
+
+
+@pytest.mark.parametrize("form", OTHER_FORMS)
+def test_not_positive_definite_gives_non_finite_rows_in_the_other_forms(form):
+    """a precision matrix that is not positive definite (M1 = -5 I), a scale_tril with a negative diagonal entry: a non-finite e
+    row and a clean return, as test_not_positive_definite_gives_non_finite_rows has it for the covariance form"""
+    from brancher_amd import native
+    lib = native.load()
+    dev = torch.device("cuda:0")
+    node, sc = other_inputs(form, 16, N=8)
+    if form == "scale_tril":
+        node.mats[1][3, 3] = -0.9
+    else:
+        node.mats[1] = -5.0 * np.eye(16, dtype=np.float32)
+    d, keep = native.mvn_desc(node)
+    handle = C.c_void_p()
+    native.check(lib.bsvi_mvn_create(C.byref(d), C.byref(handle)))
+    n_out = int(lib.bsvi_mvn_rows_out(C.byref(d)))
+    samples = torch.ones(4, 8, device=dev)
+    out = torch.zeros(n_out, 8, device=dev)
+    params = torch.zeros(4, device=dev)
+    args = native.MvnArgs(params_dev=params.data_ptr(), samples_dev=samples.data_ptr(), rows_out_dev=out.data_ptr(),
+                          n_samples_local=8, value_row0=0, stream=None)
+    args.input_rows[0] = 2
+    native.check(lib.bsvi_mvn_eval(handle, C.byref(args)))
+    torch.cuda.synchronize()
+    assert not torch.isfinite(out[-1]).any()
+    lib.bsvi_mvn_destroy(handle)
+
+
+def write_npz(path, arrays):
+    """np.savez_compressed with the members in sorted order and a fixed date: the same arrays give the same bytes"""
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for name in sorted(arrays):
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type, info.external_attr = zipfile.ZIP_DEFLATED, 0o644 << 16
+            with z.open(info, "w") as f:
+                np.lib.format.write_array(f, np.asanyarray(arrays[name]), allow_pickle=False)
+
+
+def record_rows_fixture(path=ROWS_FIXTURE):
+    """(re)writes tests/golden/mvn/torch_f32_rows.npz (`python tests/test_gpu_mvn.py --rows`): torch's float32 results on the CPU, at each of
+    F32_THREADS, of the every-row and Taylor1 cases beyond ROW_LIVE_DIM and of the two largest sizes.  torch_f32.npz is not touched."""
+    arrays = {}
+    for threads in F32_THREADS:
+        torch.set_num_threads(threads)
+        cases = [(form, D, False) for form in ROW_FORMS for D in ROW_DIMS] + [(form, D, True) for form, D in TAYLOR_CASES]
+        for form, D, value_param in cases:
+            if D > ROW_LIVE_DIM:
+                for key, v in rows_torch(form, D, torch.float32, value_param).items():
+                    if key != "values":
+                        arrays["%s/t%d/%s" % (rows_case(form, D, value_param), threads, key)] = np.asarray(v, dtype=np.float32)
+        for D in LARGEST:
+            for key, v in gp_torch(D, True, 5e-2, torch.float32, N=3).items():
+                if key != "amp_value":
+                    arrays["%s/t%d/%s" % (gp_case(D, True, 5e-2), threads, key)] = np.asarray(v, dtype=np.float32)
+    # (a result of 2 or 4 threads that is bit for bit the one of 1 thread — every size that takes no threaded path — is not stored again)
+    first = "/t%d/" % F32_THREADS[0]
+    for name in [k for k in arrays if first not in k]:
+        case, threads, key = name.rsplit("/", 2)
+        if np.array_equal(arrays[name], arrays[case + first + key]):
+            del arrays[name]
+    meta = dict(written_by="python tests/test_gpu_mvn.py --rows", torch=torch.__version__.split("+")[0], threads=list(F32_THREADS), device="cpu")
+    arrays["meta"] = np.asarray(json.dumps(meta, sort_keys=True))
+    write_npz(path, arrays)
+
+
 def record_f32_fixture(path=F32_FIXTURE):
     """(re)writes tests/golden/mvn/torch_f32.npz: torch's float32 results of every case above on the CPU, at each of F32_THREADS"""
     arrays = {}
@@ -280,4 +576,7 @@ def record_f32_fixture(path=F32_FIXTURE):
 
 if __name__ == "__main__":
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    record_f32_fixture()
+    if "--rows" in sys.argv[1:]:
+        record_rows_fixture()
+    else:
+        record_f32_fixture()
