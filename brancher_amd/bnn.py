@@ -7,8 +7,8 @@ Bayesian neural networks on the dense-link path: lowering and engine for graphs 
     k      = CategoricalVariable(logits=logits, name="k");  k.observe(labels)
     q:       NormalVariable(loc, scale, <same name>, learnable=True) for weights1, b1, weights2, b2
 
-— the reference's `tests/test_MNIST_bayesian_neural_network.py:20-60` (any depth, any of tanh / relu / sigmoid / softplus
-between the layers, biases optional) — and the regression model of the same family, the chain as the loc of an observed Normal,
+— the reference's `tests/test_MNIST_bayesian_neural_network.py:20-60` (any depth, any of tanh / relu / sigmoid / softplus /
+leaky_relu / elu / selu / softsign / hardtanh / relu6 / silu / gelu between the layers, with torch's keywords; biases optional) — and the regression model of the same family, the chain as the loc of an observed Normal,
 
     y = NormalVariable(BF.matmul(weights2, hidden) + b2, sigma, name="y");  y.observe(targets)        # targets [DS, C, 1]
 
@@ -28,18 +28,28 @@ dense path: priors and posteriors are matched by NAME, auto-created roots `<var>
 minibatch rescaling of the likelihood (`variables.py:849` TODO).
 """
 import ctypes as C
+import numbers
 
 import numpy as np
 import torch
 
 from brancher_amd import distributions as D
 from brancher_amd import lowering, native
+from brancher_amd import symbolic as sym
 from brancher_amd.lowering import LoweringError, _Lowering
 from brancher_amd.native import OUT_HEADER, BnnArgs, BnnDesc, BnnLayer
 from brancher_amd.variables import RandomVariable, RootVariable
 
 LIK_CATEGORICAL, LIK_BERNOULLI, LIK_NORMAL = 0, 1, 2
-ACTIVATIONS = dict(tanh=1, relu=2, sigmoid=3, softplus=4)
+ACTIVATIONS = dict(tanh=1, relu=2, sigmoid=3, softplus=4,      # bsvi_bnn_activation (include/bsvi.h); relu6 is hardtanh(0, 6)
+                   leaky_relu=5, elu=6, selu=7, softsign=8, hardtanh=9, relu6=9, silu=10, gelu=11)
+# the kinds with parameters (bsvi_bnn_set_activation_params): name -> ((keyword, torch's default), ...) in torch's positional order, and
+# what each must satisfy; PLAIN_KEYWORDS: the keywords the other new names take, with the one value that is served
+ACTIVATION_PARAMS = dict(leaky_relu=(("negative_slope", 0.01),), elu=(("alpha", 1.0),), hardtanh=(("min_val", -1.0), ("max_val", 1.0)))
+ACTIVATION_RULES = dict(leaky_relu=(lambda s: s > 0, "negative_slope > 0"), elu=(lambda a: a > 0, "alpha > 0"),
+                        hardtanh=(lambda lo, hi: lo < hi, "min_val < max_val"))
+PLAIN_KEYWORDS = dict(leaky_relu=dict(inplace=False), elu=dict(inplace=False), selu=dict(inplace=False), hardtanh=dict(inplace=False),
+                      relu6=dict(inplace=False), silu=dict(inplace=False), gelu=dict(approximate="none"))
 NO_BIAS = 0xFFFFFFFF
 MAX_LAYERS = 8                                                         # BNN_MAX_LAYERS (csrc/bnn_kernel.inc)
 MIDDLE_PATHS = ("mid_gen", "upper_gen", "upper_lds", "upper_mem")      # bsvi_bnn_select::BnnMiddle (csrc/bnn_select.h)
@@ -74,6 +84,8 @@ class BnnProgram:
             s["scale"] = "head" if self.scale_head else "learnable" if self.scale_learnable else "constant"
             if self.family != D.DIST_NORMAL:
                 s["family"] = LIKELIHOOD_FAMILIES[self.family].lower()
+        if any("activation_params" in l for l in self.layers):      # (a kind behind softplus: every hidden layer's function by name)
+            s["activations"] = [activation_text(l) for l in self.layers[:-1]]
         s["priors"] = {t["name"]: t.get("prior", "normal") for t in self.tensors}
         if any(t.get("point") for t in self.tensors):
             s["point"] = [t["name"] for t in self.tensors if t["point"]]
@@ -86,8 +98,69 @@ def _is_random(v):
     return isinstance(v, RandomVariable) and getattr(v, "_type", None) != "Deterministic node"
 
 
+def _activation(e):
+    """the node between two layers -> (name, (p0, p1) of bsvi_bnn_set_activation_params | None for the four kinds without parameters), or
+    the refusal: it names the function and the cause"""
+    name = e.attr[0] if e.op == "call" and isinstance(e.attr[0], str) else None
+    if name not in ACTIVATIONS:
+        raise LoweringError("bnn path: between two layers stands one of BF.%s%s" % (" / BF.".join(ACTIVATIONS), " (not BF.%s)" % name if name else ""))
+    kwargs = e.attr[1]
+    if name not in PLAIN_KEYWORDS and name not in ACTIVATION_PARAMS:
+        if len(e.args) != 1 or kwargs:
+            raise LoweringError("bnn path: between two layers stands one of BF.%s (BF.%s takes the layer alone)" % (" / BF.".join(ACTIVATIONS), name))
+        return name, (None if ACTIVATIONS[name] <= ACTIVATIONS["softplus"] else (0.0, 0.0))
+    where = "bnn path: BF.%s between two layers: " % name
+    plain = lambda x: x.attr if isinstance(x, sym.Expr) and x.op == "const" else x
+
+    def number(x, what):
+        v = plain(x)
+        if isinstance(v, (sym.Expr, bool, np.bool_)) or not isinstance(v, numbers.Real):
+            raise LoweringError(where + "%s is not a number (a parameter of an activation is a Python number: a variable or an array is not "
+                                "served)" % what)
+        return float(v)
+
+    spec = ACTIVATION_PARAMS.get(name, ())
+    if len(e.args) - 1 > len(spec):
+        raise LoweringError(where + "%d positional arguments behind the layer (it takes %s)"
+                            % (len(e.args) - 1, ", ".join(k for k, _ in spec) or "none"))
+    values, given = [d for _, d in spec], set()
+    for (k, _), a in zip(spec, e.args[1:]):
+        values[len(given)] = number(a, k)
+        given.add(k)
+    for k, v in kwargs.items():
+        if k in [s for s, _ in spec]:
+            if k in given:
+                raise LoweringError(where + "%s is given twice" % k)
+            values[[s for s, _ in spec].index(k)] = number(v, k)
+        elif k in PLAIN_KEYWORDS.get(name, {}):
+            served, got = PLAIN_KEYWORDS[name][k], plain(v)
+            if isinstance(got, sym.Expr) or type(got) is not type(served) or got != served:
+                raise LoweringError(where + "%s=%r is not served (only %s=%r)" % (k, "an expression" if isinstance(got, sym.Expr) else got, k, served))
+        else:
+            raise LoweringError(where + "unknown keyword %r" % k)
+    if name in ACTIVATION_RULES:
+        holds, rule = ACTIVATION_RULES[name]
+        with np.errstate(over="ignore"):      # (as the library receives them: single precision — 1e-50 is 0 there, 1e39 is inf)
+            rounded = [float(np.float32(v)) for v in values]
+        if not (all(np.isfinite(v) for v in rounded) and holds(*rounded)):
+            raise LoweringError(where + "it needs finite parameters with %s in single precision (got %s)"
+                                % (rule, ", ".join("%s=%g" % (k, v) for (k, _), v in zip(spec, values))))
+    if name == "relu6":
+        values = [0.0, 6.0]
+    return name, tuple(values + [0.0] * (2 - len(values)))
+
+
+def activation_text(layer):
+    """`leaky_relu(negative_slope=0.2)`: a layer's activation as `summary()` shows it"""
+    name = layer.get("activation_name") or {v: k for k, v in reversed(list(ACTIVATIONS.items()))}.get(layer["activation"], "none")
+    spec = ACTIVATION_PARAMS.get("hardtanh" if name == "relu6" else name, ())
+    if name == "relu6" or not spec:
+        return name
+    return "%s(%s)" % (name, ", ".join("%s=%g" % (k, v) for (k, _), v in zip(spec, layer["activation_params"])))
+
+
 def _chain(e):
-    """logits expression -> ([(W variable, bias variable | None, activation of the layer's output | None)] bottom up, x variable)"""
+    """logits expression -> ([(W variable, bias variable | None, (name, parameters) of the layer's activation | None)] bottom up, x variable)"""
     def is_call(x, names):
         return x.op == "call" and isinstance(x.attr[0], str) and x.attr[0] in names
 
@@ -109,11 +182,10 @@ def _chain(e):
     W, inner = mm.args[0].attr, mm.args[1]
     if inner.op == "var":
         return [[W, bias, None]], inner.attr
-    if is_call(inner, tuple(ACTIVATIONS)) and len(inner.args) == 1 and not inner.attr[1]:
-        below, x = _chain(inner.args[0])
-        below[-1][2] = inner.attr[0]
-        return below + [[W, bias, None]], x
-    raise LoweringError("bnn path: between two layers stands one of BF.%s" % " / BF.".join(ACTIVATIONS))
+    act = _activation(inner)
+    below, x = _chain(inner.args[0])
+    below[-1][2] = act
+    return below + [[W, bias, None]], x
 
 
 def _depends_on_latent(e):
@@ -478,7 +550,9 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
                 raise LoweringError("bnn path: bias %r must be a column [%d, 1]" % (b.name, t["rows"]))
             bias0 = tb["row0"]
         layers.append(dict(rows=t["rows"], cols=t["cols"], weight_row0=t["row0"], bias_row0=bias0,
-                           activation=ACTIVATIONS[act] if act else 0, weights=W.name, bias=b.name if b is not None else None))
+                           activation=ACTIVATIONS[act[0]] if act else 0, weights=W.name, bias=b.name if b is not None else None))
+        if act and act[1] is not None:      # (one of the kinds behind softplus: the layers of the four old kinds are what they were)
+            layers[-1].update(activation_name=act[0], activation_params=act[1])
         width = t["rows"]
     if head:
         ts, last = by_name[head[3].name], layers[-1]
@@ -667,6 +741,9 @@ class CompiledBnn:
         if row_point is not None and np.any(row_point):    # (without the call no row is a point)
             row_point = np.ascontiguousarray(row_point, dtype=np.uint8)
             native.check(lib.bsvi_bnn_set_point_rows(handle, row_point.ctypes.data_as(C.c_void_p), row_point.size))
+        if any("activation_params" in l for l in p.layers):      # (without the call torch's defaults hold; a model of the four old kinds makes none)
+            act_p = np.ascontiguousarray([l.get("activation_params", (0.0, 0.0)) for l in p.layers], dtype=np.float32)
+            native.check(lib.bsvi_bnn_set_activation_params(handle, act_p.ctypes.data_as(C.c_void_p), len(p.layers)))
         self._exact_data = bool(lib.bsvi_bnn_exact_data(handle))
         dev = self.device
         self.n_params = p.n_params

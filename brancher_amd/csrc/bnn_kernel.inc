@@ -137,26 +137,51 @@ struct BParams {
     // first row quad bnn_row_sums still takes (R1 / 4 then, else 0)
     uint32_t shared1, quad0;
     float* a1s; float* dpart; float* dbar; float* GT1;
+    // the parameters of the layers' activations (bsvi_bnn_set_activation_params, or torch's defaults): read by bnn_upper and
+    // bnn_predict_fwd for the kinds that have some.  Behind every other member, as `family` is
+    float act_p[BNN_MAX_LAYERS][2];
 };
 
-__device__ __forceinline__ float bnn_act(uint32_t act, float v) {
+// p: the layer's two parameters (BParams::act_p: leaky_relu's slope, elu's alpha, hardtanh's limits; the same expressions as
+// bnn_source.h's act_text / act_grad_text / act_pair_text)
+__device__ __forceinline__ float bnn_act(uint32_t act, float v, const float* p) {
     switch (act) {
     case BSVI_BNN_ACT_TANH: return tanhf(v);
     case BSVI_BNN_ACT_RELU: return fmaxf(v, 0.0f);
     case BSVI_BNN_ACT_SIGMOID: return sigmoidf_(v);
     case BSVI_BNN_ACT_SOFTPLUS: return v > 20.0f ? v : log1pf(expf(v));
+    case BSVI_BNN_ACT_LEAKY_RELU: return v > 0.0f ? v : p[0] * v;
+    case BSVI_BNN_ACT_ELU: return v > 0.0f ? v : p[0] * expm1f(v);
+    case BSVI_BNN_ACT_SELU: return (float)BSVI_SELU_SCALE * (v > 0.0f ? v : (float)BSVI_SELU_ALPHA * expm1f(v));
+    case BSVI_BNN_ACT_SOFTSIGN: return v / (1.0f + fabsf(v));
+    case BSVI_BNN_ACT_HARDTANH: return fminf(fmaxf(v, p[0]), p[1]);
+    case BSVI_BNN_ACT_SILU: return v * sigmoidf_(v);
+    case BSVI_BNN_ACT_GELU: return v * (0.5f * (1.0f + erff(v * BSVI_INV_SQRT2)));
     default: return v;
     }
 }
 // derivative of the activation through its OUTPUT y (what the forward sweep stored)
-__device__ __forceinline__ float bnn_act_grad(uint32_t act, float y) {
+__device__ __forceinline__ float bnn_act_grad(uint32_t act, float y, const float* p) {
     switch (act) {
     case BSVI_BNN_ACT_TANH: return 1.0f - y * y;
     case BSVI_BNN_ACT_RELU: return y > 0.0f ? 1.0f : 0.0f;
     case BSVI_BNN_ACT_SIGMOID: return y * (1.0f - y);
     case BSVI_BNN_ACT_SOFTPLUS: return y > 20.0f ? 1.0f : -expm1f(-y);
-    default: return 1.0f;
+    case BSVI_BNN_ACT_LEAKY_RELU: return y > 0.0f ? 1.0f : p[0];
+    case BSVI_BNN_ACT_ELU: return y > 0.0f ? 1.0f : y + p[0];
+    case BSVI_BNN_ACT_SELU: return y > 0.0f ? (float)BSVI_SELU_SCALE : y + (float)(BSVI_SELU_SCALE * BSVI_SELU_ALPHA);
+    case BSVI_BNN_ACT_SOFTSIGN: return (1.0f - fabsf(y)) * (1.0f - fabsf(y));
+    case BSVI_BNN_ACT_HARDTANH: return y > p[0] && y < p[1] ? 1.0f : 0.0f;
+    default: return 1.0f;      // NONE.  (SILU and GELU never come here: bnn_act_grad_from_input sends them to bnn_act_grad_input)
     }
+}
+// SILU and GELU are not monotone: their derivative through the PRE-activation v.  bnn_upper's forward sweep leaves it in the unit's delta
+// slot, which nothing reads before the reverse sweep multiplies it in place
+__device__ __forceinline__ bool bnn_act_grad_from_input(uint32_t act) { return act == BSVI_BNN_ACT_SILU || act == BSVI_BNN_ACT_GELU; }
+__device__ __forceinline__ float bnn_act_grad_input(uint32_t act, float v) {
+    if (act == BSVI_BNN_ACT_SILU) { const float sg = sigmoidf_(v); return sg * (1.0f + v * (1.0f - sg)); }
+    if (act == BSVI_BNN_ACT_GELU) return 0.5f * (1.0f + erff(v * BSVI_INV_SQRT2)) + v * (BSVI_INV_SQRT_2PI * expf(-0.5f * v * v));
+    return 1.0f;      // (no other kind: a kind added to bnn_act_grad_from_input gets its branch here)
 }
 
 // a scale head's sigma = a + b g(raw) and d sigma / d raw = b g'(raw): g softplus (as bnn_act writes it; torch's backward is 1 above the
@@ -491,14 +516,16 @@ __global__ void __launch_bounds__(256) bnn_upper(const BParams Q) {
         for (uint32_t h = 0; h < L1.rows; ++h) {
             float v = Q.a1T[(size_t)b * Q.NC + (size_t)h * Q.n_pad + n];
             if (L1.b0 != 0xFFFFFFFFu) v += W(L1.b0 - Q.R1 + h);
-            Y(L1, h) = bnn_act(L1.act, v);
+            Y(L1, h) = bnn_act(L1.act, v, Q.act_p[0]);
+            if (bnn_act_grad_from_input(L1.act)) Dl(L1, h) = bnn_act_grad_input(L1.act, v);
         }
         for (uint32_t l = 1; l < Q.n_layers; ++l) {
             const BnnLayerDev L = Q.layer[l], Lp = Q.layer[l - 1];
             for (uint32_t i = 0; i < L.rows; ++i) {
                 float s = L.b0 != 0xFFFFFFFFu ? W(L.b0 - Q.R1 + i) : 0.0f;
                 for (uint32_t j = 0; j < L.cols; ++j) s += W(L.w0 - Q.R1 + i * L.cols + j) * Y(Lp, j);
-                Y(L, i) = bnn_act(L.act, s);
+                Y(L, i) = bnn_act(L.act, s, Q.act_p[l]);
+                if (bnn_act_grad_from_input(L.act)) Dl(L, i) = bnn_act_grad_input(L.act, s);
             }
         }
         // ---- likelihood and d f / d logits (distributions.py:294-311 / 561-592 through torch: log_softmax, BCE with logits)
@@ -548,7 +575,7 @@ __global__ void __launch_bounds__(256) bnn_upper(const BParams Q) {
             for (uint32_t j = 0; j < L.cols; ++j) {
                 float s = 0.0f;
                 for (uint32_t i = 0; i < L.rows; ++i) s += W(L.w0 - Q.R1 + i * L.cols + j) * Dl(L, i);
-                Dl(Lp, j) = s * bnn_act_grad(Lp.act, Y(Lp, j));
+                Dl(Lp, j) = s * (bnn_act_grad_from_input(Lp.act) ? Dl(Lp, j) : bnn_act_grad(Lp.act, Y(Lp, j), Q.act_p[l - 1]));
             }
         }
         if (LDSW) {          // what bnn_small reads: every activation below the last layer, every delta
@@ -1154,6 +1181,8 @@ struct bsvi_bnn {
     // the shared first layer (bnn_select.h, shared_first): 0 not asked yet, 1 shared, -1 both products per sample.  Decided once, from
     // the point rows and BSVI_BNN_SHARED1 as they stand when the workspace is sized or the first launch is made (bnn_shared_first)
     mutable std::atomic<int> shared_state{0};
+    // the parameters of the layers' activations: torch's defaults (bnn_create) until bsvi_bnn_set_activation_params
+    float act_p[BNN_MAX_LAYERS][2] = {};
     mutable std::atomic<bool> launched{false};      // a launch was made: the priors stay as they are
     uint64_t act_floats = 0, delta_floats = 0;      // per (sample, minibatch row)
     uint32_t act_off[BNN_MAX_LAYERS] = {};
@@ -1194,6 +1223,8 @@ static bsvi_bnn_source::Net bnn_source_net(const bsvi_bnn* p) {
     N.R1 = p->R1; N.Rs = p->Rs; N.act_floats = (uint32_t)p->act_floats; N.C = p->C; N.B_pad = p->B_pad;
     N.likelihood = p->d.likelihood; N.family = p->family; N.scale_learn = p->scale_learn; N.heads = p->heads;
     memcpy(&N.head_a_bits, &p->head_a, 4); memcpy(&N.head_b_bits, &p->head_b, 4);
+    N.act_params_set = true;
+    memcpy(N.act_p, p->act_p, sizeof N.act_p);
     const char* e = getenv("BSVI_BNN_CAUCHY_LOG");
     N.cauchy_log1p = e && !strcmp(e, "log1p");
     return N;
@@ -1281,7 +1312,7 @@ static int bnn_create(const bsvi_bnn_desc* desc, const bool normal, const uint32
     for (uint32_t l = 0; l < desc->n_layers; ++l) {
         const bsvi_bnn_layer& L = desc->layers[l];
         if (!L.rows || L.cols != width) return fail(BSVI_ERR_INVALID, "layer shapes do not chain");
-        if (L.activation > BSVI_BNN_ACT_SOFTPLUS) return fail(BSVI_ERR_UNSUPPORTED, "unknown activation");
+        if (L.activation > BSVI_BNN_ACT_GELU) return fail(BSVI_ERR_UNSUPPORTED, "unknown activation");
         if ((uint64_t)L.weight_row0 + (uint64_t)L.rows * L.cols > R || (L.bias_row0 != 0xFFFFFFFFu && (uint64_t)L.bias_row0 + L.rows > R))
             return fail(BSVI_ERR_INVALID, "layer rows out of range");
         if (l == 0 && L.weight_row0 != 0) return fail(BSVI_ERR_INVALID, "the first layer's weights are rows [0, H1 P)");
@@ -1333,6 +1364,7 @@ static int bnn_create(const bsvi_bnn_desc* desc, const bool normal, const uint32
     if (normal) { p->LC = width; p->scale_u = scale_uniform; p->scale_stride = scale_stride; p->scale_learn = learn; }
     if (heads) { p->C = p->LC = width / 2u; p->heads = heads->transform; p->head_a = heads->a; p->head_b = heads->b; }
     for (uint32_t l = 0; l < desc->n_layers; ++l) { p->act_off[l] = (uint32_t)p->act_floats; p->act_floats += p->layers[l].rows; }
+    for (uint32_t l = 0; l < desc->n_layers; ++l) bsvi_bnn_source::act_default(p->layers[l].activation, p->act_p[l]);
     p->delta_floats = p->act_floats;
     {   // exact data: both products on the bf16 matrix cores (three MFMAs on the exact pieces of the other operand); BSVI_DENSE_XGEMM=0: f32
         const char* xe = getenv("BSVI_DENSE_XGEMM");
@@ -1508,6 +1540,31 @@ extern "C" int bsvi_bnn_set_point_rows(bsvi_bnn* p, const uint8_t* row_point, ui
     return BSVI_OK;
 }
 
+// the parameters of the layers' activations (include/bsvi.h).  Before the first launch only: the generated kernels carry them as literals
+// and are compiled at the first launch (or by bsvi_bnn_middle).  The pair of a layer whose kind has no parameter is not read and not kept
+extern "C" int bsvi_bnn_set_activation_params(bsvi_bnn* p, const float* params, uint32_t n_layers) {
+    if (!p || !params) return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_activation_params: null argument");
+    if (n_layers != p->d.n_layers) return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_activation_params: n_layers is not the model's number of layers");
+    if (p->launched.load() || p->upper_gen.state || p->mid_gen.state)
+        return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_activation_params: the model was launched already (set the parameters before the first launch)");
+    for (uint32_t l = 0; l < n_layers; ++l) {
+        const uint32_t a = p->layers[l].activation;
+        const float p0 = params[2 * l], p1 = params[2 * l + 1];
+        if (!std::isfinite(p0) || !std::isfinite(p1)) return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_activation_params: a parameter is not finite");
+        if (a == BSVI_BNN_ACT_LEAKY_RELU && !(p0 > 0.0f))
+            return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_activation_params: the negative_slope of a leaky_relu layer must be > 0");
+        if (a == BSVI_BNN_ACT_ELU && !(p0 > 0.0f)) return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_activation_params: the alpha of an elu layer must be > 0");
+        if (a == BSVI_BNN_ACT_HARDTANH && !(p0 < p1))
+            return fail(BSVI_ERR_INVALID, "bsvi_bnn_set_activation_params: the limits of a hardtanh layer need min_val < max_val");
+    }
+    for (uint32_t l = 0; l < n_layers; ++l) {
+        const uint32_t a = p->layers[l].activation;
+        if (a == BSVI_BNN_ACT_LEAKY_RELU || a == BSVI_BNN_ACT_ELU || a == BSVI_BNN_ACT_HARDTANH) p->act_p[l][0] = params[2 * l];
+        if (a == BSVI_BNN_ACT_HARDTANH) p->act_p[l][1] = params[2 * l + 1];
+    }
+    return BSVI_OK;
+}
+
 extern "C" void bsvi_bnn_destroy(bsvi_bnn* p) {
     if (!p) return;
     if (p->dev_blob) (void)hipFree(p->dev_blob);
@@ -1633,6 +1690,7 @@ static int bnn_fill(const bsvi_bnn* p, const bsvi_bnn_args* a, BParams& Q, BnnLa
         D.act_off = (uint32_t)(nb * p->act_off[l]); D.delta_off = D.act_off;
         D.in_off = l ? (uint32_t)(nb * p->act_off[l - 1]) : 0u;
     }
+    memcpy(Q.act_p, p->act_p, sizeof Q.act_p);
     Q.R = p->R; Q.R1 = p->R1; Q.Rs = p->Rs ? p->Rs : 1; Q.P = p->P; Q.C = p->C; Q.H1 = p->H1; Q.DS = p->d.dataset_size; Q.B = p->d.batch_size;
     Q.B_pad = p->B_pad; Q.Kp = p->Kp; Q.P_ld = p->P_ld; Q.n_local = a->n_samples_local; Q.n_pad = L.n_pad; Q.n_global = a->n_samples_global;
     Q.sample_base = a->sample_base; Q.NC = L.NC; Q.n_uniform_grad = p->d.n_uniform_grad; Q.likelihood = p->d.likelihood;
@@ -1897,7 +1955,7 @@ __global__ void __launch_bounds__(256) bnn_predict_fwd(const BParams Q, const Bn
         for (uint32_t h = 0; h < L1.rows; ++h) {
             float v = V.a1[(size_t)j * Q.NC + (size_t)h * Q.n_pad + n];
             if (L1.b0 != 0xFFFFFFFFu) v += W(L1.b0 - Q.R1 + h);
-            Y(cur, h) = bnn_act(L1.act, v);
+            Y(cur, h) = bnn_act(L1.act, v, Q.act_p[0]);
         }
         for (uint32_t l = 1; l < Q.n_layers; ++l) {
             const BnnLayerDev L = Q.layer[l];
@@ -1906,7 +1964,7 @@ __global__ void __launch_bounds__(256) bnn_predict_fwd(const BParams Q, const Bn
                 // (unrolled by four: eight reads in flight in front of four dependent FMAs, the additions in the same order)
 #pragma unroll 4
                 for (uint32_t k = 0; k < L.cols; ++k) s += W(L.w0 - Q.R1 + i * L.cols + k) * Y(cur, k);
-                Y(cur ^ 1u, i) = bnn_act(L.act, s);
+                Y(cur ^ 1u, i) = bnn_act(L.act, s, Q.act_p[l]);
             }
             cur ^= 1u;
         }
@@ -2074,6 +2132,7 @@ extern "C" int bsvi_bnn_predict(const bsvi_bnn* p, const bsvi_bnn_predict_args* 
         BnnLayerDev& D = Q.layer[l];
         D.rows = S.rows; D.cols = S.cols; D.w0 = S.weight_row0; D.b0 = S.bias_row0; D.act = S.activation;
     }
+    memcpy(Q.act_p, p->act_p, sizeof Q.act_p);
     Q.R = p->R; Q.R1 = p->R1; Q.Rs = p->Rs ? p->Rs : 1; Q.P = p->P; Q.C = p->C; Q.H1 = p->H1;
     Q.Kp = p->Kp; Q.P_ld = p->P_ld; Q.n_local = a->n_samples_local; Q.n_pad = L.n_pad; Q.n_global = a->n_samples_local;
     Q.sample_base = a->sample_base; Q.NC = L.NC; Q.likelihood = p->d.likelihood;

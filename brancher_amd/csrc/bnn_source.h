@@ -36,7 +36,36 @@ struct Net {
     bool scale_learn = false;
     uint32_t heads = 0, head_a_bits = 0, head_b_bits = 0;      // a scale head's BSVI_UT_* transform (0: none), a and b of sigma = a + b g(raw) as bits
     bool cauchy_log1p = false;               // BSVI_BNN_CAUCHY_LOG=log1p, read by the caller
+    // the parameters of the layers' activations (bsvi_bnn_set_activation_params); act_params_set false: torch's defaults (act_default)
+    bool act_params_set = false;
+    float act_p[MAX_LAYERS][2] = {};
 };
+
+// torch's defaults of the parametrised activations: leaky_relu's negative_slope, elu's alpha, hardtanh's (min_val, max_val)
+inline void act_default(uint32_t a, float p[2]) {
+    p[0] = a == BSVI_BNN_ACT_LEAKY_RELU ? 0.01f : (a == BSVI_BNN_ACT_ELU ? 1.0f : (a == BSVI_BNN_ACT_HARDTANH ? -1.0f : 0.0f));
+    p[1] = a == BSVI_BNN_ACT_HARDTANH ? 1.0f : 0.0f;
+}
+// SILU and GELU are not monotone: their derivative is taken from the pre-activation, where every other kind's is a function of the output
+inline bool act_grad_from_input(uint32_t a) { return a == BSVI_BNN_ACT_SILU || a == BSVI_BNN_ACT_GELU; }
+// selu's two constants as torch holds them, and their product
+#define BSVI_SELU_SCALE 1.0507009873554804934193349852946
+#define BSVI_SELU_ALPHA 1.6732632423543772848170429916717
+// gelu's 1 / sqrt(2) and 1 / sqrt(2 pi): ONE spelling for the static kernels (bnn_kernel.inc) and, as text, for the generated ones
+#define BSVI_INV_SQRT2 0.707106781f
+#define BSVI_INV_SQRT_2PI 0.398942280f
+#define BSVI_TEXT_(x) #x
+#define BSVI_TEXT(x) BSVI_TEXT_(x)
+
+// the activation of layer l with its parameters
+struct Act { uint32_t kind; float p[2]; };
+inline Act act_of(const Net& N, uint32_t l) {
+    Act a;
+    a.kind = N.layer[l].activation;
+    if (N.act_params_set) { a.p[0] = N.act_p[l][0]; a.p[1] = N.act_p[l][1]; }
+    else act_default(a.kind, a.p);
+    return a;
+}
 
 inline std::string fmt(const char* f, ...) {
     char buf[512];
@@ -47,24 +76,54 @@ inline std::string fmt(const char* f, ...) {
     return std::string(buf);
 }
 
-inline std::string act_text(uint32_t a, const std::string& v) {
-    switch (a) {
+// a finite float as a literal that reads back to the same bits (nine significant digits)
+inline std::string flit(float x) {
+    std::string s = fmt("%.9g", (double)x);
+    if (s.find_first_of(".e") == std::string::npos) s += ".0";
+    return s + "f";
+}
+
+// v: the NAME of the pre-activation (it is read more than once)
+inline std::string act_text(const Act& a, const std::string& v) {
+    switch (a.kind) {
     case BSVI_BNN_ACT_TANH: return "tanhf(" + v + ")";
     case BSVI_BNN_ACT_RELU: return "fmaxf(" + v + ", 0.0f)";
     case BSVI_BNN_ACT_SIGMOID: return "sigmoidf_(" + v + ")";
     case BSVI_BNN_ACT_SOFTPLUS: return "((" + v + ") > 20.0f ? (" + v + ") : log1pf(expf(" + v + ")))";
+    case BSVI_BNN_ACT_LEAKY_RELU: return "(" + v + " > 0.0f ? " + v + " : " + flit(a.p[0]) + " * " + v + ")";
+    case BSVI_BNN_ACT_ELU: return "(" + v + " > 0.0f ? " + v + " : " + flit(a.p[0]) + " * expm1f(" + v + "))";
+    case BSVI_BNN_ACT_SELU:
+        return "(" + flit((float)BSVI_SELU_SCALE) + " * (" + v + " > 0.0f ? " + v + " : " + flit((float)BSVI_SELU_ALPHA) + " * expm1f(" + v + ")))";
+    case BSVI_BNN_ACT_SOFTSIGN: return "(" + v + " / (1.0f + fabsf(" + v + ")))";
+    case BSVI_BNN_ACT_HARDTANH: return "fminf(fmaxf(" + v + ", " + flit(a.p[0]) + "), " + flit(a.p[1]) + ")";
+    case BSVI_BNN_ACT_SILU: return "(" + v + " * sigmoidf_(" + v + "))";
+    case BSVI_BNN_ACT_GELU: return "(" + v + " * (0.5f * (1.0f + erff(" + v + " * " BSVI_TEXT(BSVI_INV_SQRT2) "))))";
     default: return v;
     }
 }
 // through the OUTPUT of the activation
-inline std::string act_grad_text(uint32_t a, const std::string& y) {
-    switch (a) {
+inline std::string act_grad_text(const Act& a, const std::string& y) {
+    switch (a.kind) {
     case BSVI_BNN_ACT_TANH: return "(1.0f - " + y + " * " + y + ")";
     case BSVI_BNN_ACT_RELU: return "(" + y + " > 0.0f ? 1.0f : 0.0f)";
     case BSVI_BNN_ACT_SIGMOID: return "(" + y + " * (1.0f - " + y + "))";
     case BSVI_BNN_ACT_SOFTPLUS: return "(" + y + " > 20.0f ? 1.0f : -expm1f(-" + y + "))";
+    case BSVI_BNN_ACT_LEAKY_RELU: return "(" + y + " > 0.0f ? 1.0f : " + flit(a.p[0]) + ")";
+    case BSVI_BNN_ACT_ELU: return "(" + y + " > 0.0f ? 1.0f : " + y + " + " + flit(a.p[0]) + ")";
+    case BSVI_BNN_ACT_SELU:
+        return "(" + y + " > 0.0f ? " + flit((float)BSVI_SELU_SCALE) + " : " + y + " + " + flit((float)(BSVI_SELU_SCALE * BSVI_SELU_ALPHA)) + ")";
+    case BSVI_BNN_ACT_SOFTSIGN: return "((1.0f - fabsf(" + y + ")) * (1.0f - fabsf(" + y + ")))";
+    case BSVI_BNN_ACT_HARDTANH: return "(" + y + " > " + flit(a.p[0]) + " && " + y + " < " + flit(a.p[1]) + " ? 1.0f : 0.0f)";
     default: return std::string("1.0f");
     }
+}
+// SILU | GELU: the statement that leaves act(v) in `y` and act'(v) in `d`, the unit's delta slot, which nothing reads before the reverse
+// sweep multiplies it in place (sigma (1 + v (1 - sigma)) | Phi(v) + v phi(v))
+inline std::string act_pair_text(const Act& a, const std::string& v, const std::string& y, const std::string& d) {
+    if (a.kind == BSVI_BNN_ACT_SILU)
+        return "{ const float sg = sigmoidf_(" + v + "); " + y + " = " + v + " * sg; " + d + " = sg * (1.0f + " + v + " * (1.0f - sg)); }";
+    return "{ const float cdf = 0.5f * (1.0f + erff(" + v + " * " BSVI_TEXT(BSVI_INV_SQRT2) ")); " + y + " = " + v + " * cdf; " + d + " = cdf + " + v +
+           " * (" BSVI_TEXT(BSVI_INV_SQRT_2PI) " * expf(-0.5f * " + v + " * " + v + ")); }";
 }
 
 // what both translation units open with, up to their argument struct
@@ -87,7 +146,14 @@ inline std::string forward_sweep(const Net& N, const char* w, const char* a1) {
     std::string s = "#pragma unroll\n";
     s += fmt("        for (uint32_t h = 0; h < %uu; ++h) {\n            float v = %s;\n", L0.rows, a1);
     if (L0.bias_row0 != NO_BIAS) s += fmt("            v += %s[%uu + h];\n", w, L0.bias_row0 - N.R1);
-    s += "            y[" + fmt("%uu", N.act_off[0]) + " + h] = " + act_text(L0.activation, "v") + ";\n        }\n";
+    // (a kind whose derivative needs the pre-activation leaves it in the unit's delta slot: act_pair_text)
+    auto store = [&](uint32_t l, const char* unit, const char* v) {
+        const std::string at = fmt("[%uu + %s]", N.act_off[l], unit);
+        const Act a = act_of(N, l);
+        if (act_grad_from_input(a.kind)) return "            " + act_pair_text(a, v, "y" + at, "d" + at) + "\n        }\n";
+        return "            y" + at + " = " + act_text(a, v) + ";\n        }\n";
+    };
+    s += store(0, "h", "v");
     for (uint32_t l = 1; l < N.n_layers; ++l) {
         const bsvi_bnn_layer& L = N.layer[l];
         s += "#pragma unroll\n";
@@ -95,7 +161,7 @@ inline std::string forward_sweep(const Net& N, const char* w, const char* a1) {
         s += L.bias_row0 != NO_BIAS ? fmt("            float sm = %s[%uu + i];\n", w, L.bias_row0 - N.R1) : std::string("            float sm = 0.0f;\n");
         s += "#pragma unroll\n";
         s += fmt("            for (uint32_t j = 0; j < %uu; ++j) sm += %s[%uu + i * %uu + j] * y[%uu + j];\n", L.cols, w, L.weight_row0 - N.R1, L.cols, N.act_off[l - 1]);
-        s += "            y[" + fmt("%uu", N.act_off[l]) + " + i] = " + act_text(L.activation, "sm") + ";\n        }\n";
+        s += store(l, "i", "sm");
     }
     return s;
 }
@@ -105,11 +171,12 @@ inline std::string reverse_sweep(const Net& N, const char* w) {
     std::string s;
     for (uint32_t l = N.n_layers - 1; l >= 1; --l) {
         const bsvi_bnn_layer& L = N.layer[l];
-        const bsvi_bnn_layer& Lp = N.layer[l - 1];
+        const Act ap = act_of(N, l - 1);
+        const std::string below = fmt("[%uu + j]", N.act_off[l - 1]);
         s += "#pragma unroll\n";
         s += fmt("        for (uint32_t j = 0; j < %uu; ++j) {\n            float sm = 0.0f;\n#pragma unroll\n", L.cols);
         s += fmt("            for (uint32_t i = 0; i < %uu; ++i) sm += %s[%uu + i * %uu + j] * d[%uu + i];\n", L.rows, w, L.weight_row0 - N.R1, L.cols, N.act_off[l]);
-        s += "            d[" + fmt("%uu", N.act_off[l - 1]) + " + j] = sm * " + act_grad_text(Lp.activation, "y[" + fmt("%uu", N.act_off[l - 1]) + " + j]") + ";\n        }\n";
+        s += "            d" + below + " = sm * " + (act_grad_from_input(ap.kind) ? "d" + below : act_grad_text(ap, "y" + below)) + ";\n        }\n";
     }
     return s;
 }

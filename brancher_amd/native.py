@@ -189,6 +189,7 @@ EXPORTS.update({
     "bsvi_bnn_set_likelihood_family": (C.c_int, [C.c_void_p, C.c_uint32]),
     "bsvi_bnn_set_scale_latents": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     "bsvi_bnn_set_point_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "bsvi_bnn_set_activation_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "bsvi_bnn_destroy": (None, [C.c_void_p]),
     "bsvi_bnn_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_uint32]),
     "bsvi_bnn_exact_data": (C.c_int, [C.c_void_p]),

@@ -774,11 +774,27 @@ def _bnn_widths(widths, n_features, hidden, n_outputs):
 
 
 def _bnn_activations(activations, activation, n_hidden_layers):
+    """one (name, keywords) per hidden layer: every entry a name of `BF` — tanh, relu, sigmoid, softplus, leaky_relu, elu, selu, softsign,
+    hardtanh, relu6, silu, gelu — or a pair (name, {keyword: number}), as ("leaky_relu", dict(negative_slope=0.2))"""
     if activations is None:
-        return [activation] * n_hidden_layers
+        activations = [activation] * n_hidden_layers
     if len(activations) != n_hidden_layers:
         raise ValueError("activations names one function per hidden layer: %d, not %d" % (n_hidden_layers, len(activations)))
-    return list(activations)
+    return [(a, {}) if isinstance(a, str) else (a[0], dict(a[1])) for a in activations]
+
+
+def _np_activation(name, kw):
+    """the teacher's activation in numpy (torch's definitions and defaults)"""
+    from math import erf
+    sigmoid = lambda v: 1. / (1. + np.exp(-v))
+    selu = (1.0507009873554804934193349852946, 1.6732632423543772848170429916717)
+    lo, hi = (0., 6.) if name == "relu6" else (kw.get("min_val", -1.), kw.get("max_val", 1.))
+    return dict(tanh=np.tanh, relu=lambda v: np.maximum(v, 0.), sigmoid=sigmoid, softplus=lambda v: np.log1p(np.exp(v)),
+                leaky_relu=lambda v: np.where(v > 0, v, kw.get("negative_slope", 0.01) * v),
+                elu=lambda v: np.where(v > 0, v, kw.get("alpha", 1.) * np.expm1(v)),
+                selu=lambda v: selu[0] * np.where(v > 0, v, selu[1] * np.expm1(v)), softsign=lambda v: v / (1. + np.abs(v)),
+                hardtanh=lambda v: np.clip(v, lo, hi), relu6=lambda v: np.clip(v, lo, hi), silu=lambda v: v * sigmoid(v),
+                gelu=lambda v: 0.5 * v * (1. + np.vectorize(erf)(v / np.sqrt(2.))))[name]
 
 
 def _bnn_scale_latents(scale_latent, tensor_names):
@@ -888,7 +904,8 @@ def build_bayesian_neural_network(api, dataset_size=48, batch_size=30, n_feature
     tanh saturates and every gradient of the first layer vanishes: the fixtures use a scale that keeps the units alive);
     q_loc_scale: posterior means drawn at that many posterior scales from zero; hidden2 > 0: a second hidden layer.
     widths: the full list of layer widths, features first, outputs last (it overrides n_features, n_hidden, hidden2 and n_classes: any
-    depth); activations: one name per hidden layer (default: `activation` everywhere).  pixels="integers" / "normal": the features of
+    depth); activations: one name per hidden layer, or a pair (name, {keywords}) as ("leaky_relu", dict(negative_slope=0.2))
+    (`_bnn_activations`; default: `activation` everywhere).  pixels="integers" / "normal": the features of
     `build_bnn_regression` (-3 .. 3, exactly bf16 | standard normal).  teacher: an integer — the labels are what a fixed random linear
     map of the centred features (drawn from that seed, whatever `seed` is) ranks highest, so that there is something to learn and a
     second build with another `seed` is held-out data of the same task (examples/bnn_predict.py); None: uniformly random labels.
@@ -927,7 +944,7 @@ def build_bayesian_neural_network(api, dataset_size=48, batch_size=30, n_feature
         b = prior_of("b%d" % l, (rows, 1))
         w = prior_of("weights%d" % l, (rows, cols))
         pre = BF.matmul(w, layer) + b
-        layer = getattr(BF, acts[l - 1])(pre) if l + 1 < len(widths) else pre
+        layer = getattr(BF, acts[l - 1][0])(pre, **acts[l - 1][1]) if l + 1 < len(widths) else pre
         sw = q_scale1 if (l == 1 and q_scale1 is not None) else q_scale
         q_vars.append(posterior_of(q_loc_scale * q_scale * rng.normal(0., 1., (rows, 1)), q_scale * np.ones((rows, 1)), "b%d" % l))
         q_vars.append(posterior_of(q_loc_scale * sw * rng.normal(0., 1., (rows, cols)), sw * np.ones((rows, cols)), "weights%d" % l))
@@ -954,7 +971,8 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
     come from a teacher network of the same shape plus noise of scale sigma.  Posterior means are drawn at `q_loc_scale` posterior
     scales from zero, and the scale of the first layer (default 0.4 / sqrt(sum_p E x_p^2)) keeps every hidden unit off saturation.
     widths: the full list of layer widths, features first, outputs last (it overrides n_features, n_hidden, hidden2 and n_outputs: any
-    depth); activations: one name per hidden layer (default: `activation` everywhere).  learnable_sigma: True — the reference's idiom,
+    depth); activations: one name per hidden layer, or a pair (name, {keywords}) (`_bnn_activations`; default: `activation` everywhere;
+    the teacher applies the same functions).  learnable_sigma: True — the reference's idiom,
     `NormalVariable(chain, sigma, "y", learnable=True)`: a learnable root `y_scale` behind a softplus in the joint model's parameter
     group; "exp" — `BF.exp` of a learnable root `y_log_scale`; the model's sigma then starts at sigma_init (one number or one per
     output; default: the teacher's sigma).  prior / prior_loc: as for `build_bayesian_neural_network` (the Bayesian lasso is
@@ -1000,7 +1018,7 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
         trunk = h
         h = h @ wt.T + (0.3 * rng.normal(0., 1., widths[l]) if bias else 0.)
         if l + 1 < len(widths):
-            h = np_acts[acts[l - 1]](h)
+            h = _np_activation(*acts[l - 1])(h)
     if scale_head:
         # the teacher's noise scale: a head of its own on the teacher's trunk, half-unit pre-activations about -1
         g = dict(softplus=np_acts["softplus"], exp=np.exp, sigmoid=np_acts["sigmoid"])[scale_head]
@@ -1024,7 +1042,7 @@ def build_bnn_regression(api, dataset_size=40, batch_size=17, n_features=64, n_h
         if bias:
             pre = pre + prior_of("b%d" % l, (rows, 1))
             q_vars.append(posterior_of(q_loc_scale * q_scale * rng.normal(0., 1., (rows, 1)), q_scale * np.ones((rows, 1)), "b%d" % l))
-        trunk, layer = layer, (getattr(BF, acts[l - 1])(pre) if l + 1 < len(widths) else pre)
+        trunk, layer = layer, (getattr(BF, acts[l - 1][0])(pre, **acts[l - 1][1]) if l + 1 < len(widths) else pre)
         q_vars.append(posterior_of(q_loc_scale * sw * rng.normal(0., 1., (rows, cols)), sw * np.ones((rows, cols)), "weights%d" % l))
     if scale_head:
         rows, cols = n_outputs, widths[-2]

@@ -18,6 +18,7 @@ MI355X:
     python examples/bnn_regression.py --hierarchical     # a latent prior scale per layer: NormalVariable(0, tau1, "weights1"), tau1 LogNormal
     python examples/bnn_regression.py --point weights1,b1     # a deterministic trunk under a Bayesian last layer: RootVariable("weights1"), ...
     python examples/bnn_regression.py --map              # every tensor a point estimate, trained with inference.MAP()
+    python examples/bnn_regression.py --activation gelu  # BF.gelu in the place of BF.tanh; with keywords: leaky_relu:negative_slope=0.2
 
 With --learn-sigma the model starts from a guess of 1.0 and learns the noise scale with the posterior (a learnable root `y_scale`
 behind a softplus in the joint model's parameter group, stepped from the second iteration on, as the reference steps it); the learned
@@ -87,6 +88,18 @@ elif "--point" in sys.argv[1:]:
         sys.exit("--point weights1,b1 (tensor names, comma-separated)")
 if POINT:
     KW.update(point=POINT)
+# --activation NAME[:k=v,...]: the function of the hidden layer — any of tanh, relu, sigmoid, softplus, leaky_relu, elu, selu, softsign,
+# hardtanh, relu6, silu, gelu — with its keywords, as `--activation leaky_relu:negative_slope=0.2` or `--activation hardtanh:min_val=-2,max_val=2`
+ACTIVATION = ("tanh", {})
+if "--activation" in sys.argv[1:]:
+    name, _, given = (sys.argv[sys.argv.index("--activation") + 1:] or [""])[0].partition(":")
+    try:
+        ACTIVATION = (name, {k: float(v) for k, v in (kv.split("=") for kv in given.split(",") if kv)})
+    except ValueError:
+        sys.exit("--activation NAME[:keyword=number,...]")
+    if not name:
+        sys.exit("--activation NAME[:keyword=number,...]")
+    KW.update(activations=[ACTIVATION])
 
 
 def value_of(params, name):
@@ -105,7 +118,7 @@ def posterior_mean_rmse(model):
     y = next(v for v in model.flatten() if v.name == "y")
     X, Y = dataset_of(next(v for v in model.flatten() if v.name == "x")), dataset_of(y.dataset)
     p = engine.compile_model(model).named_params()
-    hidden = np.tanh(X @ value_of(p, "weights1").reshape(KW["n_hidden"], -1).T + value_of(p, "b1").reshape(1, -1))
+    hidden = W._np_activation(*ACTIVATION)(X @ value_of(p, "weights1").reshape(KW["n_hidden"], -1).T + value_of(p, "b1").reshape(1, -1))
     pred = hidden @ value_of(p, "weights2").reshape(KW["n_outputs"], -1).T + value_of(p, "b2").reshape(1, -1)
     if LIKELIHOOD != "normal":
         print("    median |error| of the posterior-mean prediction: %.3f" % float(np.median(np.abs(pred - Y))))

@@ -546,7 +546,11 @@ int bsvi_dense_step(const bsvi_dense* d, const bsvi_dense_args* args, const bsvi
  *  H_l x H_l-1 products evaluated per (sample, minibatch row).  Replaces the same reference lines as bsvi_dense_* for this graph.
  * ========================================================================================= */
 typedef enum bsvi_bnn_activation {
-    BSVI_BNN_ACT_NONE = 0, BSVI_BNN_ACT_TANH = 1, BSVI_BNN_ACT_RELU = 2, BSVI_BNN_ACT_SIGMOID = 3, BSVI_BNN_ACT_SOFTPLUS = 4
+    BSVI_BNN_ACT_NONE = 0, BSVI_BNN_ACT_TANH = 1, BSVI_BNN_ACT_RELU = 2, BSVI_BNN_ACT_SIGMOID = 3, BSVI_BNN_ACT_SOFTPLUS = 4,
+    /* torch.nn.functional's leaky_relu (negative_slope), elu (alpha), selu, softsign, hardtanh (min_val, max_val; relu6 is (0, 6)), silu and
+     * gelu (approximate="none"); the parameters: bsvi_bnn_set_activation_params, torch's defaults without it */
+    BSVI_BNN_ACT_LEAKY_RELU = 5, BSVI_BNN_ACT_ELU = 6, BSVI_BNN_ACT_SELU = 7, BSVI_BNN_ACT_SOFTSIGN = 8, BSVI_BNN_ACT_HARDTANH = 9,
+    BSVI_BNN_ACT_SILU = 10, BSVI_BNN_ACT_GELU = 11
 } bsvi_bnn_activation;
 
 typedef struct bsvi_bnn_layer {
@@ -680,6 +684,15 @@ int bsvi_bnn_set_scale_latents(bsvi_bnn* b, uint32_t n_latents, const uint8_t* r
  * launch is BSVI_ERR_INVALID.  Without the call (or with every byte 0) no row is a point, and such a model runs the kernels it ran;
  * bsvi_bnn_predict uses the value for the point rows.  No struct changes, the ABI version stays. */
 int bsvi_bnn_set_point_rows(bsvi_bnn* b, const uint8_t* row_point, uint32_t n_rows);
+/* The PARAMETERS of the layers' activations: params[l][0], params[l][1] of layer l — LEAKY_RELU: (negative_slope s > 0, unused),
+ * ELU: (alpha > 0, unused), HARDTANH: (min_val, max_val) with min_val < max_val; the pair of a layer of any other kind is not read.
+ * Without the call torch's defaults hold: s = 0.01, alpha = 1, (-1, 1).  Valid after any of the create calls and before the first launch
+ * (the generated kernels carry the values as literals): a null pointer, n_layers other than the model's, a non-finite value (of any
+ * layer), s <= 0, alpha <= 0, min_val >= max_val or a call after a launch is BSVI_ERR_INVALID.  The derivative of every kind but
+ * SILU and GELU is taken from the layer's stored output (at the kinks: s, alpha, lambda alpha_0, 1, 1 at v = 0 and 0 at hardtanh's two limits,
+ * torch's values); SILU and GELU are not monotone — the forward sweep leaves act'(v) where the unit's delta will stand and the reverse
+ * sweep multiplies in place.  bsvi_bnn_predict applies the same forward values.  No struct changes, the ABI version stays. */
+int bsvi_bnn_set_activation_params(bsvi_bnn* b, const float* params /* [n_layers][2] */, uint32_t n_layers);
 /* The SHARED FIRST LAYER: when every row of weights1 (the first H1 x n_features rows) is a point row, all samples see the same weights1;
  * the launches then take the first product once (a1 = W1 x, broadcast to the samples), sum d f / d a1 over the samples in a fixed order
  * (no atomics: results are the same bits from run to run) and take ONE second product; no per-sample copy of weights1 is written and
