@@ -13,7 +13,12 @@ and nothing synchronises with the host inside the loop.  Deviations, on purpose:
   * one loss entry per iteration (the reference appends twice per good iteration,
     `inference.py:105,108`, which makes ``np.array(loss_list)`` raise under numpy >= 1.24);
   * "Numerical error, skipping sample" warnings are emitted after the loop (the flags are
-    read back once), not inside it.
+    read back once), not inside it;
+  * ``SteinVariationalGradientDescent.correct_gradient`` REPELS.  The reference (`inference.py:308-315`, "work in progress") adds
+    ``(theta_i - theta_j) K_ij / bw`` to the gradient of particle i, and a descent step along it pulls the particles together:
+    run on two one-dimensional particles at 0 and 1 with zero gradients (bandwidth 2 / log 2 = 2.885) it hands back -0.2914 for the
+    particle at 0 and +0.2914 for the one at 1, so both step towards each other.  Here the term has the sign of Liu & Wang (2016),
+    ``-(theta_i - theta_j) K_ij / bw``: +0.2914 and -0.2914 on the same input.
 """
 import warnings
 from abc import ABC, abstractmethod
@@ -82,7 +87,8 @@ def perform_inference(joint_model, number_iterations, number_samples=1,
     inference_method.post_process(joint_model)
     # torch modules used as links are trained IN PLACE by the reference (their nn.Parameters belong to the optimizers,
     # `optimizers.py:36-49`); here their tensors live in the engine's parameter buffer: written back
-    for link in engine.module_links_of(joint_model, posterior_model):
+    posteriors = posterior_model if isinstance(posterior_model, (list, tuple)) else [posterior_model]     # (a list: particles)
+    for link in engine.module_links_of(joint_model, *posteriors):
         link.sync_to_module()
 
 
@@ -165,3 +171,120 @@ class MAP(ReverseKL):
             pretraining_iterations, **opt_params):
         return super().run(joint_model, posterior_model, sampler_model, number_iterations, 1, optimizer,
                            pretraining_iterations, **opt_params)
+
+
+class _ParticleLoss:
+    """the sum of the particles' losses with the protocol the loop of `perform_inference` expects: ``backward()`` marks the gradient
+    block of every particle's compiled program (each evaluation wrote its own) as the gradient of this value"""
+
+    def __init__(self, losses):
+        import torch
+        self.losses = losses
+        self.tensor = torch.stack([loss.tensor for loss in losses]).sum()
+
+    def detach(self):
+        return self.tensor.detach()
+
+    def backward(self):
+        for loss in self.losses:
+            loss.backward()
+
+
+class SteinVariationalGradientDescent(InferenceMethod):
+    """Stein variational gradient descent (Liu & Wang 2016; `inference.py:277-327`): the posterior is a LIST of particles, each a model of
+    learnable RootVariables named like the latents — what `MAP` takes, N times.  ``compute_loss`` is the sum of the particles' MAP losses
+    (one compiled program and one launch per particle, loss and gradient together); ``correct_gradient`` couples the gradients on the
+    device (`bsvi_svgd_direction`, csrc/svgd_kernel.hip: RBF kernel, the reference's median bandwidth unless ``bandwidth`` fixes it) and
+    writes them back into the particles' gradient blocks, which ``ProbabilisticOptimizer.update()`` then steps with any optimizer.
+    ``bandwidth`` holds the last bandwidth used once a run has ended.  The repulsion has the sign of the paper, not the reference's (the
+    module docstring)."""
+    MIN_PARTICLES, MAX_PARTICLES = 2, 256
+
+    def __init__(self, bandwidth=None):
+        self.learnable_model = False
+        self.needs_sampler = False
+        self.learnable_sampler = False
+        if bandwidth is not None and not (np.isfinite(bandwidth) and bandwidth > 0):
+            raise ValueError("bandwidth is None (the median rule) or a positive number")
+        self.fixed_bandwidth = bandwidth
+        self.bandwidth = bandwidth
+        self._map = MAP()
+        self._plan = None
+
+    @staticmethod
+    def _roots(particle):
+        """the particle's variables in the one order every particle is laid out in: by name"""
+        return sorted(particle.flatten(), key=lambda var: var.name)
+
+    def check_model_compatibility(self, joint_model, posterior_model, sampler_model):
+        from brancher_amd.variables import ProbabilisticModel, RootVariable
+        if not isinstance(posterior_model, (list, tuple)) or not all(isinstance(p, ProbabilisticModel) for p in posterior_model):
+            raise ValueError("SteinVariationalGradientDescent: posterior_model is a list of particles, each a ProbabilisticModel of learnable RootVariables")
+        if not self.MIN_PARTICLES <= len(posterior_model) <= self.MAX_PARTICLES:
+            raise ValueError("SteinVariationalGradientDescent: {} particles, the method takes {} .. {}".format(
+                len(posterior_model), self.MIN_PARTICLES, self.MAX_PARTICLES))
+        first = None
+        for index, particle in enumerate(posterior_model):
+            members = particle.flatten()
+            # (a random variable first: its constants are roots that are not learnable, and it is the random variable that is to be named)
+            for var in [v for v in members if not isinstance(v, RootVariable)] + [v for v in members if not getattr(v, "learnable", True)]:
+                raise ValueError("SteinVariationalGradientDescent: particle {}: variable {!r} is a {}, a particle holds learnable "
+                                 "RootVariables only".format(index, var.name, type(var).__name__ if not isinstance(var, RootVariable)
+                                                             else "RootVariable that is not learnable"))
+            layout = [(var.name, tuple(var.parameter.shape)) for var in self._roots(particle)]
+            if first is None:
+                first = layout
+            names, names0 = [n for n, _ in layout], [n for n, _ in first]
+            if names != names0:
+                odd = sorted(set(names) ^ set(names0)) or names
+                raise ValueError("SteinVariationalGradientDescent: particle {}: variable {!r} is not in every particle (particle 0 holds {})".format(
+                    index, odd[0], ", ".join(names0)))
+            for (name, shape), (_, shape0) in zip(layout, first):
+                if shape != shape0:
+                    raise ValueError("SteinVariationalGradientDescent: particle {}: variable {!r} has shape {}, particle 0 has {}".format(
+                        index, name, shape, shape0))
+
+    def compute_loss(self, joint_model, posterior_model, sampler_model, number_samples, input_values={}):
+        return _ParticleLoss([self._map.compute_loss(joint_model, particle, sampler_model, 1, input_values) for particle in posterior_model])
+
+    def _build_plan(self, posterior_model):
+        """once per list of particles: where every particle's values and gradients live (index tensors on the device, in the order of
+        `_roots`) and the [N][D] buffers the kernels work on"""
+        import torch
+        from brancher_amd.native import OUT_HEADER
+        rows = []
+        for index, particle in enumerate(posterior_model):
+            pars = [var.parameter for var in self._roots(particle)]
+            stores = {id(par._store) for par in pars}
+            if None in {par._store for par in pars} or len(stores) != 1:
+                raise RuntimeError("particle {} is not part of one compiled model yet: evaluate the loss first".format(index))
+            store = pars[0]._store
+            idx = torch.from_numpy(np.concatenate([np.arange(par._offset, par._offset + par.size) for par in pars]).astype(np.int64)).to(store.device)
+            rows.append((store, idx, idx + OUT_HEADER))
+        device, dim = rows[0][0].device, rows[0][1].numel()
+        if any(idx.numel() != dim or store.device != device for store, idx, _ in rows):
+            raise RuntimeError("the particles differ in size or live on several devices")
+        return dict(key=tuple(id(p) for p in posterior_model), rows=rows, workspace=None,
+                    theta=torch.empty(len(rows), dim, device=device), grad=torch.empty(len(rows), dim, device=device),
+                    bandwidth=torch.zeros(1, device=device))
+
+    def correct_gradient(self, joint_model, posterior_model, sampler_model, number_samples, input_values={}):
+        import torch
+        from brancher_amd import native
+        if self._plan is None or self._plan["key"] != tuple(id(p) for p in posterior_model):
+            self._plan = self._build_plan(posterior_model)
+        plan = self._plan
+        theta, grad = plan["theta"], plan["grad"]
+        for row, (store, idx, idx_out) in enumerate(plan["rows"]):
+            if not getattr(store, "grads_valid", False):
+                raise RuntimeError("no gradients: call compute_loss(...).backward() before correct_gradient()")
+            torch.index_select(store.params, 0, idx, out=theta[row])
+            torch.index_select(store.out, 0, idx_out, out=grad[row])
+        plan["workspace"] = native.svgd_direction(theta, grad, grad, bandwidth=self.fixed_bandwidth, bandwidth_out=plan["bandwidth"],
+                                                  workspace=plan["workspace"])
+        for row, (store, idx, idx_out) in enumerate(plan["rows"]):
+            store.out.index_copy_(0, idx_out, grad[row])
+
+    def post_process(self, joint_model):
+        if self._plan is not None:
+            self.bandwidth = float(self._plan["bandwidth"].item())

@@ -446,6 +446,37 @@ class ReduceNode:
             pass
 
 
+# Stein variational gradient descent: the step that couples the particles (csrc/svgd_kernel.hip)
+EXPORTS.update({
+    "bsvi_svgd_workspace_bytes": (C.c_size_t, [C.c_uint32, C.c_uint64]),
+    "bsvi_svgd_direction": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_float, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
+})
+
+
+def svgd_direction(theta, grad, out, dim=None, bandwidth=None, bandwidth_out=None, workspace=None):
+    """bsvi_svgd_direction on device tensors [N][ld] (f32, rows contiguous): `out` (may be `grad`) receives the coupled gradients of the
+    first `dim` columns, `bandwidth_out` (one float on the device, or None) the bandwidth used; bandwidth None / <= 0: the median rule.
+    Returns the workspace, for the next call of the same shape."""
+    import torch
+    lib = load()
+    n, ld = theta.shape
+    dim = ld if dim is None else int(dim)
+    for name, x in (("theta", theta), ("grad", grad), ("out", out)):
+        if x.dtype != torch.float32 or tuple(x.shape) != (n, ld) or not x.is_contiguous() or not x.is_cuda:
+            raise ValueError("svgd_direction: {} is not a contiguous f32 device tensor of shape {}".format(name, (n, ld)))
+    need = lib.bsvi_svgd_workspace_bytes(n, dim)
+    if need == 0:
+        check(-1)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=theta.device)
+    with torch.cuda.device(theta.device):
+        check(lib.bsvi_svgd_direction(theta.data_ptr(), grad.data_ptr(), out.data_ptr(), n, dim, ld,
+                                      float(bandwidth) if bandwidth else 0.0, bandwidth_out.data_ptr() if bandwidth_out is not None else None,
+                                      workspace.data_ptr(), torch.cuda.current_stream().cuda_stream))
+    return workspace
+
+
 # bsvi_struct_kind (include/bsvi.h) -> the ctypes mirror of the struct: load() checks every size against bsvi_sizeof()
 STRUCT_KINDS = {0: UniformEntry, 1: Record, 2: ProgramDesc, 3: ElboArgs, 4: OptCfg, 5: DenseDesc, 6: DenseArgs, 7: MlpLayer,
                 8: AmortDesc, 9: AmortArgs, 10: MvnInsn, 11: MvnDesc, 12: MvnArgs, 13: BnnLayer, 14: BnnDesc, 15: BnnArgs,

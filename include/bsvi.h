@@ -1125,6 +1125,24 @@ int bsvi_train_persistent_minibatch(const bsvi_program* p, const bsvi_elbo_args*
 size_t bsvi_program_source_minibatch(const bsvi_program_desc* desc, int variant, uint32_t n_sources, const uint32_t* geometry,
                                      char* buf, size_t capacity);
 
+/* (ABI 11, entry points added without a change to any struct) Stein variational gradient descent (Liu & Wang 2016; the reference's
+ * inference.py:277-327, SteinVariationalGradientDescent.correct_gradient + update_bandwidth): the step that couples N particles.
+ * theta_dev [n_particles][ld] holds the particles, grad_dev [n_particles][ld] the gradient of each particle's own loss -log p, both f32,
+ * columns 0 .. dim - 1 of every row; out_dev [n_particles][ld] receives
+ *   out_i = sum_j K_ij grad_j - (1 / bw) (theta_i sum_j K_ij - sum_j K_ij theta_j),   K_ij = exp(-|theta_i - theta_j|^2 / (2 bw)),
+ * the second term the repulsion written as a gradient of the loss (the reference adds it with the other sign, an attraction: DESIGN.md
+ * 4.8), no 1 / N factor, as in the reference.  out_dev may be grad_dev; it may not overlap theta_dev.  bandwidth > 0 fixes bw;
+ * bandwidth <= 0 selects the reference's rule bw = 2 median_{i != j}(|theta_i - theta_j|)^2 / log(n_particles), the exact median (the
+ * mean of the two middle values when their count is even).  bandwidth_out_dev (or NULL) receives the bw used, one float.
+ * Three launches on `stream`, sums in a fixed order: the same inputs give the same bits.  Served: 2 <= n_particles <= 256,
+ * 1 <= dim <= ld, n_particles * ld < 2^31; anything else is BSVI_ERR_INVALID with the limit in the message.  With the median rule the
+ * call waits for the stream and reads one word back: when all particles coincide the rule gives bw = 0, the call returns
+ * BSVI_ERR_INVALID saying so and out_dev is not written (no NaN).  With a fixed bandwidth nothing synchronises.
+ * workspace_dev: bsvi_svgd_workspace_bytes(n_particles, dim) bytes of device memory, 16-byte aligned (0: shape not served). */
+size_t bsvi_svgd_workspace_bytes(uint32_t n_particles, uint64_t dim);
+int bsvi_svgd_direction(const float* theta_dev, const float* grad_dev, float* out_dev, uint32_t n_particles, uint64_t dim, uint64_t ld,
+                        float bandwidth, float* bandwidth_out_dev, void* workspace_dev, void* stream);
+
 const char* bsvi_last_error(void);
 int bsvi_abi_version(void);
 /* number of gfx950 devices visible to the HIP runtime (0 if none) */
