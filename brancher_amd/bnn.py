@@ -661,6 +661,29 @@ def row_parameters(p, theta=None):
     return values[p.row_uniform[0]], values[p.row_uniform[1]]
 
 
+MIN_PARTICLES, MAX_PARTICLES = 2, 256                                  # BNN_MIN_PARTICLES, BNN_MAX_PARTICLES (csrc/bnn_particles.inc)
+
+
+def check_particles(p, n_particles):
+    """what `bsvi_bnn_particles_fwd_bwd` serves, asked of a lowered program before any device work (the library asks the same of its
+    handle); every refusal is a ValueError that names the feature or the limit"""
+    where = "batched particles (bsvi_bnn_particles_fwd_bwd): "
+    if not MIN_PARTICLES <= n_particles <= MAX_PARTICLES:
+        raise ValueError(where + "{} particles, served are {} .. {}".format(n_particles, MIN_PARTICLES, MAX_PARTICLES))
+    if p.scale_latents:
+        raise ValueError(where + "scale latents ({}) are not served".format(", ".join(l["name"] for l in p.scale_latents)))
+    if p.scale_learnable:
+        raise ValueError(where + "a learnable sigma is not served (the scale of the likelihood must be a constant)")
+    if p.scale_head:
+        raise ValueError(where + "a scale head is not served (the scale of the likelihood must be a constant)")
+    if getattr(p, "estimator", "pathwise") != "pathwise":
+        raise ValueError(where + "the {} estimator is not served (a particle has no log q and no draw)".format(p.estimator))
+    random = [t["name"] for t in p.tensors if not t.get("point")]
+    if random:
+        raise ValueError(where + "not every row is a point row: {} has a Normal posterior (a particle is a model of learnable "
+                                 "RootVariables named like every tensor)".format(", ".join(random)))
+
+
 def make_desc(p):
     """bsvi_bnn_desc of a lowered program -> (desc, the arrays it points into: keep them alive as long as the desc)"""
     layers = (BnnLayer * len(p.layers))(*[BnnLayer(rows=l["rows"], cols=l["cols"], weight_row0=l["weight_row0"],

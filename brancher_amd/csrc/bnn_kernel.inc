@@ -1729,13 +1729,18 @@ static int bnn_fill(const bsvi_bnn* p, const bsvi_bnn_args* a, BParams& Q, BnnLa
     return BSVI_OK;
 }
 
-static int bnn_launch(const bsvi_bnn* p, const BParams& Q, const BnnLayout& L, hipStream_t s) {
+// row parameters, the minibatch and (latent prior scales) the latents' draws: the first launch of an iteration
+static void bnn_launch_head(const bsvi_bnn* p, const BParams& Q, hipStream_t s) {
     const uint32_t head_n = std::max(Q.R, Q.B_pad);
     const uint32_t head_blocks = (head_n + 255) / 256, gy = (std::max(Q.Kp, Q.P_ld) + 255) / 256;
     p->launched.store(true);
     const uint32_t lat_blocks = (Q.n_latents * Q.n_pad + 255u) / 256u;      // (none without latent prior scales)
     hipLaunchKernelGGL(bnn_head_gather, dim3(Q.B_pad * gy + head_blocks + lat_blocks), dim3(256), 0, s, Q, gy, head_blocks);
-    bnn_launch_draw(p, Q, L.row_chunks, s);
+}
+
+// from the weights of every sample (bnn_draw | bnn_particles_in) to their gradients per sample (GT | GT1, gsm) and likelihoods: the
+// first product, the middle kernel the network selects, the second product
+static int bnn_launch_products(const bsvi_bnn* p, const BParams& Q, hipStream_t s) {
     int rc;
     const bool mid = bnn_gen_ready(p, true);
     if (Q.shared1) {
@@ -1791,6 +1796,13 @@ static int bnn_launch(const bsvi_bnn* p, const BParams& Q, const BnnLayout& L, h
     }
     else if (Q.exact) rc = bsvi_xgemm_nt(Q.XbT_bf, nullptr, Q.dlogp, (long)Q.NC * Q.B_pad, Q.GT, (int)Q.NC, (int)Q.P, (int)Q.NC, (int)Q.B_pad, s);
     else rc = bsvi_gemm_f32(1, Q.da1T, (int)Q.B_pad, Q.Xb, (int)Q.P_ld, Q.GT, (int)Q.P_ld, (int)Q.NC, (int)Q.P, (int)Q.B_pad, s);
+    return rc;
+}
+
+static int bnn_launch(const bsvi_bnn* p, const BParams& Q, const BnnLayout& L, hipStream_t s) {
+    bnn_launch_head(p, Q, s);
+    bnn_launch_draw(p, Q, L.row_chunks, s);
+    const int rc = bnn_launch_products(p, Q, s);
     if (rc) return rc;
     bnn_launch_row_sums(p, Q, s);
     if (Q.n_latents) hipLaunchKernelGGL(bnn_latent_terms, dim3(Q.n_pad / 256u + (Q.n_pad % 256u ? 1u : 0u)), dim3(256), 0, s, Q);

@@ -200,7 +200,13 @@ class SteinVariationalGradientDescent(InferenceMethod):
     module docstring)."""
     MIN_PARTICLES, MAX_PARTICLES = 2, 256
 
-    def __init__(self, bandwidth=None):
+    def __init__(self, bandwidth=None, batched=False):
+        """``batched=True``: all particles of a Bayesian neural network in one pass (`_run_batched`); a model another path serves is
+        refused, not served particle by particle."""
+        self.batched = bool(batched)
+        if self.batched:
+            self.run = self._run_batched      # (an attribute of the instance: `perform_inference` hands the loop to a method with `run`)
+        self._program = None
         self.learnable_model = False
         self.needs_sampler = False
         self.learnable_sampler = False
@@ -243,6 +249,102 @@ class SteinVariationalGradientDescent(InferenceMethod):
                 if shape != shape0:
                     raise ValueError("SteinVariationalGradientDescent: particle {}: variable {!r} has shape {}, particle 0 has {}".format(
                         index, name, shape, shape0))
+        if self.batched and joint_model is not None:
+            self._program = self._batched_program(joint_model, posterior_model)
+
+    @staticmethod
+    def _batched_program(joint_model, particles):
+        """the lowered program of the Bayesian neural network all particles share (lowered with particle 0, no device work), or the
+        refusal: a model one of the paths in front of the BNN path serves (`engine.compile_model` asks them in this order) is named
+        with its path, and what `bsvi_bnn_particles_fwd_bwd` does not serve with the feature (`bnn.check_particles`)"""
+        from brancher_amd import bnn, dense, lowering
+        what = "SteinVariationalGradientDescent(batched=True): "
+        for path, lower in (("scalar path (CompiledELBO)", lowering.lower), ("dense-link path (CompiledDense)", dense.lower_dense)):
+            try:
+                lower(joint_model, particles[0], "pathwise")
+            except lowering.LoweringError:
+                continue
+            raise ValueError(what + "the model is served by the {}; the particles of a Bayesian neural network alone are evaluated in one "
+                                    "pass (the BNN path, CompiledBnn): use batched=False".format(path))
+        try:
+            program = bnn.lower_bnn(joint_model, particles[0], "pathwise")
+        except lowering.LoweringError as err:
+            raise ValueError(what + "the model is not a Bayesian neural network the BNN path serves ({})".format(err)) from None
+        bnn.check_particles(program, len(particles))
+        return program
+
+    def _build_batched_plan(self, joint_model, particles):
+        """once per list of particles: a CompiledBnn of its own (its handle takes both products per particle) whose parameter buffer and
+        output block are extended by the [N][ld] table of the particles and the table of their gradients — the particles' STORE: every
+        particle's parameters are bound to their row, in the latent vector's row order"""
+        import torch
+        from brancher_amd import bnn
+        from brancher_amd.native import OUT_HEADER
+        if self._program is None:
+            self._program = self._batched_program(joint_model, particles)
+        program = self._program
+        compiled = bnn.CompiledBnn(joint_model, particles[0], "pathwise", program=program)
+        n, dim = len(particles), program.n_rows
+        ld = (dim + 3) // 4 * 4
+        # the table starts a multiple of four floats into both buffers (16-byte rows), behind the handle's own parameters and gradients
+        # and one header of the optimizer step: its finite flag is out[base + 3]
+        base = (max(program.n_params, 1) + 3) // 4 * 4 + OUT_HEADER
+        table = np.zeros((n, ld), dtype=np.float32)
+        by_name = {t["name"]: t for t in program.tensors}
+        for row, particle in enumerate(particles):
+            for var in particle.flatten():
+                t = by_name[var.name]
+                table[row, t["row0"]:t["row0"] + t["size"]] = var.parameter.numpy().reshape(-1)
+        dev = compiled.device
+        params = torch.zeros(base + n * ld, device=dev)
+        params[:compiled.params.numel()] = compiled.params
+        params[base:] = torch.from_numpy(table.reshape(-1)).to(dev)
+        compiled.params, compiled.out = params, torch.zeros(OUT_HEADER + base + n * ld, device=dev)
+        for row, particle in enumerate(particles):
+            for var in particle.flatten():
+                var.parameter.bind(compiled, base + row * ld + by_name[var.name]["row0"])
+        mask = torch.zeros(n, ld, dtype=torch.uint8, device=dev)
+        mask[:, :dim] = 1
+        return dict(key=tuple(id(p) for p in particles), compiled=compiled, n=n, dim=dim, ld=ld, base=base, mask=mask.reshape(-1),
+                    theta=params[base:].view(n, ld), grad=compiled.out[OUT_HEADER + base:].view(n, ld), flag=compiled.out[base + 3:base + 4],
+                    loss=torch.zeros(n, device=dev), bandwidth=torch.zeros(1, device=dev), workspace=None, svgd_workspace=None)
+
+    def _run_batched(self, joint_model, posterior_model, sampler_model, number_iterations, number_samples, optimizer,
+                     pretraining_iterations, **opt_params):
+        """the loop of `perform_inference` for ``batched=True``, three native calls an iteration whatever the number of particles:
+        `bsvi_bnn_particles_fwd_bwd` on the table that IS the particles' parameter store (loss and gradient of every particle; one
+        minibatch, shared), `bsvi_svgd_direction` in place on the gradient table, one `bsvi_optimizer_step` over its N ld elements with
+        per-element state.  No gather, no scatter, no launch per particle.  A non-finite loss skips the step, as the loop does."""
+        import ctypes as C
+        import torch
+        from brancher_amd import native
+        if self._plan is None or self._plan["key"] != tuple(id(p) for p in posterior_model) or "compiled" not in self._plan:
+            self._plan = self._build_batched_plan(joint_model, posterior_model)
+        plan = self._plan
+        compiled, n, ld, base, theta, grad, loss = (plan[k] for k in ("compiled", "n", "ld", "base", "theta", "grad", "loss"))
+        cfg = native.make_opt_cfg(optimizer, **opt_params)
+        dev = compiled.device
+        K = int(number_iterations)
+        state = torch.zeros(4 * n * ld, device=dev)
+        curve, finite = torch.zeros(K, device=dev), torch.zeros(K, device=dev)
+        seed = int(compiled._seed(None))
+        for it in range(K):
+            plan["workspace"] = native.bnn_particles_fwd_bwd(compiled.handle, compiled.params, compiled.out, theta, grad, loss, seed=seed,
+                                                             offset=compiled.iteration, workspace=plan["workspace"])
+            compiled.iteration += 1
+            curve[it] = loss.sum()
+            finite[it] = plan["flag"][0] = torch.isfinite(curve[it]).float()
+            if not bool(finite[it]):
+                continue
+            plan["svgd_workspace"] = native.svgd_direction(theta, grad, grad, dim=plan["dim"], bandwidth=self.fixed_bandwidth,
+                                                           bandwidth_out=plan["bandwidth"], workspace=plan["svgd_workspace"])
+            with torch.cuda.device(dev):
+                native.check(compiled.lib.bsvi_optimizer_step(C.byref(cfg), C.c_void_p(compiled.params.data_ptr() + 4 * base),
+                                                              C.c_void_p(compiled.out.data_ptr() + 4 * base), C.c_void_p(state.data_ptr()),
+                                                              C.c_void_p(plan["mask"].data_ptr()), n * ld, compiled._stream()))
+        compiled.grads_valid = True
+        self.last_compiled = compiled
+        return curve, finite
 
     def compute_loss(self, joint_model, posterior_model, sampler_model, number_samples, input_values={}):
         return _ParticleLoss([self._map.compute_loss(joint_model, particle, sampler_model, 1, input_values) for particle in posterior_model])

@@ -477,6 +477,40 @@ def svgd_direction(theta, grad, out, dim=None, bandwidth=None, bandwidth_out=Non
     return workspace
 
 
+# ... and all particles of a Bayesian neural network through its kernels in one pass (csrc/bnn_particles.inc)
+EXPORTS.update({
+    "bsvi_bnn_particles_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_uint32]),
+    "bsvi_bnn_particles_fwd_bwd": (C.c_int, [C.c_void_p, C.POINTER(BnnArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
+                                             C.c_void_p]),
+})
+
+
+def bnn_particles_fwd_bwd(handle, params, out, theta, grad, loss, seed=0, offset=0, indices=None, workspace=None):
+    """bsvi_bnn_particles_fwd_bwd on a bsvi_bnn `handle` whose rows are all points: `theta` [N][ld] (f32 on the device, rows contiguous,
+    row n the values of particle n in the latent vector's row order) -> `grad` [N][ld], the gradient of every particle's loss
+    -log p(theta_n, minibatch), and `loss` [N].  `params` / `out`: the handle's parameter vector and output block (the priors' parameters
+    are read from the first); the minibatch is the one of (seed, offset), or `indices` (int32 on the device).  The first call on a handle
+    fixes both products per sample for it.  Returns the workspace, zeroed when it is made, for the next call of the same N."""
+    import torch
+    lib = load()
+    n, ld = theta.shape
+    for name, x, shape in (("theta", theta, (n, ld)), ("grad", grad, (n, ld)), ("loss", loss, (n,))):
+        if x.dtype != torch.float32 or tuple(x.shape) != shape or not x.is_contiguous() or not x.is_cuda:
+            raise ValueError("bnn_particles_fwd_bwd: {} is not a contiguous f32 device tensor of shape {}".format(name, shape))
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    with torch.cuda.device(theta.device):
+        need = lib.bsvi_bnn_particles_workspace_bytes(handle, n)
+        if need == 0:
+            check(-1)
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.zeros(need, dtype=torch.uint8, device=theta.device)      # (zeroed once, as CompiledBnn.workspace)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        args = BnnArgs(params_dev=ptr(params), indices_dev=ptr(indices), seed=int(seed), offset=int(offset), n_samples_local=n,
+                       n_samples_global=n, out_dev=ptr(out), workspace_dev=ptr(workspace), stream=stream)
+        check(lib.bsvi_bnn_particles_fwd_bwd(handle, C.byref(args), ptr(theta), ptr(grad), ptr(loss), n, ld, stream))
+    return workspace
+
+
 # bsvi_struct_kind (include/bsvi.h) -> the ctypes mirror of the struct: load() checks every size against bsvi_sizeof()
 STRUCT_KINDS = {0: UniformEntry, 1: Record, 2: ProgramDesc, 3: ElboArgs, 4: OptCfg, 5: DenseDesc, 6: DenseArgs, 7: MlpLayer,
                 8: AmortDesc, 9: AmortArgs, 10: MvnInsn, 11: MvnDesc, 12: MvnArgs, 13: BnnLayer, 14: BnnDesc, 15: BnnArgs,

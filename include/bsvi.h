@@ -1143,6 +1143,25 @@ size_t bsvi_svgd_workspace_bytes(uint32_t n_particles, uint64_t dim);
 int bsvi_svgd_direction(const float* theta_dev, const float* grad_dev, float* out_dev, uint32_t n_particles, uint64_t dim, uint64_t ld,
                         float bandwidth, float* bandwidth_out_dev, void* workspace_dev, void* stream);
 
+/* (ABI 11, entry points added without a change to any struct) All particles of a Bayesian neural network in one pass: the particles take
+ * the place of the samples (n_samples_local = n_particles), so the two products, the middle kernel and the epilogue run once for all of
+ * them.  theta_dev [n_particles][ld] holds particle n's value of row r (the latent vector's row order: weights1 first, then the other
+ * tensors) at theta_dev[n * ld + r], ld >= the model's number of rows; grad_dev [n_particles][ld] receives the gradient of the
+ * particle's own loss,  -(d log p(minibatch | theta_n) + prior_weight d log p(theta_n)) / d theta[n][r],  and loss_dev [n_particles]
+ * that loss, -log p(theta_n, minibatch) with the model's weights; columns past the last row are neither read nor written.  grad_dev
+ * may not be theta_dev.  16-byte loads and stores when ld is a multiple of 4 and the table's base is 16-byte aligned, else scalars.
+ * One minibatch (args: seed, offset | indices_dev) is shared by the particles.  Of `args` are read params_dev (the prior parameters
+ * of the rows come from the uniform table; the q loc entries are not read), indices_dev, seed, offset, out_dev, indices_out_dev and
+ * workspace_dev — bsvi_bnn_particles_workspace_bytes(b, n_particles) bytes; the launches go to `stream`.  No atomics: the same inputs
+ * give the same bits.  Served: a handle whose rows are ALL point rows (bsvi_bnn_set_point_rows), a classifier or a regression with a
+ * constant scale (any family), every activation and depth, 2 <= n_particles <= 256.  Refused with the feature or the limit in the
+ * message: rows that are not points, scale latents, a learnable sigma, a scale head, the BlackBox estimator, f_weight_dev / q_weight_dev
+ * (custom estimators), and a handle whose launches already took the shared first layer — the particles differ in weights1, so the first
+ * of these two calls on a handle that has not chosen yet fixes both products per sample for it (bsvi_bnn_shared_first then returns 0). */
+size_t bsvi_bnn_particles_workspace_bytes(const bsvi_bnn* b, uint32_t n_particles);
+int bsvi_bnn_particles_fwd_bwd(const bsvi_bnn* b, const bsvi_bnn_args* args, const float* theta_dev, float* grad_dev, float* loss_dev,
+                               uint32_t n_particles, uint64_t ld, void* stream);
+
 const char* bsvi_last_error(void);
 int bsvi_abi_version(void);
 /* number of gfx950 devices visible to the HIP runtime (0 if none) */
