@@ -1236,7 +1236,8 @@ extern "C" int bsvi_dense_create(const bsvi_dense_desc* desc, bsvi_dense** out) 
     if (desc->abi_version != BSVI_ABI_VERSION) return fail(BSVI_ERR_INVALID, "ABI version mismatch");
     if (!desc->n_classes || !desc->n_features || !desc->batch_size || desc->batch_size > desc->dataset_size)
         return fail(BSVI_ERR_INVALID, "bad dense shape");
-    if (desc->n_classes > 16) return fail(BSVI_ERR_UNSUPPORTED, "dense path supports at most 16 classes");
+    // (17 .. 32 classes: the handle serves bsvi_dense_particles_fwd_bwd alone — dense_call refuses the sampled path's launches)
+    if (desc->n_classes > 32) return fail(BSVI_ERR_UNSUPPORTED, "a dense handle has at most 32 classes");
     if (desc->likelihood == BSVI_LIK_BERNOULLI && desc->n_classes != 1) return fail(BSVI_ERR_INVALID, "Bernoulli likelihood needs one output");
     if (desc->likelihood > BSVI_LIK_BERNOULLI) return fail(BSVI_ERR_UNSUPPORTED, "unknown likelihood");
     if (desc->estimator > BSVI_EST_BLACKBOX) return fail(BSVI_ERR_INVALID, "unknown estimator");
@@ -1332,6 +1333,7 @@ extern "C" size_t bsvi_dense_workspace_bytes(const bsvi_dense* p, uint32_t n_loc
 // what the selection needs of a call, behind the checks of the arguments that depend on the estimator
 static int dense_call(const bsvi_dense* p, const bsvi_dense_args* a, dsel::Call& c) {
     if (!a->n_samples_local || !a->n_samples_global) return fail(BSVI_ERR_INVALID, "zero samples");
+    if (p->d.n_classes > 16) return fail(BSVI_ERR_UNSUPPORTED, "dense path supports at most 16 classes");
     if (a->q_weight_dev && p->d.estimator != BSVI_EST_BLACKBOX)
         return fail(BSVI_ERR_INVALID, "q_weight_dev needs a model lowered for the BlackBox estimator (its launches accumulate log q)");
     if (a->logq_out_dev && p->d.estimator != BSVI_EST_BLACKBOX)

@@ -184,6 +184,24 @@ def lower_dense(joint, posterior, estimator="pathwise"):
     return prog
 
 
+MIN_PARTICLES, MAX_PARTICLES, MAX_PARTICLE_CLASSES, MAX_PARTICLE_FEATURES = 2, 256, 32, 1024
+
+
+def check_particles(p, n_particles):
+    """what `bsvi_dense_particles_fwd_bwd` serves, asked of a lowered program before any device work (the library asks the same of its
+    handle); every refusal is a ValueError that names the feature or the limit"""
+    where = "batched particles (bsvi_dense_particles_fwd_bwd): "
+    if not MIN_PARTICLES <= n_particles <= MAX_PARTICLES:
+        raise ValueError(where + "{} particles, served are {} .. {}".format(n_particles, MIN_PARTICLES, MAX_PARTICLES))
+    if not p.point_estimate:
+        raise ValueError(where + "{} has a Normal posterior (a particle is a model of one learnable RootVariable named like the "
+                                 "weights: a point estimate)".format(p.latent_name))
+    if p.n_classes > MAX_PARTICLE_CLASSES:
+        raise ValueError(where + "{} classes, served are 1 .. {}".format(p.n_classes, MAX_PARTICLE_CLASSES))
+    if p.n_features > MAX_PARTICLE_FEATURES:
+        raise ValueError(where + "{} features, served are 1 .. {}".format(p.n_features, MAX_PARTICLE_FEATURES))
+
+
 class CompiledDense:
     """Engine for a dense-link model; same surface as engine.CompiledELBO."""
 
@@ -210,7 +228,7 @@ class CompiledDense:
             native.check(n)
         return [self.lib.bsvi_dense_kind_name(kinds[i]).decode() for i in range(n)]
 
-    def __init__(self, joint_model, posterior_model, estimator="pathwise", device=None, program=None):
+    def __init__(self, joint_model, posterior_model, estimator="pathwise", device=None, program=None, particles=False):
         from brancher_amd import engine
         self.device = device or engine._device()
         self.program = program if program is not None else lower_dense(joint_model, posterior_model, estimator)
@@ -236,6 +254,8 @@ class CompiledDense:
                       uniform=ptr(k["uniform"]), consts=ptr(k["consts"]),
                       param_uniform_ptr=ptr(k["ptr"]), param_uniform_idx=ptr(k["idx"]), dataset=ptr(k["dataset"]),
                       labels=ptr(k["labels"]))
+        if p.n_classes > 16 and not particles:      # the library creates 17 .. 32 classes for bsvi_dense_particles_fwd_bwd alone
+            raise native.NativeError("dense path supports at most 16 classes")
         handle = C.c_void_p()
         native.check(lib.bsvi_dense_create(C.byref(d), C.byref(handle)))
         self.handle = handle

@@ -201,8 +201,8 @@ class SteinVariationalGradientDescent(InferenceMethod):
     MIN_PARTICLES, MAX_PARTICLES = 2, 256
 
     def __init__(self, bandwidth=None, batched=False):
-        """``batched=True``: all particles of a Bayesian neural network in one pass (`_run_batched`); a model another path serves is
-        refused, not served particle by particle."""
+        """``batched=True``: all particles of a Bayesian neural network, or of a logistic regression (the dense-link path), in one pass
+        (`_run_batched`); a model the scalar path serves is refused, not served particle by particle."""
         self.batched = bool(batched)
         if self.batched:
             self.run = self._run_batched      # (an attribute of the instance: `perform_inference` hands the loop to a method with `run`)
@@ -254,18 +254,26 @@ class SteinVariationalGradientDescent(InferenceMethod):
 
     @staticmethod
     def _batched_program(joint_model, particles):
-        """the lowered program of the Bayesian neural network all particles share (lowered with particle 0, no device work), or the
-        refusal: a model one of the paths in front of the BNN path serves (`engine.compile_model` asks them in this order) is named
-        with its path, and what `bsvi_bnn_particles_fwd_bwd` does not serve with the feature (`bnn.check_particles`)"""
+        """the lowered program all particles share (lowered with particle 0, no device work; `engine.compile_model` asks the paths in
+        this order): a `dense.DenseProgram` (logistic regression: `bsvi_dense_particles_fwd_bwd`) or a Bayesian neural network's
+        (`bsvi_bnn_particles_fwd_bwd`) — or the refusal: a model the scalar path serves is named with its path, and what the two calls
+        do not serve with the feature (`dense.check_particles`, `bnn.check_particles`)"""
         from brancher_amd import bnn, dense, lowering
         what = "SteinVariationalGradientDescent(batched=True): "
-        for path, lower in (("scalar path (CompiledELBO)", lowering.lower), ("dense-link path (CompiledDense)", dense.lower_dense)):
-            try:
-                lower(joint_model, particles[0], "pathwise")
-            except lowering.LoweringError:
-                continue
+        try:
+            lowering.lower(joint_model, particles[0], "pathwise")
+        except lowering.LoweringError:
+            pass
+        else:
             raise ValueError(what + "the model is served by the {}; the particles of a Bayesian neural network alone are evaluated in one "
-                                    "pass (the BNN path, CompiledBnn): use batched=False".format(path))
+                                    "pass (the BNN path, CompiledBnn): use batched=False".format("scalar path (CompiledELBO)"))
+        try:      # a logistic regression (the dense-link path): its particles go through one fused kernel (csrc/dense_particles.inc)
+            program = dense.lower_dense(joint_model, particles[0], "pathwise")
+        except lowering.LoweringError:
+            pass
+        else:
+            dense.check_particles(program, len(particles))
+            return program
         try:
             program = bnn.lower_bnn(joint_model, particles[0], "pathwise")
         except lowering.LoweringError as err:
@@ -274,23 +282,29 @@ class SteinVariationalGradientDescent(InferenceMethod):
         return program
 
     def _build_batched_plan(self, joint_model, particles):
-        """once per list of particles: a CompiledBnn of its own (its handle takes both products per particle) whose parameter buffer and
+        """once per list of particles: a CompiledBnn (its handle takes both products per particle) or CompiledDense of its own, with the
+        call that evaluates all particles on it (`evaluate`: the two have one signature), whose parameter buffer and
         output block are extended by the [N][ld] table of the particles and the table of their gradients — the particles' STORE: every
         particle's parameters are bound to their row, in the latent vector's row order"""
         import torch
-        from brancher_amd import bnn
+        from brancher_amd import bnn, dense, native
         from brancher_amd.native import OUT_HEADER
         if self._program is None:
             self._program = self._batched_program(joint_model, particles)
         program = self._program
-        compiled = bnn.CompiledBnn(joint_model, particles[0], "pathwise", program=program)
-        n, dim = len(particles), program.n_rows
+        if isinstance(program, dense.DenseProgram):      # one tensor, the weight matrix, rows r = c P + p
+            compiled, evaluate = dense.CompiledDense(joint_model, particles[0], "pathwise", program=program, particles=True), native.dense_particles_fwd_bwd
+            tensors = [dict(name=program.latent_name, row0=0, size=program.n_classes * program.n_features)]
+        else:
+            compiled, evaluate = bnn.CompiledBnn(joint_model, particles[0], "pathwise", program=program), native.bnn_particles_fwd_bwd
+            tensors = program.tensors
+        n, dim = len(particles), sum(t["size"] for t in tensors)
         ld = (dim + 3) // 4 * 4
         # the table starts a multiple of four floats into both buffers (16-byte rows), behind the handle's own parameters and gradients
         # and one header of the optimizer step: its finite flag is out[base + 3]
         base = (max(program.n_params, 1) + 3) // 4 * 4 + OUT_HEADER
         table = np.zeros((n, ld), dtype=np.float32)
-        by_name = {t["name"]: t for t in program.tensors}
+        by_name = {t["name"]: t for t in tensors}
         for row, particle in enumerate(particles):
             for var in particle.flatten():
                 t = by_name[var.name]
@@ -305,14 +319,14 @@ class SteinVariationalGradientDescent(InferenceMethod):
                 var.parameter.bind(compiled, base + row * ld + by_name[var.name]["row0"])
         mask = torch.zeros(n, ld, dtype=torch.uint8, device=dev)
         mask[:, :dim] = 1
-        return dict(key=tuple(id(p) for p in particles), compiled=compiled, n=n, dim=dim, ld=ld, base=base, mask=mask.reshape(-1),
+        return dict(key=tuple(id(p) for p in particles), compiled=compiled, evaluate=evaluate, n=n, dim=dim, ld=ld, base=base, mask=mask.reshape(-1),
                     theta=params[base:].view(n, ld), grad=compiled.out[OUT_HEADER + base:].view(n, ld), flag=compiled.out[base + 3:base + 4],
                     loss=torch.zeros(n, device=dev), bandwidth=torch.zeros(1, device=dev), workspace=None, svgd_workspace=None)
 
     def _run_batched(self, joint_model, posterior_model, sampler_model, number_iterations, number_samples, optimizer,
                      pretraining_iterations, **opt_params):
         """the loop of `perform_inference` for ``batched=True``, three native calls an iteration whatever the number of particles:
-        `bsvi_bnn_particles_fwd_bwd` on the table that IS the particles' parameter store (loss and gradient of every particle; one
+        `bsvi_bnn_particles_fwd_bwd` or `bsvi_dense_particles_fwd_bwd` on the table that IS the particles' parameter store (loss and gradient of every particle; one
         minibatch, shared), `bsvi_svgd_direction` in place on the gradient table, one `bsvi_optimizer_step` over its N ld elements with
         per-element state.  No gather, no scatter, no launch per particle.  A non-finite loss skips the step, as the loop does."""
         import ctypes as C
@@ -329,8 +343,8 @@ class SteinVariationalGradientDescent(InferenceMethod):
         curve, finite = torch.zeros(K, device=dev), torch.zeros(K, device=dev)
         seed = int(compiled._seed(None))
         for it in range(K):
-            plan["workspace"] = native.bnn_particles_fwd_bwd(compiled.handle, compiled.params, compiled.out, theta, grad, loss, seed=seed,
-                                                             offset=compiled.iteration, workspace=plan["workspace"])
+            plan["workspace"] = plan["evaluate"](compiled.handle, compiled.params, compiled.out, theta, grad, loss, seed=seed,
+                                                 offset=compiled.iteration, workspace=plan["workspace"])
             compiled.iteration += 1
             curve[it] = loss.sum()
             finite[it] = plan["flag"][0] = torch.isfinite(curve[it]).float()

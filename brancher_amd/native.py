@@ -511,6 +511,40 @@ def bnn_particles_fwd_bwd(handle, params, out, theta, grad, loss, seed=0, offset
     return workspace
 
 
+# ... and all particles of a dense-link model (logistic regression) in one fused kernel (csrc/dense_particles.inc)
+EXPORTS.update({
+    "bsvi_dense_particles_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_uint32]),
+    "bsvi_dense_particles_fwd_bwd": (C.c_int, [C.c_void_p, C.POINTER(DenseArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
+                                               C.c_void_p]),
+})
+
+
+def dense_particles_fwd_bwd(handle, params, out, theta, grad, loss, seed=0, offset=0, indices=None, workspace=None):
+    """bsvi_dense_particles_fwd_bwd on a bsvi_dense `handle`: `theta` [N][ld] (f32 on the device, rows contiguous, row n the weights of
+    particle n, r = c P + p) -> `grad` [N][ld], the gradient of every particle's loss -log p(theta_n, minibatch), and `loss` [N].
+    `params`: the handle's parameter vector (the prior's parameters are read from it; `out` is not touched: the argument mirrors
+    `bnn_particles_fwd_bwd`); the minibatch is the one of (seed, offset), or `indices` (int32 on the device).  Returns the workspace, for the
+    next call of the same N."""
+    import torch
+    lib = load()
+    n, ld = theta.shape
+    for name, x, shape in (("theta", theta, (n, ld)), ("grad", grad, (n, ld)), ("loss", loss, (n,))):
+        if x.dtype != torch.float32 or tuple(x.shape) != shape or not x.is_contiguous() or not x.is_cuda:
+            raise ValueError("dense_particles_fwd_bwd: {} is not a contiguous f32 device tensor of shape {}".format(name, shape))
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    with torch.cuda.device(theta.device):
+        need = lib.bsvi_dense_particles_workspace_bytes(handle, n)
+        if need == 0:
+            check(-1)
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty(need, dtype=torch.uint8, device=theta.device)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        args = DenseArgs(params_dev=ptr(params), indices_dev=ptr(indices), seed=int(seed), offset=int(offset), n_samples_local=n,
+                         n_samples_global=n, stream=stream)
+        check(lib.bsvi_dense_particles_fwd_bwd(handle, C.byref(args), ptr(theta), ptr(grad), ptr(loss), n, ld, ptr(workspace)))
+    return workspace
+
+
 # bsvi_struct_kind (include/bsvi.h) -> the ctypes mirror of the struct: load() checks every size against bsvi_sizeof()
 STRUCT_KINDS = {0: UniformEntry, 1: Record, 2: ProgramDesc, 3: ElboArgs, 4: OptCfg, 5: DenseDesc, 6: DenseArgs, 7: MlpLayer,
                 8: AmortDesc, 9: AmortArgs, 10: MvnInsn, 11: MvnDesc, 12: MvnArgs, 13: BnnLayer, 14: BnnDesc, 15: BnnArgs,

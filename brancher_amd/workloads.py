@@ -625,12 +625,16 @@ def build_binary_logistic_regression(api, dataset_size=50, batch_size=30, n_feat
     return model
 
 
-def build_map_logistic_regression(api, dataset_size=30, n_features=4, n_classes=3, seed=0):
+def build_map_logistic_regression(api, dataset_size=30, n_features=4, n_classes=3, seed=0, data=None):
     """`examples/MAP_logistic_regression.py:17-56`: multinomial logistic regression whose "posterior" is a learnable
-    RootVariable named like the weight matrix — a point estimate trained with `inference.MAP` on the full batch."""
+    RootVariable named like the weight matrix — a point estimate trained with `inference.MAP` on the full batch.
+    data: (features [dataset_size, n_features], labels [dataset_size]) in the place of the synthetic rows."""
     BF = api.BF
-    X, labels = logreg_data(dataset_size, n_features, n_classes, seed)
-    X = (X * 6.0).astype(np.float32)                       # iris-like magnitudes
+    if data is None:
+        X, labels = logreg_data(dataset_size, n_features, n_classes, seed)
+        X = (X * 6.0).astype(np.float32)                   # iris-like magnitudes
+    else:
+        X, labels = np.asarray(data[0], dtype=np.float32), np.asarray(data[1])
     indices = api.RandomIndices(dataset_size=dataset_size, batch_size=dataset_size, name="indices", is_observed=True)
     x = api.EmpiricalVariable(X.reshape(dataset_size, n_features, 1), indices=indices, name="x", is_observed=True)
     lab = api.EmpiricalVariable(labels.astype(np.int32), indices=indices, name="labels", is_observed=True)

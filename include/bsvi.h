@@ -509,6 +509,8 @@ typedef struct bsvi_dense_args {
     float* logq_out_dev;         /* per-sample log q(W_n) [n_samples_local] or NULL               */
 } bsvi_dense_args;
 
+/* 1 .. 32 classes.  bsvi_dense_fwd_bwd, bsvi_dense_step and bsvi_dense_plan serve 1 .. 16 and refuse a handle of 17 .. 32 classes
+ * (BSVI_ERR_UNSUPPORTED, "dense path supports at most 16 classes"); such a handle exists for bsvi_dense_particles_fwd_bwd alone. */
 int bsvi_dense_create(const bsvi_dense_desc* desc, bsvi_dense** out);
 void bsvi_dense_destroy(bsvi_dense* d);
 size_t bsvi_dense_workspace_bytes(const bsvi_dense* d, uint32_t n_samples_local);
@@ -1161,6 +1163,22 @@ int bsvi_svgd_direction(const float* theta_dev, const float* grad_dev, float* ou
 size_t bsvi_bnn_particles_workspace_bytes(const bsvi_bnn* b, uint32_t n_particles);
 int bsvi_bnn_particles_fwd_bwd(const bsvi_bnn* b, const bsvi_bnn_args* args, const float* theta_dev, float* grad_dev, float* loss_dev,
                                uint32_t n_particles, uint64_t ld, void* stream);
+
+/* (ABI 11, entry points added without a change to any struct) All particles of a dense-link model (logistic regression: Categorical or
+ * Bernoulli logits = W x) in one fused kernel.  theta_dev [n_particles][ld] holds particle n's weight of row r = c P + p at
+ * theta_dev[n * ld + r], ld >= C P; grad_dev [n_particles][ld] receives
+ *   -( lik_weight d log p(minibatch | theta_n) + prior_weight d log N(theta_n; prior loc, prior scale) ) / d theta[n][r]
+ * and loss_dev [n_particles] the value -log p(theta_n, minibatch); columns C P .. ld of grad_dev are not written.  One minibatch
+ * (args: seed, offset | indices_dev, as bsvi_dense_fwd_bwd draws it; indices_out_dev receives it) is shared by the particles; of `args`
+ * are also read params_dev (the prior's parameters go through the uniform table) and the stream.  The handle's posterior plays no part.
+ * One launch of the dense path's head, the fused kernel, and — when the particles alone leave most of the chip idle and the minibatch
+ * has more than 128 rows — a launch that adds the per-split partial gradients in split order.  No atomics: the same inputs give the same
+ * bits.  Served: 2 <= n_particles <= 256, 1 <= C <= 32 (a handle of 17 .. 32 classes serves these two calls only), 1 <= P <= 1024, any
+ * batch size, n_particles * ld < 2^31; anything else is BSVI_ERR_INVALID with the limit in the message.
+ * workspace_dev: bsvi_dense_particles_workspace_bytes(d, n_particles) bytes of device memory, 256-byte aligned (0: not served). */
+size_t bsvi_dense_particles_workspace_bytes(const bsvi_dense* d, uint32_t n_particles);
+int bsvi_dense_particles_fwd_bwd(const bsvi_dense* d, const bsvi_dense_args* args, const float* theta_dev, float* grad_dev, float* loss_dev,
+                                 uint32_t n_particles, uint64_t ld, void* workspace_dev);
 
 const char* bsvi_last_error(void);
 int bsvi_abi_version(void);
