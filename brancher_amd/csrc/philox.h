@@ -19,6 +19,11 @@
 // draw is -sign(v) log1p(-|v|) of that uniform base noise v, the Cauchy draw the tangent itself.  The weights of that pass are the BNN
 // path's ordinary draw (c1 = (row >> 2) | 0x40000000, the seed as it is).
 //
+// The posterior-predictive pass of the dense-link path (dense_predict.inc, bsvi_dense_predict) draws from the likelihood with a counter
+// tag of its own and the seed as it is:  c0 = global set index, c1 = (m >> 2) | 0x20000000 for row m of the caller's x (next to the
+// weights' 0x40000000 and the scalar engines' 0x80000000), c2 / c3 = the 64-bit offset; set n and row m read u01(word m & 3).  The weights
+// of that pass are the dense path's ordinary draw (c1 = (row >> 2) | 0x40000000).
+//
 // Latent prior scales of the Bayesian neural networks (bsvi_bnn_set_scale_latents): with quads = ceil(n_rows / 4), latent t takes
 // normal t & 3 of the ordinary row-quad call whose quad index is quads + (t >> 2) — c1 = (quads + (t >> 2)) | 0x40000000, the same
 // counters, key and box_muller_fast pairing as the rows, behind every quad a row uses.  A pure function of (seed, offset, global sample,

@@ -178,6 +178,7 @@ def lower_dense(joint, posterior, estimator="pathwise"):
     prog.latent_name = Wq.name
     prog.point_estimate = point is not None
     prog.indices_name = ind_x.name
+    prog.x_name, prog.likelihood_name = x_var.name, k.name
     prog.lik_weight, prog.prior_weight, prog.entropy_weight = 1.0, 1.0, (0.0 if point is not None else 1.0)
     prog.n_noise = C_ * P_
     prog.bmax = 1
@@ -200,6 +201,17 @@ def check_particles(p, n_particles):
         raise ValueError(where + "{} classes, served are 1 .. {}".format(p.n_classes, MAX_PARTICLE_CLASSES))
     if p.n_features > MAX_PARTICLE_FEATURES:
         raise ValueError(where + "{} features, served are 1 .. {}".format(p.n_features, MAX_PARTICLE_FEATURES))
+
+
+def row_parameters(p, theta=None):
+    """(q loc [C P], q scale [C P]) of a lowered program at the flat parameter values `theta`: the uniform table on the host, in
+    double precision (`bnn.row_parameters` on this path's two row ranges) — what `dense_predict_head` leaves in `rowp` on the device"""
+    import types
+    from brancher_amd import bnn
+    rows = np.arange(p.n_classes * p.n_features)
+    shim = types.SimpleNamespace(uniform=p.uniform, consts=p.consts, parameters=p.parameters, n_params=p.n_params,
+                                 row_uniform=(p.q_loc[0] + p.q_loc[1] * rows, p.q_scale[0] + p.q_scale[1] * rows))
+    return bnn.row_parameters(shim, theta)
 
 
 class CompiledDense:
@@ -377,6 +389,91 @@ class CompiledDense:
             res["f"] = fvals
             if logq is not None:
                 res["lq"] = logq
+        return res
+
+    def _predict_rows(self, x):
+        """the caller's rows as a contiguous f32 device tensor [M, P]: from [M, P], [M, P, 1] or the reference's [1, M, P, 1]"""
+        a = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x, dtype=np.float32))
+        if a.ndim == 4 and a.shape[0] == 1:
+            a = a[0]
+        if a.ndim == 3 and a.shape[-1] == 1:
+            a = a[..., 0]
+        P = self.program.n_features
+        if a.ndim != 2:
+            raise ValueError("predict takes rows as [M, {P}], [M, {P}, 1] or [1, M, {P}, 1]: got shape {}".format(
+                tuple(x.shape) if hasattr(x, "shape") else np.shape(x), P=P))
+        if a.shape[1] != P:
+            raise ValueError("the rows have {} features, the model was built on {}".format(a.shape[1], P))
+        if a.shape[0] < 1:
+            raise ValueError("predict needs at least one row")
+        return a.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def _predict(self, rows, n_sets, sets_per_split, **how):
+        key = (n_sets, int(rows.shape[0]), int(sets_per_split or 0))
+        ws = self.__dict__.get("_predict_ws")       # (one workspace kept: the shape of the last call)
+        res, ws = native.dense_predict(self.handle, rows, n_sets, self.program.n_classes, sets_per_split=key[2],
+                                       workspace=ws[1] if ws is not None and ws[0] == key else None, **how)
+        self._predict_ws = (key, ws)
+        res["n_rows"] = key[1]
+        return res
+
+    def predict(self, x, number_samples, seed=None, offset=None, noise=None, want_outputs=False, want_draws=False, want_noise=False,
+                sample_base=0, sets_per_split=None):
+        """Posterior predictive on rows the caller hands in (bsvi_dense_predict, csrc/dense_predict.inc), as `CompiledBnn.predict`:
+        `number_samples` weight sets from the CURRENT posterior — the draw of a training launch at the same (seed, offset, sample_base),
+        or `noise` ([C P, N], or named as the oracle takes it); a point estimate gives its value N times — against every row of `x`.
+        Device tensors: "probs" [N, M, C] (softmax probabilities | the sigmoid of the logit), "mean" [M, C] (their mean over the sets,
+        fixed order) and on request "outputs" [N, M, C] (logits), "draws" [N, M, C] (one draw of the likelihood per set and row:
+        one-hot | 0 / 1) and "noise" [C P, N] (the eps drawn).  offset=None draws from the sampling range (1 << 62) + tick, as the
+        samplers of the engine do; `self.iteration`, `self.out` and the gradients are left alone.  Not sharded: every rank computes all
+        N sets.  sets_per_split (default: chosen from the chip) is the number of sets a workgroup walks; it moves the order of the
+        mean's sum between different values of itself only."""
+        p, N = self.program, int(number_samples)
+        if N < 1:
+            raise ValueError("number_samples must be at least 1")
+        rows = self._predict_rows(x)
+        if p.n_classes > 16:
+            raise ValueError("predict samples weight sets of at most 16 classes: this handle of {} serves predict_particles".format(p.n_classes))
+        if noise is not None and not isinstance(noise, dict) and tuple(noise.shape) != (p.n_noise, N):
+            raise ValueError("noise must be [{}, {}]: got {}".format(p.n_noise, N, tuple(noise.shape)))
+        noise_t = self._noise_tensor(noise, N, 0, N)
+        if noise_t is not None:
+            if tuple(noise_t.shape) != (p.n_noise, N):
+                raise ValueError("noise must be [{}, {}]: got {}".format(p.n_noise, N, tuple(noise_t.shape)))
+            noise_t = noise_t.to(device=self.device, dtype=torch.float32).contiguous()
+        if offset is None:
+            _engine._sample_tick[0] += 1
+            offset = (1 << 62) + _engine._sample_tick[0]
+        if not isinstance(seed, int) or seed is True:
+            seed = _engine.shared_seed(seed, self.device)
+        res = self._predict(rows, N, sets_per_split, params=self.params, noise=noise_t, seed=int(seed), offset=int(offset),
+                            sample_base=int(sample_base), want_outputs=want_outputs, want_draws=want_draws, want_noise=want_noise)
+        res.update(seed=int(seed), offset=int(offset))
+        return res
+
+    def predict_particles(self, table, x, dim=None, seed=None, offset=None, want_outputs=False, want_draws=False, sample_base=0,
+                          sets_per_split=None):
+        """The predictive of an ensemble of point estimates: row n of `table` [N, ld] (f32 on the device, contiguous; the layout of
+        `native.dense_particles_fwd_bwd`, value r = c P + p, `dim` = C P values of a row, the rest padding) is weight set n, read in
+        place.  The result of `predict` without "noise"; "mean" is the ensemble's predictive.  (seed, offset) only feed the draws."""
+        p = self.program
+        R = p.n_classes * p.n_features
+        if dim is not None and int(dim) != R:
+            raise ValueError("predict_particles: dim is {}, a weight set of this model has {} x {} = {} values".format(dim, p.n_classes, p.n_features, R))
+        if not torch.is_tensor(table) or table.ndim != 2 or table.shape[0] < 1:
+            raise ValueError("predict_particles: the table is a two-dimensional tensor [N, ld] of at least one row")
+        if table.shape[1] < R:
+            raise ValueError("predict_particles: the table has {} columns, a weight set of this model has {} x {} = {} values".format(
+                table.shape[1], p.n_classes, p.n_features, R))
+        rows = self._predict_rows(x)
+        if offset is None:
+            _engine._sample_tick[0] += 1
+            offset = (1 << 62) + _engine._sample_tick[0]
+        if not isinstance(seed, int) or seed is True:
+            seed = _engine.shared_seed(seed, self.device) if want_draws else 0
+        res = self._predict(rows, int(table.shape[0]), sets_per_split, table=table, seed=int(seed), offset=int(offset),
+                            sample_base=int(sample_base), want_outputs=want_outputs, want_draws=want_draws)
+        res.update(seed=int(seed), offset=int(offset))
         return res
 
     def evaluate_weighted(self, number_samples, f_weight, q_weight, seed, offset, noise=None, minibatch=None):

@@ -1403,6 +1403,86 @@ def _bnn_posterior_sample(model, compiled, number_samples, input_values):
     return out
 
 
+def _dense_predictor(model, compiled):
+    """the engine that answers a prediction of a dense-link model, as `_bnn_predictor`: the model's own when it trains on
+    `dense.CompiledDense`; for a regression small enough for the scalar engine (which trains it — the reference's two-feature
+    `minibatch_logistic_regression` — and whose sampler refuses the caller's rows) a CompiledDense kept for prediction alone: the
+    parameters stay bound to the engine that trains them and their current values are copied in before every call.  None: not a
+    model of the family."""
+    from brancher_amd import dense
+    if type(compiled).__name__ == "CompiledDense":
+        return compiled
+    posterior = model.posterior_model
+    kept = model.__dict__.get("_dense_predictor")
+    if kept is None or kept[0] is not posterior:
+        try:
+            program = dense.lower_dense(model, posterior)
+        except lowering.LoweringError:
+            return None
+        bound = [(par, par._store, par._offset) for par, _, _, _ in program.parameters]
+        predictor = dense.CompiledDense(model, posterior, program=program)
+        for par, store, offset in bound:                   # (the constructor bound them to itself)
+            if store is None:
+                par.unbind()
+            else:
+                par.bind(store, offset)
+        kept = model.__dict__["_dense_predictor"] = (posterior, predictor)
+    predictor = kept[1]
+    theta = np.zeros(max(predictor.n_params, 1), dtype=np.float32)
+    for par, off, size, _ in predictor.program.parameters:
+        theta[off:off + size] = par.numpy().reshape(-1)
+    predictor.params.copy_(torch.from_numpy(theta[:predictor.params.numel()]).to(predictor.device))
+    return predictor
+
+
+def _dense_posterior_sample(model, compiled, number_samples, input_values):
+    """`ProbabilisticModel._get_posterior_sample` of a dense-link model (the last step of examples/MNIST_logistic_regression.py:73 and
+    MAP_logistic_regression.py:84) through `CompiledDense.predict`, as `_bnn_posterior_sample`: N weight sets from the posterior and the
+    likelihood's draw on the rows of `input_values[x]` — or, without them, on one minibatch at the call's (seed, offset).  Keyed by the
+    JOINT model's variables in the reference's shapes: the weights [N, 1, C, P] (mu + s eps of the reported noise; a point estimate
+    tiled), x as given ([N, B, P, 1] for the minibatch), the likelihood variable one-hot [N, M, C, 1] | 0 / 1 [N, M, 1, 1], and the
+    roots above them, tiled."""
+    from brancher_amd import dense
+    from brancher_amd.variables import RootVariable
+    p, dev, N = compiled.program, compiled.device, int(number_samples)
+    by_name = {v.name: v for v in model.flatten()}
+    x_var, lik_var = by_name[p.x_name], by_name[p.likelihood_name]
+    _sample_tick[0] += 1
+    seed, offset = int(shared_seed(None, dev)), (1 << 62) + _sample_tick[0]
+    given = _given(input_values, x_var)
+    out = {}
+    if given is not None:
+        rows = torch.from_numpy(np.ascontiguousarray(given, dtype=np.float32))
+    else:
+        # the minibatch of (seed, offset) through the launch that draws it; the caller's gradients are left alone
+        keep, valid = compiled.out.clone(), compiled.grads_valid
+        idx = compiled.evaluate(N, seed=seed, offset=offset, want_indices=True)["indices"].long()
+        compiled.out.copy_(keep)
+        compiled.grads_valid = valid
+        rows = torch.from_numpy(p.dataset).to(dev)[idx]
+        out[by_name[p.indices_name]] = idx
+        out[x_var] = rows.reshape(1, p.batch_size, p.n_features, 1).expand(N, -1, -1, -1).contiguous()
+    res = compiled.predict(rows, N, seed=seed, offset=offset, want_draws=True, want_noise=True)
+    out[lik_var] = res["draws"].reshape(N, res["n_rows"], p.n_classes, 1)
+    loc, scale = dense.row_parameters(p, compiled.params.detach().cpu().numpy()[:max(p.n_params, 1)])
+    weights = loc.astype(np.float32)[:, None] + scale.astype(np.float32)[:, None] * res["noise"].cpu().numpy()
+    out[by_name[p.latent_name]] = torch.from_numpy(np.ascontiguousarray(weights.T.reshape(N, 1, p.n_classes, p.n_features))).to(dev)
+    # the roots above the likelihood, not looking past a variable the caller gave
+    seen, stack = set(), [lik_var]
+    while stack:
+        v = stack.pop()
+        if v in seen:
+            continue
+        seen.add(v)
+        if v is x_var and given is not None:
+            continue
+        if isinstance(v, RootVariable) and v not in out and isinstance(v.value, (np.ndarray, list, tuple)):
+            t = torch.from_numpy(np.ascontiguousarray(v.value, dtype=np.float32)).to(dev)
+            out[v] = t.expand((N,) + tuple(t.shape[1:])).contiguous() if t.ndim > 1 and t.shape[0] == 1 else t
+        stack.extend(v.parents)
+    return out
+
+
 def sample_model(model, number_samples, observed=False, input_values={}):
     """`ProbabilisticModel._get_sample` (variables.py:732-742)."""
     if observed:
@@ -1439,11 +1519,15 @@ def posterior_sample(model, number_samples, input_values={}):
         except lowering.LoweringError:
             compiled = None
         if compiled is not None and type(compiled).__name__ != "CompiledAmortized":
-            compiled = _bnn_predictor(model, compiled)
+            # (a dense-link model that the one-layer network's lowering refuses — features no multiple of 4, a scale-less prior —
+            #  answers from the dense path's forward-only kernel; the models the detour serves keep it and their draws)
+            compiled = _bnn_predictor(model, compiled) or _dense_predictor(model, compiled)
         if compiled is None:
             raise scalar_error
         if type(compiled).__name__ == "CompiledBnn":
             out = _bnn_posterior_sample(model, compiled, number_samples, input_values)
+        elif type(compiled).__name__ == "CompiledDense":
+            out = _dense_posterior_sample(model, compiled, number_samples, input_values)
         else:
             out = _amortized_posterior_sample(model, compiled, number_samples)
         for var, value in (input_values or {}).items():

@@ -360,6 +360,37 @@ class SteinVariationalGradientDescent(InferenceMethod):
         self.last_compiled = compiled
         return curve, finite
 
+    def predict(self, joint_model, posterior_model, x, want_outputs=False, want_draws=False):
+        """The predictive of the particle ensemble of a logistic regression (the dense-link path) on the rows `x`, all particles in one
+        launch (`CompiledDense.predict_particles`, csrc/dense_predict.inc): "probs" [N, M, C] per particle, "mean" [M, C] the
+        ensemble's predictive, on request "outputs" (logits) and "draws".  When this instance's batched plan holds these particles its
+        table is read in place — no copy, no gather; otherwise an engine and the table of the particles' current values are built for
+        the call.  Particles of a Bayesian neural network are refused: their ensemble has no fused predictive."""
+        import torch
+        from brancher_amd import dense, lowering
+        self.check_model_compatibility(None, posterior_model, None)
+        plan = self._plan
+        if plan is not None and plan.get("key") == tuple(id(p) for p in posterior_model) and isinstance(plan.get("compiled"), dense.CompiledDense):
+            compiled, table, dim = plan["compiled"], plan["theta"], plan["dim"]
+        else:
+            try:
+                program = dense.lower_dense(joint_model, posterior_model[0], "pathwise")
+            except lowering.LoweringError as err:
+                raise ValueError("SteinVariationalGradientDescent.predict serves the particles of a logistic regression (the dense-link path); "
+                                 "the predictive of the particles of a Bayesian neural network, or of another model, is not served "
+                                 "({})".format(err)) from None
+            if not program.point_estimate:
+                raise ValueError("SteinVariationalGradientDescent.predict: {} has a Normal posterior, a particle is a point estimate".format(program.latent_name))
+            bound = [(par, par._store, par._offset) for par, _, _, _ in program.parameters]
+            compiled = dense.CompiledDense(joint_model, posterior_model[0], "pathwise", program=program, particles=True)
+            for par, store, offset in bound:                   # (the constructor bound them to itself)
+                par.unbind() if store is None else par.bind(store, offset)
+            dim = program.n_classes * program.n_features
+            values = np.stack([next(v for v in particle.flatten() if v.name == program.latent_name).parameter.numpy().reshape(-1)
+                               for particle in posterior_model]).astype(np.float32)
+            table = torch.from_numpy(values).to(compiled.device)
+        return compiled.predict_particles(table, x, dim=dim, want_outputs=want_outputs, want_draws=want_draws)
+
     def compute_loss(self, joint_model, posterior_model, sampler_model, number_samples, input_values={}):
         return _ParticleLoss([self._map.compute_loss(joint_model, particle, sampler_model, 1, input_values) for particle in posterior_model])
 

@@ -545,6 +545,60 @@ def dense_particles_fwd_bwd(handle, params, out, theta, grad, loss, seed=0, offs
     return workspace
 
 
+# ... and the posterior predictive of the dense-link path, sampled weight sets or a table of particles (csrc/dense_predict.inc)
+class DensePredictArgs(Sized):
+    """bsvi_dense_predict_args (no bsvi_struct_kind of its own: load() checks it against bsvi_dense_predict_args_size())"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32),
+                ("params_dev", C.c_void_p), ("theta_dev", C.c_void_p), ("ld", C.c_uint64), ("x_dev", C.c_void_p), ("noise_dev", C.c_void_p),
+                ("seed", C.c_uint64), ("offset", C.c_uint64),
+                ("n_sets", C.c_uint32), ("sample_base", C.c_uint32), ("n_rows", C.c_uint32), ("sets_per_split", C.c_uint32),
+                ("z_out", C.c_void_p), ("p_out", C.c_void_p), ("mean_out", C.c_void_p), ("draw_out", C.c_void_p),
+                ("noise_out", C.c_void_p), ("workspace_dev", C.c_void_p), ("stream", C.c_void_p)]
+
+
+EXPORTS.update({
+    "bsvi_dense_predict_args_size": (C.c_size_t, []),
+    "bsvi_dense_predict_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "bsvi_dense_predict": (C.c_int, [C.c_void_p, C.POINTER(DensePredictArgs)]),
+})
+
+
+def dense_predict(handle, x, n_sets, n_classes, params=None, table=None, noise=None, seed=0, offset=0, sample_base=0, sets_per_split=0,
+                  want_outputs=False, want_draws=False, want_noise=False, workspace=None):
+    """bsvi_dense_predict on a bsvi_dense `handle`: `x` [M][P] (contiguous f32 on the device) against `n_sets` weight sets — drawn from
+    the posterior at `params` (eps from `noise` [C P][n_sets], or the draw of a training launch at (seed, offset, sample_base)), or the
+    rows of `table` [n_sets][ld] read in place.  Returns (result, workspace): "probs" [N, M, C], "mean" [M, C] and on request "outputs"
+    (logits), "draws" and "noise" [C P, N] — device tensors — and the workspace for the next call of the same shape."""
+    import torch
+    lib = load()
+    n, m = int(n_sets), int(x.shape[0])
+    for name, t in (("x", x), ("table", table), ("noise", noise)):
+        if t is not None and (t.dtype != torch.float32 or t.ndim != 2 or not t.is_contiguous() or not t.is_cuda):
+            raise ValueError("dense_predict: {} is not a contiguous two-dimensional f32 device tensor".format(name))
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    with torch.cuda.device(x.device):
+        need = lib.bsvi_dense_predict_workspace_bytes(handle, n, m, int(sets_per_split))
+        if need == 0:
+            check(-1)
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+        new = lambda *shape: torch.empty(shape, device=x.device)
+        res = dict(probs=new(n, m, n_classes), mean=new(m, n_classes))
+        if want_outputs:
+            res["outputs"] = new(n, m, n_classes)
+        if want_draws:
+            res["draws"] = new(n, m, n_classes)
+        if want_noise:
+            res["noise"] = new(x.shape[1] * n_classes, n)
+        args = DensePredictArgs(params_dev=ptr(params), theta_dev=ptr(table), ld=0 if table is None else int(table.shape[1]), x_dev=ptr(x),
+                                noise_dev=ptr(noise), seed=int(seed), offset=int(offset), n_sets=n, sample_base=int(sample_base), n_rows=m,
+                                sets_per_split=int(sets_per_split), z_out=ptr(res.get("outputs")), p_out=ptr(res["probs"]),
+                                mean_out=ptr(res["mean"]), draw_out=ptr(res.get("draws")), noise_out=ptr(res.get("noise")),
+                                workspace_dev=ptr(workspace), stream=C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        check(lib.bsvi_dense_predict(handle, C.byref(args)))
+    return res, workspace
+
+
 # bsvi_struct_kind (include/bsvi.h) -> the ctypes mirror of the struct: load() checks every size against bsvi_sizeof()
 STRUCT_KINDS = {0: UniformEntry, 1: Record, 2: ProgramDesc, 3: ElboArgs, 4: OptCfg, 5: DenseDesc, 6: DenseArgs, 7: MlpLayer,
                 8: AmortDesc, 9: AmortArgs, 10: MvnInsn, 11: MvnDesc, 12: MvnArgs, 13: BnnLayer, 14: BnnDesc, 15: BnnArgs,
@@ -582,6 +636,9 @@ def load():
     if lib.bsvi_bnn_predict_args_size() != C.sizeof(BnnPredictArgs):
         raise NativeError("BnnPredictArgs: this binding declares {} bytes, libbsvi.so {} (include/bsvi.h and native.py disagree)".format(
             C.sizeof(BnnPredictArgs), lib.bsvi_bnn_predict_args_size()))
+    if lib.bsvi_dense_predict_args_size() != C.sizeof(DensePredictArgs):
+        raise NativeError("DensePredictArgs: this binding declares {} bytes, libbsvi.so {} (include/bsvi.h and native.py disagree)".format(
+            C.sizeof(DensePredictArgs), lib.bsvi_dense_predict_args_size()))
     _lib = lib
     return lib
 

@@ -3,7 +3,8 @@
 Three classes, four features (iris-like magnitudes); the particles are point estimates of the weight matrix, as in the reference's SVGD
 playground, and start as small random matrices.  `batched=True` evaluates every particle's loss and gradient in one call
 (csrc/dense_particles.inc), couples the gradients and steps one table that holds all particles.  The ensemble predicts with the mean of
-the particles' softmax, here on rows the particles never saw.
+the particles' softmax, here on rows the particles never saw: one `predict` call (csrc/dense_predict.inc) reads the particles' table in
+place and hands back every particle's probabilities and their mean — the playground's last step, without its loop over particles and rows.
 
     python examples/svgd_logistic_regression.py
 """
@@ -32,11 +33,10 @@ def main(n_particles=5, iterations=400, lr=0.02, n_train=90, n_test=60, n_featur
     method = inference.SteinVariationalGradientDescent(batched=True)
     inference.perform_inference(model, number_iterations=iterations, optimizer="Adam", lr=lr, inference_method=method, posterior_model=particles)
 
-    weights = torch.tensor(np.stack([next(iter(p.flatten())).parameter.numpy().reshape(n_classes, n_features) for p in particles]))
-    held_out, labels = torch.tensor(x[n_train:]), torch.tensor(y[n_train:])
-    probabilities = torch.softmax(held_out @ weights.transpose(1, 2), -1)                 # [particles][rows][classes]
-    ensemble = (probabilities.mean(0).argmax(1) == labels).float().mean()
-    each = (probabilities.argmax(2) == labels).float().mean(1)
+    labels = torch.tensor(y[n_train:])
+    predicted = method.predict(model, particles, x[n_train:])       # "probs" [particles][rows][classes], "mean" [rows][classes]
+    ensemble = (predicted["mean"].argmax(1).cpu() == labels).float().mean()
+    each = (predicted["probs"].argmax(2).cpu() == labels).float().mean(1)
     curve = model.diagnostics["loss curve"]
     print("loss (sum over %d particles): %.1f -> %.1f, last bandwidth %.3f" % (n_particles, curve[0], curve[-1], method.bandwidth))
     print("held-out accuracy of the ensemble (mean softmax of the particles): %.3f; of the particles alone: %.3f .. %.3f" % (

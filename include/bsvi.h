@@ -1180,6 +1180,52 @@ size_t bsvi_dense_particles_workspace_bytes(const bsvi_dense* d, uint32_t n_part
 int bsvi_dense_particles_fwd_bwd(const bsvi_dense* d, const bsvi_dense_args* args, const float* theta_dev, float* grad_dev, float* loss_dev,
                                  uint32_t n_particles, uint64_t ld, void* workspace_dev);
 
+/* (ABI 11, entry points and a struct of their own added; no existing struct changes) The posterior predictive of a dense-link model on
+ * rows the CALLER hands in (the reference's `model._get_posterior_sample(N, input_values={x: rows})` of a logistic regression, and the
+ * ensemble of an SVGD run), forward only (csrc/dense_predict.inc).  For x_dev [n_rows][P] and n_sets weight sets W_n [C][P]:
+ *   z [n_sets][n_rows][C]  logits W_n x[m]
+ *   p [n_sets][n_rows][C]  softmax over the classes | the sigmoid of the one logit (Bernoulli / Binomial(1))
+ *   mean [n_rows][C]       the mean of p over the sets, summed in ascending set order (fixed: the same inputs give the same bits)
+ *   draw [n_sets][n_rows][C]  one draw of the likelihood per set and row, one-hot | 0 / 1: u = u01(word m & 3) of the Philox call with
+ *                          counter (sample_base + n, (m >> 2) | 0x20000000, offset low, offset high) and the seed as the key — a tag of
+ *                          its own next to the weights' 0x40000000; Categorical: the first class whose partial sum of the stored f32
+ *                          probabilities, in class order, is >= u, the last class if none is; Bernoulli: u < p.
+ * Every output pointer is optional (NULL: not written).  The weight sets are
+ *   sampled (theta_dev NULL): W_n = mu + s eps_n from the handle's posterior at params_dev; eps is noise_dev [C P][n_sets] or, when that
+ *     is NULL, the draw of bsvi_dense_fwd_bwd at the same (seed, offset, sample_base): a prediction sees exactly the weights a training
+ *     launch at that triple drew.  noise_out [C P][n_sets] receives the eps used.  A point estimate has s = 0: every set is its value.
+ *   a table (theta_dev [n_sets][ld], ld >= C P, any alignment, the layout of bsvi_dense_particles_fwd_bwd: row r = c P + p), read in
+ *     place; params_dev is not read, noise_dev and noise_out must be NULL.
+ * One launch that transposes the rows (and evaluates the row parameters), the fused kernel, and — when the rows alone leave most of the
+ * chip idle — a launch that adds the per-split sums of the mean in split order.  sets_per_split: 0, or the number of sets a workgroup
+ * walks (rounded up to whole blocks of floor(32 / C) sets); it changes the order of the mean's sum between different values of itself
+ * only, never a z, p or draw.  Nothing of the handle's training state is touched.  Served: n_sets >= 1, n_rows >= 1, 1 <= C <= 32 (a
+ * sampled call: C <= 16), P >= 1, n_sets * n_rows * C < 2^31 and n_sets * ld < 2^31 (sampled: ld = C P); anything else is
+ * BSVI_ERR_INVALID / BSVI_ERR_UNSUPPORTED with the limit in bsvi_last_error.  Not sharded over ranks. */
+typedef struct bsvi_dense_predict_args {
+    uint32_t struct_size;            /* sizeof(bsvi_dense_predict_args) */
+    uint32_t reserved0;
+    const float* params_dev;         /* [n_params] (sampled)                                                    */
+    const float* theta_dev;          /* [n_sets][ld] (table) or NULL (sampled)                                  */
+    uint64_t ld;
+    const float* x_dev;              /* [n_rows][n_features]                                                    */
+    const float* noise_dev;          /* eps [C P][n_sets] or NULL -> Philox (sampled)                           */
+    uint64_t seed, offset;
+    uint32_t n_sets, sample_base, n_rows, sets_per_split;
+    float* z_out;                    /* [n_sets][n_rows][C] or NULL                                             */
+    float* p_out;                    /* [n_sets][n_rows][C] or NULL                                             */
+    float* mean_out;                 /* [n_rows][C] or NULL                                                     */
+    float* draw_out;                 /* [n_sets][n_rows][C] or NULL                                             */
+    float* noise_out;                /* eps used [C P][n_sets] or NULL (sampled)                                */
+    void* workspace_dev;             /* bsvi_dense_predict_workspace_bytes(...) bytes, 256-byte aligned         */
+    void* stream;
+} bsvi_dense_predict_args;
+/* sizeof(bsvi_dense_predict_args) inside this build of the library (no bsvi_struct_kind: the kinds are a closed list) */
+size_t bsvi_dense_predict_args_size(void);
+/* bytes of workspace of a call with these sizes; 0: not served (bsvi_last_error names the limit) */
+size_t bsvi_dense_predict_workspace_bytes(const bsvi_dense* d, uint32_t n_sets, uint32_t n_rows, uint32_t sets_per_split);
+int bsvi_dense_predict(const bsvi_dense* d, const bsvi_dense_predict_args* args);
+
 const char* bsvi_last_error(void);
 int bsvi_abi_version(void);
 /* number of gfx950 devices visible to the HIP runtime (0 if none) */
