@@ -662,6 +662,7 @@ def row_parameters(p, theta=None):
 
 
 MIN_PARTICLES, MAX_PARTICLES = 2, 256                                  # BNN_MIN_PARTICLES, BNN_MAX_PARTICLES (csrc/bnn_particles.inc)
+MAX_ENSEMBLE_WIDTH = 320                                               # ENS_MAX_WIDTH (csrc/bnn_select.h): the widest layer predict_particles serves
 
 
 def check_particles(p, n_particles):
@@ -1008,6 +1009,44 @@ class CompiledBnn:
         for k, t in (("var", var), ("outputs", outputs), ("draws", draws), ("noise", noise_o)):
             if t is not None:
                 res[k] = t
+        return res
+
+    def predict_particles(self, table, x, dim=None, seed=None, offset=None, want_outputs=False, want_draws=False):
+        """The predictive of an ensemble of point estimates of this network (bsvi_bnn_predict_particles, csrc/bnn_ensemble.inc): row n of
+        `table` [N, ld] (f32 on the device, contiguous; the layout of `native.bnn_particles_fwd_bwd`: the latent vector's row order,
+        `dim` = `program.n_rows` values of a row, the rest padding) is particle n, read in place, and the whole chain runs on every row of
+        `x` in one fused kernel.  Device tensors: "probs" [N, M, C] (softmax probabilities | sigmoid of the logit | the loc), "mean"
+        [M, C] (the ensemble's predictive: their mean over the particles, fixed order), "var" [M, C] where the family has one (Normal:
+        population variance of the loc over the particles + sigma^2; Laplace + 2 sigma^2; a Cauchy likelihood and the classifiers have
+        none), and on request "outputs" [N, M, C] (logits | loc) and "draws" [N, M, C] (one draw of the likelihood per particle and row,
+        the stream of `predict` with the particle as the sample).  (seed, offset) only feed the draws.  One workspace is kept, for the
+        shape of the last call; `self.iteration`, `self.out` and the gradients are left alone."""
+        p, R = self.program, self.program.n_rows
+        check_particles(p, int(table.shape[0]) if torch.is_tensor(table) and table.ndim == 2 else MIN_PARTICLES)
+        if dim is not None and int(dim) != R:
+            raise ValueError("predict_particles: dim is {}, a weight set of this model has {} values".format(dim, R))
+        if not torch.is_tensor(table) or table.ndim != 2:
+            raise ValueError("predict_particles: the table is a two-dimensional tensor [N, ld]")
+        if table.shape[1] < R:
+            raise ValueError("predict_particles: the table has {} columns, a weight set of this model has {} values".format(table.shape[1], R))
+        widest = max(l["rows"] for l in p.layers)
+        if widest > MAX_ENSEMBLE_WIDTH:
+            raise ValueError("predict_particles: a layer of {} units, served are layers of up to {} (bsvi_bnn_predict_particles)".format(
+                widest, MAX_ENSEMBLE_WIDTH))
+        rows = self._predict_rows(x)
+        if offset is None:
+            _engine._sample_tick[0] += 1
+            offset = (1 << 62) + _engine._sample_tick[0]
+        if not isinstance(seed, int) or seed is True:
+            seed = _engine.shared_seed(seed, self.device) if want_draws else 0
+        key = (int(table.shape[0]), int(rows.shape[0]))
+        ws = self.__dict__.get("_particles_ws")
+        want_var = p.likelihood == LIK_NORMAL and getattr(p, "family", D.DIST_NORMAL) != D.DIST_CAUCHY
+        res, workspace = native.bnn_predict_particles(self.handle, self.params, table, rows, p.n_classes, seed=int(seed), offset=int(offset),
+                                                      want_var=want_var, want_outputs=want_outputs, want_draws=want_draws,
+                                                      workspace=ws[1] if ws is not None and ws[0] == key else None)
+        self._particles_ws = (key, workspace)
+        res.update(n_rows=key[1], seed=int(seed), offset=int(offset))
         return res
 
     def evaluate_weighted(self, number_samples, f_weight, q_weight, seed, offset, noise=None, minibatch=None):

@@ -1933,6 +1933,33 @@ __global__ void __launch_bounds__(256) bnn_predict_gather(const BParams Q, const
     }
 }
 
+// the likelihood's Philox words of (sample n, row m): the call whose key word k1 is xor-ed with c0 >> 2 (c0 = 0: the classifiers' call)
+__device__ __forceinline__ u32x4 bnn_predict_words(const BParams& Q, const uint32_t n, const uint32_t m, const uint32_t c0) {
+    return philox4x32(Q.sample_base + n, m, Q.offset_lo, Q.offset_hi, Q.seed_lo ^ BNN_KEY_PREDICT, Q.seed_hi ^ (c0 >> 2));
+}
+
+// the unit draws e of outputs c0 .. c0 + 3 (c0 a multiple of 4) of a loc-scale likelihood: the draw is loc + sigma e
+__device__ __forceinline__ void bnn_predict_noise4(const BParams& Q, const uint32_t n, const uint32_t m, const uint32_t c0, float e[4]) {
+    const u32x4 w = bnn_predict_words(Q, n, m, c0);
+    if (Q.family == BSVI_DIST_NORMAL) {
+        box_muller_fast(w.x, w.y, e[0], e[1]);
+        box_muller_fast(w.z, w.w, e[2], e[3]);
+    } else {
+        // Laplace | Cauchy: ONE word per output, word c & 3 of the call the Normal's output c reads (philox.h) — a word of
+        // its own for every output, so that no two outputs of a row share a draw.  The library's draws of the two
+        // families (dist_math.h, sample_from_noise_generic): Laplace -sign(v) log1p(-|v|) of the uniform base noise v
+        const uint32_t wd[4] = {w.x, w.y, w.z, w.w};
+        for (uint32_t k = 0; k < 4u; ++k) {
+            if (Q.family == BSVI_DIST_LAPLACE) {
+                const float v = laplace_noise(wd[k]);
+                e[k] = -(v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f)) * log1pf(-fabsf(v));
+            } else {
+                e[k] = cauchy_noise(wd[k]);
+            }
+        }
+    }
+}
+
 // One thread per (sample n, row j of the pass), lanes along n; a workgroup = 64 samples x 8 rows (a wave takes two), as bnn_upper.
 // LDSW: the small tensors of the 64 samples staged once per workgroup, transposed ([row][sample]), and the thread's two activation
 // buffers a column of LDS each ([unit][thread]); else both in global memory.  The arithmetic of the forward sweep is bnn_upper's, in
@@ -1993,31 +2020,13 @@ __global__ void __launch_bounds__(256) bnn_predict_fwd(const BParams Q, const Bn
             }
         } else if (V.z_out) for (uint32_t c = 0; c < C; ++c) V.z_out[at + c] = Y(cur, c);
         u32x4 x = {0u, 0u, 0u, 0u};
-        if (V.draw_out && Q.likelihood != BSVI_LIK_NORMAL)
-            x = philox4x32(Q.sample_base + n, m, Q.offset_lo, Q.offset_hi, Q.seed_lo ^ BNN_KEY_PREDICT, Q.seed_hi);
+        if (V.draw_out && Q.likelihood != BSVI_LIK_NORMAL) x = bnn_predict_words(Q, n, m, 0u);
         if (Q.likelihood == BSVI_LIK_NORMAL) {
             for (uint32_t c = 0; c < C; ++c) pp[c] = Y(cur, c);
             if (V.draw_out) {
                 for (uint32_t c0 = 0; c0 < C; c0 += 4u) {
-                    const u32x4 w = philox4x32(Q.sample_base + n, m, Q.offset_lo, Q.offset_hi, Q.seed_lo ^ BNN_KEY_PREDICT, Q.seed_hi ^ (c0 >> 2));
                     float e[4];
-                    if (Q.family == BSVI_DIST_NORMAL) {
-                        box_muller_fast(w.x, w.y, e[0], e[1]);
-                        box_muller_fast(w.z, w.w, e[2], e[3]);
-                    } else {
-                        // Laplace | Cauchy: ONE word per output, word c & 3 of the call the Normal's output c reads (philox.h) — a word of
-                        // its own for every output, so that no two outputs of a row share a draw.  The library's draws of the two
-                        // families (dist_math.h, sample_from_noise_generic): Laplace -sign(v) log1p(-|v|) of the uniform base noise v
-                        const uint32_t wd[4] = {w.x, w.y, w.z, w.w};
-                        for (uint32_t k = 0; k < 4u; ++k) {
-                            if (Q.family == BSVI_DIST_LAPLACE) {
-                                const float v = laplace_noise(wd[k]);
-                                e[k] = -(v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f)) * log1pf(-fabsf(v));
-                            } else {
-                                e[k] = cauchy_noise(wd[k]);
-                            }
-                        }
-                    }
+                    bnn_predict_noise4(Q, n, m, c0, e);
                     for (uint32_t c = c0; c < C && c < c0 + 4u; ++c) V.draw_out[at + c] = Y(cur, c) + (Q.heads ? sp[c] : V.sg[c]) * e[c - c0];
                 }
             }

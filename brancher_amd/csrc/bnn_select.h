@@ -101,6 +101,64 @@ inline PredictLayout predict_layout(uint32_t R, uint32_t Rs, uint32_t P, uint32_
     return L;
 }
 
+// ---- the predictive of a particle ensemble (bsvi_bnn_predict_particles, bnn_ensemble.inc): every size its launch derives.
+// A workgroup of 256 owns `rows` rows of x (128; 64 or 32 when two activation tiles of 128 rows do not fit) and walks groups of `group`
+// particles.  LDS, in floats: the staged K chunks of A and B, two buffers each [2][128][ENS_CHUNK + 1] | tile 0 | tile 1, tile t
+// [group][rows][stride_t] holding the outputs of the layers l with l % 2 == t (stride: the widest of them plus one slot, odd).
+constexpr uint32_t ENS_ROWS = 128, ENS_CHUNK = 32, ENS_BLOCKS = 4, ENS_MAX_WIDTH = 320, ENS_WORKGROUPS = 512;
+constexpr size_t ENS_STAGE_FLOATS = 2u * 2u * ENS_ROWS * (ENS_CHUNK + 1u);
+
+struct EnsemblePlan {
+    uint32_t served;                // 0: a layer is wider than ENS_MAX_WIDTH (`widest` names it)
+    uint32_t widest;
+    uint32_t group;                 // particles a workgroup carries at once
+    uint32_t blocks;                // 32-column MFMA blocks held in accumulators at once (of the first product's columns group x H1)
+    uint32_t rows;                  // rows of x per workgroup
+    uint32_t stride[2], tile[2];    // the tiles' row strides and offsets, in floats
+    size_t lds_bytes;
+    uint32_t n_groups, row_tiles, splits;      // grid (row_tiles, splits): split y takes the groups y, y + splits, ...
+    size_t sigma, probs, workspace_bytes;      // the workspace: sigma [C] | probs [N][M][C] (used when the caller keeps none)
+};
+
+// widths: the layers' output widths (hidden ..., C), n_layers of them
+inline EnsemblePlan ensemble_plan(const uint32_t* widths, uint32_t n_layers, uint32_t n_particles, uint32_t n_rows) {
+    EnsemblePlan E{};
+    uint32_t w[2] = {0u, 0u};
+    for (uint32_t l = 0; l < n_layers; ++l) {
+        if (widths[l] > E.widest) E.widest = widths[l];
+        if (widths[l] > w[l & 1u]) w[l & 1u] = widths[l];
+    }
+    const uint32_t C = n_layers ? widths[n_layers - 1u] : 0u, H1 = n_layers ? widths[0] : 0u;
+    if (!n_layers || !H1 || !n_particles || !n_rows || E.widest > ENS_MAX_WIDTH) return E;
+    // (the head leaves the probabilities and the draw's class beside the logits' tile: C + 1 slots of the other one)
+    if (w[n_layers & 1u] < C + 1u) w[n_layers & 1u] = C + 1u;
+    for (uint32_t t = 0; t < 2u; ++t) E.stride[t] = (w[t] + 1u) | 1u;
+    const uint32_t cols = ENS_BLOCKS * 32u;
+    uint32_t fit = H1 >= cols ? 1u : cols / H1;
+    if (fit > n_particles) fit = n_particles;
+    for (uint32_t rows = ENS_ROWS; rows >= 32u && !E.group; rows /= 2u)
+        for (uint32_t g = fit; g >= 1u; --g)
+            if ((ENS_STAGE_FLOATS + (size_t)g * rows * (E.stride[0] + E.stride[1])) * 4u <= LDS_LIMIT) { E.group = g; E.rows = rows; break; }
+    if (!E.group) return E;      // (never for a width within ENS_MAX_WIDTH: one particle on 32 rows fits)
+    E.served = 1u;
+    const uint32_t first_blocks = (E.group * H1 + 31u) / 32u;
+    E.blocks = first_blocks < ENS_BLOCKS ? first_blocks : ENS_BLOCKS;
+    E.tile[0] = (uint32_t)ENS_STAGE_FLOATS;
+    E.tile[1] = E.tile[0] + E.group * E.rows * E.stride[0];
+    E.lds_bytes = ((size_t)E.tile[1] + (size_t)E.group * E.rows * E.stride[1]) * 4u;
+    E.n_groups = (n_particles + E.group - 1u) / E.group;
+    E.row_tiles = (n_rows + E.rows - 1u) / E.rows;
+    // few row tiles (the one-row call): the groups are dealt over grid.y until the chip has ENS_WORKGROUPS workgroups
+    E.splits = E.row_tiles >= ENS_WORKGROUPS ? 1u : (ENS_WORKGROUPS + E.row_tiles - 1u) / E.row_tiles;
+    if (E.splits > E.n_groups) E.splits = E.n_groups;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255u) / 256u * 256u; return at; };
+    E.sigma = take((size_t)C * 4u);
+    E.probs = take((size_t)n_particles * n_rows * C * 4u);
+    E.workspace_bytes = o + 256u;
+    return E;
+}
+
 inline const char* name(int kind) {
     switch (kind) {
     case MID_GEN: return "mid_gen";

@@ -2447,6 +2447,7 @@ extern "C" int bsvi_debug_math(int fn, int dist, const float* x_dev, const float
 #include "dense_kernel.inc"
 #include "bnn_kernel.inc"
 #include "bnn_particles.inc"
+#include "bnn_ensemble.inc"
 #include "dense_particles.inc"
 #include "dense_predict.inc"
 

@@ -365,7 +365,7 @@ class SteinVariationalGradientDescent(InferenceMethod):
         launch (`CompiledDense.predict_particles`, csrc/dense_predict.inc): "probs" [N, M, C] per particle, "mean" [M, C] the
         ensemble's predictive, on request "outputs" (logits) and "draws".  When this instance's batched plan holds these particles its
         table is read in place — no copy, no gather; otherwise an engine and the table of the particles' current values are built for
-        the call.  Particles of a Bayesian neural network are refused: their ensemble has no fused predictive."""
+        the call.  Particles of a Bayesian neural network are refused here: `predict_network` serves them."""
         import torch
         from brancher_amd import dense, lowering
         self.check_model_compatibility(None, posterior_model, None)
@@ -378,7 +378,7 @@ class SteinVariationalGradientDescent(InferenceMethod):
             except lowering.LoweringError as err:
                 raise ValueError("SteinVariationalGradientDescent.predict serves the particles of a logistic regression (the dense-link path); "
                                  "the predictive of the particles of a Bayesian neural network, or of another model, is not served "
-                                 "({})".format(err)) from None
+                                 "({}); the particles of a Bayesian neural network: predict_network".format(err)) from None
             if not program.point_estimate:
                 raise ValueError("SteinVariationalGradientDescent.predict: {} has a Normal posterior, a particle is a point estimate".format(program.latent_name))
             bound = [(par, par._store, par._offset) for par, _, _, _ in program.parameters]
@@ -388,6 +388,39 @@ class SteinVariationalGradientDescent(InferenceMethod):
             dim = program.n_classes * program.n_features
             values = np.stack([next(v for v in particle.flatten() if v.name == program.latent_name).parameter.numpy().reshape(-1)
                                for particle in posterior_model]).astype(np.float32)
+            table = torch.from_numpy(values).to(compiled.device)
+        return compiled.predict_particles(table, x, dim=dim, want_outputs=want_outputs, want_draws=want_draws)
+
+    def predict_network(self, joint_model, posterior_model, x, want_outputs=False, want_draws=False):
+        """The predictive of the particle ensemble of a Bayesian neural network on the rows `x`, the whole chain of all particles in one
+        fused kernel (`CompiledBnn.predict_particles`, csrc/bnn_ensemble.inc): "probs" [N, M, C] per particle, "mean" [M, C] the
+        ensemble's predictive, "var" [M, C] where the likelihood has one, on request "outputs" (logits | loc) and "draws".  When this
+        instance's batched plan holds these particles its table is read in place — no copy, no gather; otherwise an engine and the table
+        of the particles' current values, in the tensors' row order, are built for the call and the parameters' bindings restored."""
+        import torch
+        from brancher_amd import bnn, lowering
+        self.check_model_compatibility(None, posterior_model, None)
+        plan = self._plan
+        if plan is not None and plan.get("key") == tuple(id(p) for p in posterior_model) and isinstance(plan.get("compiled"), bnn.CompiledBnn):
+            compiled, table, dim = plan["compiled"], plan["theta"], plan["dim"]
+        else:
+            try:
+                program = bnn.lower_bnn(joint_model, posterior_model[0], "pathwise")
+            except lowering.LoweringError as err:
+                raise ValueError("SteinVariationalGradientDescent.predict_network serves the particles of a Bayesian neural network (the BNN "
+                                 "path, CompiledBnn); this model is not one it lowers ({})".format(err)) from None
+            bnn.check_particles(program, len(posterior_model))
+            bound = [(par, par._store, par._offset) for par, _, _, _ in program.parameters]
+            compiled = bnn.CompiledBnn(joint_model, posterior_model[0], "pathwise", program=program)
+            for par, store, offset in bound:                   # (the constructor bound them to itself)
+                par.unbind() if store is None else par.bind(store, offset)
+            dim = program.n_rows
+            values = np.zeros((len(posterior_model), dim), dtype=np.float32)
+            by_name = {t["name"]: t for t in program.tensors}
+            for row, particle in enumerate(posterior_model):
+                for var in particle.flatten():
+                    t = by_name[var.name]
+                    values[row, t["row0"]:t["row0"] + t["size"]] = var.parameter.numpy().reshape(-1)
             table = torch.from_numpy(values).to(compiled.device)
         return compiled.predict_particles(table, x, dim=dim, want_outputs=want_outputs, want_draws=want_draws)
 

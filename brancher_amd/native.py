@@ -511,6 +511,56 @@ def bnn_particles_fwd_bwd(handle, params, out, theta, grad, loss, seed=0, offset
     return workspace
 
 
+# ... and the predictive of that ensemble on rows the caller hands in, one fused forward kernel (csrc/bnn_ensemble.inc)
+class BnnPredictParticlesArgs(Sized):
+    """bsvi_bnn_predict_particles_args (no bsvi_struct_kind of its own: load() checks it against bsvi_bnn_predict_particles_args_size())"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32),
+                ("theta_dev", C.c_void_p), ("ld", C.c_uint64), ("x_dev", C.c_void_p), ("n_particles", C.c_uint32), ("n_rows", C.c_uint32),
+                ("seed", C.c_uint64), ("offset", C.c_uint64),
+                ("p_out", C.c_void_p), ("z_out", C.c_void_p), ("mean_out", C.c_void_p), ("var_out", C.c_void_p), ("draw_out", C.c_void_p),
+                ("params_dev", C.c_void_p), ("workspace_dev", C.c_void_p), ("stream", C.c_void_p)]
+
+
+EXPORTS.update({
+    "bsvi_bnn_predict_particles_args_size": (C.c_size_t, []),
+    "bsvi_bnn_predict_particles_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "bsvi_bnn_predict_particles": (C.c_int, [C.c_void_p, C.POINTER(BnnPredictParticlesArgs)]),
+})
+
+
+def bnn_predict_particles(handle, params, table, x, n_outputs, seed=0, offset=0, want_var=False, want_outputs=False, want_draws=False,
+                          workspace=None):
+    """bsvi_bnn_predict_particles on a bsvi_bnn `handle` whose rows are all points: `x` [M][P] against the particles `table` [N][ld]
+    (contiguous f32 on the device, the layout of `bnn_particles_fwd_bwd`), read in place.  Returns (result, workspace): "probs"
+    [N, M, C], "mean" [M, C], with want_var "var" [M, C], on request "outputs" and "draws" — device tensors — and the workspace for the
+    next call of the same shape."""
+    import torch
+    lib = load()
+    for name, t in (("x", x), ("table", table)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.ndim != 2 or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("bnn_predict_particles: {} is not a contiguous two-dimensional f32 device tensor".format(name))
+    (n, ld), m, c = table.shape, int(x.shape[0]), int(n_outputs)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    with torch.cuda.device(x.device):
+        need = lib.bsvi_bnn_predict_particles_workspace_bytes(handle, n, m)
+        if need == 0:
+            check(-1)
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+        new = lambda *shape: torch.empty(shape, device=x.device)
+        res = dict(probs=new(n, m, c), mean=new(m, c))
+        for key, want, shape in (("var", want_var, (m, c)), ("outputs", want_outputs, (n, m, c)), ("draws", want_draws, (n, m, c))):
+            if want:
+                res[key] = new(*shape)
+        args = BnnPredictParticlesArgs(theta_dev=ptr(table), ld=int(ld), x_dev=ptr(x), n_particles=n, n_rows=m, seed=int(seed),
+                                       offset=int(offset), p_out=ptr(res["probs"]), z_out=ptr(res.get("outputs")),
+                                       mean_out=ptr(res["mean"]), var_out=ptr(res.get("var")), draw_out=ptr(res.get("draws")),
+                                       params_dev=ptr(params), workspace_dev=ptr(workspace),
+                                       stream=C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        check(lib.bsvi_bnn_predict_particles(handle, C.byref(args)))
+    return res, workspace
+
+
 # ... and all particles of a dense-link model (logistic regression) in one fused kernel (csrc/dense_particles.inc)
 EXPORTS.update({
     "bsvi_dense_particles_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_uint32]),
@@ -639,6 +689,9 @@ def load():
     if lib.bsvi_dense_predict_args_size() != C.sizeof(DensePredictArgs):
         raise NativeError("DensePredictArgs: this binding declares {} bytes, libbsvi.so {} (include/bsvi.h and native.py disagree)".format(
             C.sizeof(DensePredictArgs), lib.bsvi_dense_predict_args_size()))
+    if lib.bsvi_bnn_predict_particles_args_size() != C.sizeof(BnnPredictParticlesArgs):
+        raise NativeError("BnnPredictParticlesArgs: this binding declares {} bytes, libbsvi.so {} (include/bsvi.h and native.py disagree)".format(
+            C.sizeof(BnnPredictParticlesArgs), lib.bsvi_bnn_predict_particles_args_size()))
     _lib = lib
     return lib
 

@@ -25,13 +25,13 @@ def main(n_particles=16, iterations=300, lr=2e-4):
 
     program = method.last_compiled.program
     x, y = program.dataset, program.labels                       # [rows, 64], [rows, 1]
-    value = lambda particle, name: next(v for v in particle.flatten() if v.name == name).parameter.numpy().reshape(shapes[name])
-    predictions = np.stack([np.tanh(x @ value(p, "weights1").T + value(p, "b1").T) @ value(p, "weights2").T + value(p, "b2").T for p in particles])
+    result = method.predict_network(model, particles, x)      # all particles on all rows in one fused kernel, their table read in place
+    mean, spread = result["mean"].cpu().numpy(), result["probs"].std(0, unbiased=False).cpu().numpy()      # [rows, 1] each
     curve = model.diagnostics["loss curve"]
     print("loss (sum over %d particles): %.1f -> %.1f, last bandwidth %.3f" % (n_particles, curve[0], curve[-1], method.bandwidth))
-    print("rmse of the particles' mean prediction: %.3f (noise scale 0.5)" % np.sqrt(((predictions.mean(0) - y) ** 2).mean()))
+    print("rmse of the particles' mean prediction: %.3f (noise scale 0.5)" % np.sqrt(((mean - y) ** 2).mean()))
     print("predictive spread over the particles, per row: mean %.3f, min %.3f, max %.3f" % (
-        predictions.std(0).mean(), predictions.std(0).min(), predictions.std(0).max()))
+        spread.mean(), spread.min(), spread.max()))
 
 
 if __name__ == "__main__":

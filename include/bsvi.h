@@ -1226,6 +1226,46 @@ size_t bsvi_dense_predict_args_size(void);
 size_t bsvi_dense_predict_workspace_bytes(const bsvi_dense* d, uint32_t n_sets, uint32_t n_rows, uint32_t sets_per_split);
 int bsvi_dense_predict(const bsvi_dense* d, const bsvi_dense_predict_args* args);
 
+/* (ABI 11, entry points and a struct of their own added; no existing struct changes) The predictive of a particle ensemble of a Bayesian
+ * neural network on rows the CALLER hands in, forward only, one fused kernel (csrc/bnn_ensemble.inc).  theta_dev [n_particles][ld] is the
+ * table of bsvi_bnn_particles_fwd_bwd (particle n's value of row r at theta_dev[n * ld + r]), read in place for any ld >= the model's
+ * number of rows and any alignment (16-byte loads where an address allows); columns past the last row are never read.  For
+ * x_dev [n_rows][n_features] and per (particle n, row m), as bsvi_bnn_predict defines them with the particle in the place of the sample:
+ *   z [n_particles][n_rows][C]     the head's raw outputs: logits, or the loc of the Normal / Laplace / Cauchy likelihood
+ *   p [n_particles][n_rows][C]     softmax probabilities (log-softmax, then expf) | the sigmoid of the single logit | the loc
+ *   mean [n_rows][C]               the mean of p over the particles, in the order n = 0, 1, ... in double precision
+ *   var [n_rows][C]                the population variance of the loc about that mean + sigma_c^2 (Laplace: + 2 sigma_c^2)
+ *   draw [n_particles][n_rows][C]  one draw of the likelihood per (n, m) from bsvi_bnn_predict's stream (key word k0 ^ 0x2545F491,
+ *                                  c0 = n, c1 = m, the offset in c2 / c3), drawn as that call draws
+ * Every output pointer is optional (NULL: not written).  params_dev: the handle's parameter vector (sigma goes through the uniform
+ * table).  No atomics, every sum in a fixed order: the same inputs give the same bits, however the grid was split.  Nothing of the
+ * handle's training state is touched.  Served: what bsvi_bnn_particles_fwd_bwd serves (every row a point, no scale latents, no learnable
+ * sigma, no scale head, 2 .. 256 particles; the refusals keep that call's wording), layers of up to 320 units (what two activation tiles
+ * of 32 rows leave of a workgroup's LDS; wider: BSVI_ERR_UNSUPPORTED with the width and the limit), any number of features and rows.
+ * var_out on a classifier is BSVI_ERR_INVALID, on a Cauchy likelihood BSVI_ERR_UNSUPPORTED. */
+typedef struct bsvi_bnn_predict_particles_args {
+    uint32_t struct_size;            /* sizeof(bsvi_bnn_predict_particles_args) */
+    uint32_t reserved0;
+    const float* theta_dev;          /* [n_particles][ld]                                                       */
+    uint64_t ld;
+    const float* x_dev;              /* [n_rows][n_features]                                                    */
+    uint32_t n_particles, n_rows;
+    uint64_t seed, offset;
+    float* p_out;                    /* [n_particles][n_rows][C] or NULL                                        */
+    float* z_out;                    /* [n_particles][n_rows][C] or NULL                                        */
+    float* mean_out;                 /* [n_rows][C] or NULL                                                     */
+    float* var_out;                  /* [n_rows][C] or NULL; Normal and Laplace likelihoods only                */
+    float* draw_out;                 /* [n_particles][n_rows][C] or NULL                                        */
+    const float* params_dev;         /* [n_params]                                                              */
+    void* workspace_dev;             /* bsvi_bnn_predict_particles_workspace_bytes(...) bytes, 256-byte aligned */
+    void* stream;
+} bsvi_bnn_predict_particles_args;
+/* sizeof(bsvi_bnn_predict_particles_args) inside this build of the library (no bsvi_struct_kind: the kinds are a closed list) */
+size_t bsvi_bnn_predict_particles_args_size(void);
+/* bytes of workspace of a call with these sizes; 0: not served (bsvi_last_error names the limit) */
+size_t bsvi_bnn_predict_particles_workspace_bytes(const bsvi_bnn* b, uint32_t n_particles, uint32_t n_rows);
+int bsvi_bnn_predict_particles(const bsvi_bnn* b, const bsvi_bnn_predict_particles_args* args);
+
 const char* bsvi_last_error(void);
 int bsvi_abi_version(void);
 /* number of gfx950 devices visible to the HIP runtime (0 if none) */
