@@ -235,7 +235,7 @@ def _constant_parameter(var, name, positive):
 
 def lower_amortized(joint, posterior, estimator="pathwise"):
     if estimator not in ("pathwise", "blackbox"):
-        raise LoweringError("the amortised path implements the Pathwise and BlackBox estimators")
+        raise LoweringError("the amortised path implements the Pathwise and BlackBox estimators, not %r" % (estimator,))
     q_flat, p_flat = posterior._flatten(), joint._flatten()
     q_random = [v for v in q_flat if _is_random(v)]
     q_emp = [v for v in q_random if v.distribution.kind == D.DIST_EMPIRICAL]

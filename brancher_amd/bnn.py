@@ -305,7 +305,7 @@ def lower_bnn(joint, posterior, estimator="pathwise"):
     # (CompiledBnn supplies it); the entropy of a Normal does not depend on the draw.  The reference tiles the means to number_samples
     # identical rows and averages: kept (N identical samples), so that the value rounds as the reference's does.
     if estimator not in ("pathwise", "blackbox", "taylor1"):
-        raise LoweringError("the bnn path implements the Pathwise, BlackBox and Taylor1 estimators")
+        raise LoweringError("the bnn path implements the Pathwise, BlackBox and Taylor1 estimators, not %r" % (estimator,))
     L = _Lowering(joint, posterior, estimator)
     q_flat = posterior._flatten()
     L.q_by_name = {v.name: v for v in q_flat}

@@ -2450,6 +2450,7 @@ extern "C" int bsvi_debug_math(int fn, int dist, const float* x_dev, const float
 #include "bnn_ensemble.inc"
 #include "dense_particles.inc"
 #include "dense_predict.inc"
+#include "dense_local.inc"
 
 // ---- the minibatch data path of the scalar engine (standard_variables.py:71-112, distributions.py:393-473) ------------
 // A variable observed through an EmpiricalVariable sees `batch` rows of a dataset, other rows in every evaluation.  To the per-sample

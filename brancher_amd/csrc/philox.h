@@ -24,6 +24,11 @@
 // weights' 0x40000000 and the scalar engines' 0x80000000), c2 / c3 = the 64-bit offset; set n and row m read u01(word m & 3).  The weights
 // of that pass are the dense path's ordinary draw (c1 = (row >> 2) | 0x40000000).
 //
+// The local reparameterisation estimator of the dense-link path (dense_local.inc, bsvi_dense_local_fwd_bwd) draws the logits' normals
+// zeta[n][b][c] with a counter tag of its own and the seed as it is:  c0 = sample n, c1 = (4 b + (c >> 2)) | 0x10000000 for minibatch row b
+// (b < 2^24; next to 0x20000000, 0x40000000 and 0x80000000 above), c2 / c3 = the 64-bit offset; class c takes normal c & 3 of the call's
+// four box_muller_fast normals ((x, y) -> 0, 1; (z, w) -> 2, 3).  No weight is drawn on that path.
+//
 // Latent prior scales of the Bayesian neural networks (bsvi_bnn_set_scale_latents): with quads = ceil(n_rows / 4), latent t takes
 // normal t & 3 of the ordinary row-quad call whose quad index is quads + (t >> 2) — c1 = (quads + (t >> 2)) | 0x40000000, the same
 // counters, key and box_muller_fast pairing as the rows, behind every quad a row uses.  A pure function of (seed, offset, global sample,

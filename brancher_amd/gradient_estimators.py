@@ -8,6 +8,7 @@ same fused kernel (include/bsvi.h `bsvi_estimator`), which evaluates
   Pathwise :  mean_s f(z_s),                      z = reparameterised draw      (:39-44)
   BlackBox :  mean_s [ log q(z_s) * stopgrad(f(z_s)) + f(z_s) ]                  (:29-36)
   Taylor1  :  mean_s f(E[q | sampled parents]_s)  — a different program, same accumulation  (:47-56)
+  LocalReparameterization :  mean_s log p(y | z_s) - KL(q || p),  z = the link's Normal pre-activations, drawn directly (dense-link path)
 
 BlackBox reproduces the reference exactly, including that its value is not the ELBO and that
 reparameterisable nodes still carry the pathwise term (the ``differentiable=False`` flag is
@@ -53,6 +54,13 @@ class PathwiseDerivativeEstimator(_Fused):
 
 class BlackBoxEstimator(_Fused):
     kernel_name = "blackbox"
+
+
+class LocalReparameterizationEstimator(_Fused):
+    # Kingma, Salimans and Welling (2015): for a mean-field Normal posterior over the weights of a LINEAR link the logits of a minibatch
+    # row are Normal themselves and are sampled directly — the same ELBO, a lower-variance gradient, no weight draw per sample and a
+    # closed-form KL term.  Served by the dense-link path (dense.py, csrc/dense_local.inc); not in the reference.
+    kernel_name = "local"
 
 
 class Taylor1Estimator(_Fused):

@@ -54,7 +54,9 @@ UT = dict(identity=0, softplus=1, sigmoid=2, exp=3, log=4, tanh=5, sqrt=6, squar
 # per-sample output log q(z) — `ProbabilisticModel.get_importance_weights`, variables.py:821-841
 # "taylor1" (`gradient_estimators.py:47-56`) is the pathwise accumulation of f evaluated at the posterior's analytic
 # means given the sampled parents: a different PROGRAM for the same kernel estimator (see _Lowering.mean_value)
-EST = dict(pathwise=0, blackbox=1, importance=0, taylor1=0)
+# "local" (local reparameterisation, Kingma et al. 2015) is a launch sequence of its own on a Pathwise handle of the dense-link path
+# (dense.py, csrc/dense_local.inc); the scalar, BNN and amortised lowerings refuse it
+EST = dict(pathwise=0, blackbox=1, importance=0, taylor1=0, local=0)
 
 UNARY_CALLS = set(UNOP) - {"copy", "powi"}
 
@@ -256,7 +258,7 @@ class _ModuleTensor:
 class _Lowering:
     def __init__(self, joint, posterior, estimator):
         if estimator not in EST:
-            raise ValueError("unknown gradient estimator %r" % (estimator,))
+            raise LoweringError("unknown gradient estimator %r" % (estimator,))
         self.joint, self.posterior, self.estimator = joint, posterior, estimator
         self.ir_cache = {}
         self.q_by_name = {}
@@ -2127,6 +2129,9 @@ def lower(joint_model, posterior_model=None, estimator="pathwise", external="inj
         posterior_model = joint_model.posterior_model
     if not isinstance(joint_model, ProbabilisticModel) or not isinstance(posterior_model, ProbabilisticModel):
         raise ValueError("lower() expects probabilistic models")
+    if estimator == "local":
+        raise LoweringError("the scalar path does not implement the 'local' estimator (local reparameterisation needs a linear link: "
+                            "the dense-link path serves it)")
     low = _Lowering(joint_model, posterior_model, estimator)
     low.external_mode = external
     return low.run()

@@ -649,6 +649,22 @@ def dense_predict(handle, x, n_sets, n_classes, params=None, table=None, noise=N
     return res, workspace
 
 
+# ... and the local reparameterisation estimator of the dense-link path (csrc/dense_local.inc)
+class DenseLocalArgs(Sized):
+    """bsvi_dense_local_args (no bsvi_struct_kind of its own: the call checks struct_size against the library's sizeof)"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_samples", C.c_uint32),
+                ("params_dev", C.c_void_p), ("out_dev", C.c_void_p), ("workspace_dev", C.c_void_p), ("stream", C.c_void_p),
+                ("seed", C.c_uint64), ("offset", C.c_uint64),
+                ("noise_dev", C.c_void_p), ("noise_out_dev", C.c_void_p), ("indices_dev", C.c_void_p), ("indices_out_dev", C.c_void_p),
+                ("loss_slot_dev", C.c_void_p), ("finite_slot_dev", C.c_void_p)]
+
+
+EXPORTS.update({
+    "bsvi_dense_local_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_uint32]),
+    "bsvi_dense_local_fwd_bwd": (C.c_int, [C.c_void_p, C.POINTER(DenseLocalArgs)]),
+})
+
+
 # bsvi_struct_kind (include/bsvi.h) -> the ctypes mirror of the struct: load() checks every size against bsvi_sizeof()
 STRUCT_KINDS = {0: UniformEntry, 1: Record, 2: ProgramDesc, 3: ElboArgs, 4: OptCfg, 5: DenseDesc, 6: DenseArgs, 7: MlpLayer,
                 8: AmortDesc, 9: AmortArgs, 10: MvnInsn, 11: MvnDesc, 12: MvnArgs, 13: BnnLayer, 14: BnnDesc, 15: BnnArgs,

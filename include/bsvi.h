@@ -1266,6 +1266,41 @@ size_t bsvi_bnn_predict_particles_args_size(void);
 size_t bsvi_bnn_predict_particles_workspace_bytes(const bsvi_bnn* b, uint32_t n_particles, uint32_t n_rows);
 int bsvi_bnn_predict_particles(const bsvi_bnn* b, const bsvi_bnn_predict_particles_args* args);
 
+/* (ABI 11, entry points and a struct of their own added; no existing struct changes) The local reparameterisation estimator of a
+ * dense-link model (Kingma, Salimans and Welling 2015; csrc/dense_local.inc): for a mean-field Normal posterior over the weights of the
+ * linear link the logits of minibatch row b are Normal, m[b][c] = sum_p x[b][p] mu[c][p], v[b][c] = sum_p x[b][p]^2 s[c][p]^2, and are
+ * sampled directly, z_n[b][c] = m + sqrt(v) zeta[n][b][c]:
+ *   loss = -( lik_weight (1 / n_samples) sum_n sum_b log p(y_b | z_n[b]) + sum_r [ prior_weight (-log s0 - log sqrt(2 pi)
+ *             - ((mu - mu0)^2 + s^2) / (2 s0^2)) + entropy_weight (log sqrt(2 pi e) + log s) ] )
+ * an unbiased gradient of the ELBO bsvi_dense_fwd_bwd estimates, with two products instead of 2 n_samples and a closed-form KL term.
+ * After the call out_dev is what bsvi_dense_fwd_bwd followed by bsvi_dense_finalize leaves: out[2] = loss, out[3] = finite flag,
+ * out[4..] = d loss / d theta; bsvi_optimizer_step applies it.  The minibatch is the one bsvi_dense_fwd_bwd gathers at the same
+ * (seed, offset), or indices_dev.  zeta is noise_dev [n_samples][B][C] or drawn: normal c & 3 (box_muller_fast of words (x, y), (z, w))
+ * of the Philox call with counter (n, (4 b + (c >> 2)) | 0x10000000, offset low, offset high) and the seed as the key; noise_out_dev
+ * receives what was used, and a call handed that noise leaves the same bits.  Where v = 0 (an all-zero row) z = m.  The handle is an
+ * ordinary bsvi_dense_create handle with BSVI_EST_PATHWISE.  No atomics, every sum in a fixed order.  BSVI_ERR_INVALID with the reason
+ * in bsvi_last_error: a point-estimate handle, more than 16 classes, n_samples of 0 or above 65536, null arguments, a workspace that is
+ * not 256-byte aligned.  Single GPU: all n_samples are computed by the caller's device. */
+typedef struct bsvi_dense_local_args {
+    uint32_t struct_size;            /* sizeof(bsvi_dense_local_args) */
+    uint32_t n_samples;
+    const float* params_dev;         /* [n_params]                                                              */
+    float* out_dev;                  /* [BSVI_OUT_HEADER + n_params]                                            */
+    void* workspace_dev;             /* bsvi_dense_local_workspace_bytes(d, n_samples) bytes, 256-byte aligned  */
+    void* stream;
+    uint64_t seed, offset;
+    const float* noise_dev;          /* zeta [n_samples][B][C] or NULL -> Philox                                */
+    float* noise_out_dev;            /* zeta used [n_samples][B][C] or NULL                                     */
+    const int32_t* indices_dev;      /* minibatch rows [B] or NULL -> the draw of (seed, offset)                */
+    int32_t* indices_out_dev;        /* [B] or NULL                                                             */
+    float* loss_slot_dev;            /* NULL, or where the loss is logged as well (a training loop's curve)     */
+    float* finite_slot_dev;          /* NULL, or where the finite flag is logged as well                        */
+} bsvi_dense_local_args;
+/* bytes of workspace of a call with n_samples; 0: not served (bsvi_last_error names the limit).  The environment variable
+ * BSVI_LOCAL_SPLITS (the number of sample splits of the forward launch; tests and timing) is read by both calls. */
+size_t bsvi_dense_local_workspace_bytes(const bsvi_dense* d, uint32_t n_samples);
+int bsvi_dense_local_fwd_bwd(const bsvi_dense* d, const bsvi_dense_local_args* args);
+
 const char* bsvi_last_error(void);
 int bsvi_abi_version(void);
 /* number of gfx950 devices visible to the HIP runtime (0 if none) */
