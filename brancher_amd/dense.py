@@ -413,11 +413,12 @@ class CompiledDense:
         if engine.dist_info()[1] > 1:
             raise ValueError("the 'local' estimator runs on one GPU: its samples are not sharded over ranks (world size {})".format(
                 engine.dist_info()[1]))
+        # asked on every call: the plan reads BSVI_LOCAL_SPLITS per call, and more splits need more of dM / dV than the cached block has
+        need = int(self.lib.bsvi_dense_local_workspace_bytes(self.handle, N))
+        if need == 0:
+            native.check(-1)
         ws = self._workspaces.get(("local", N))
-        if ws is None:
-            need = int(self.lib.bsvi_dense_local_workspace_bytes(self.handle, N))
-            if need == 0:
-                native.check(-1)
+        if ws is None or ws.numel() < need:
             ws = self._workspaces[("local", N)] = torch.empty(need, dtype=torch.uint8, device=self.device)
         return native.DenseLocalArgs(n_samples=N, params_dev=self.params.data_ptr(), out_dev=self.out.data_ptr(), workspace_dev=ws.data_ptr(),
                                      stream=self._stream(), seed=_engine.shared_seed(seed, self.device), offset=int(offset))

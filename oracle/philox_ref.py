@@ -12,6 +12,9 @@ The contract: every draw is a pure function of (seed, global sample index, noise
                                       (stream << 12) + try for the gammas of a Beta (stream 1: alpha, stream 2: beta)
     dense and BNN                     c0 = sample, c1 = (row >> 2) | 0x40000000
     amortised latents                 c0 = sample * B + b, c1 = d >> 1               one Box-Muller pair per call
+    dense predictive, likelihood draw c0 = sample_base + set, c1 = (m >> 2) | 0x20000000   row m of the caller's x reads u01(word m & 3)
+    dense local reparameterisation    c0 = sample, c1 = (4 b + (c >> 2)) | 0x10000000      minibatch row b < 2^24, class c takes normal
+                                      c & 3 of the call's two Box-Muller pairs
     dense minibatch (Feistel round)   c0 = right half, c1 = round, k0 ^ 0x5bd1e995
     amortised minibatch               c0 = right half, c1 = round | sample << 2, k0 ^ 0x7f4a7c15
     reduce node's drawn data          c0 = element // 4, c1 = 0x52454455, k0 ^ 0x3c6ef372
@@ -32,6 +35,7 @@ M0, M1 = 0xD2511F53, 0xCD9E8D57
 W0, W1 = 0x9E3779B9, 0xBB67AE85
 MASK32 = 0xFFFFFFFF
 FLAG_NORMAL, FLAG_DENSE = 0x80000000, 0x40000000
+FLAG_DENSE_PREDICT, FLAG_DENSE_LOCAL = 0x20000000, 0x10000000
 KEY_DENSE_MINIBATCH, KEY_AMORT_MINIBATCH, KEY_REDUCE_DATA = 0x5bd1e995, 0x7f4a7c15, 0x3c6ef372
 C1_REDUCE_DATA = 0x52454455
 FLOAT_EPS = float(np.finfo(np.float32).eps)
@@ -248,6 +252,41 @@ def scalar_counters(rows, beta_tries=64):
 def dense_noise(seed, offset, sample_base, n, n_rows, dtype=np.float64):
     """dense and BNN path: [n_rows, n]"""
     return normal_rows(seed, offset, np.arange(sample_base, sample_base + n), np.arange(n_rows), FLAG_DENSE, dtype)
+
+
+def local_counters(seed, offset, sample, b, c):
+    """(k0, k1, c0, c1, c2, c3) of the call behind zeta[sample][b][c] of the local reparameterisation estimator, broadcast"""
+    (k0, k1), (o0, o1) = split64(seed), split64(offset)
+    b, c = np.asarray(b, dtype=np.uint64), np.asarray(c, dtype=np.uint64)
+    c1 = (np.uint64(4) * b + (c >> np.uint64(2))) | np.uint64(FLAG_DENSE_LOCAL)
+    return k0, k1, np.asarray(sample, dtype=np.uint64), c1, o0, o1
+
+
+def local_noise(seed, offset, n, batch, classes, dtype=np.float64):
+    """local reparameterisation estimator of the dense path: the logits' normals zeta [n, batch, classes]"""
+    s, b, c = np.meshgrid(np.arange(n, dtype=np.uint64), np.arange(batch, dtype=np.uint64), np.arange(classes, dtype=np.uint64), indexing="ij")
+    k0, k1, c0, c1, o0, o1 = local_counters(seed, offset, s, b, c)
+    x = philox4x32(c0, c1, o0, o1, k0, k1)
+    z0, z1 = box_muller(x[0], x[1], dtype)
+    z2, z3 = box_muller(x[2], x[3], dtype)
+    j = c & np.uint64(3)
+    return np.where(j == 0, z0, np.where(j == 1, z1, np.where(j == 2, z2, z3)))
+
+
+def dense_predict_counters(seed, offset, sample, m):
+    """(k0, k1, c0, c1, c2, c3) of the call behind the likelihood draw of set `sample` (global) and row m of the dense predictive"""
+    (k0, k1), (o0, o1) = split64(seed), split64(offset)
+    c1 = (np.asarray(m, dtype=np.uint64) >> np.uint64(2)) | np.uint64(FLAG_DENSE_PREDICT)
+    return k0, k1, np.asarray(sample, dtype=np.uint64), c1, o0, o1
+
+
+def dense_predict_uniform(seed, offset, sample_base, n, m):
+    """dense predictive: the uniforms [n, m] (float32) behind the likelihood draws of sets sample_base .. sample_base + n - 1"""
+    s, r = np.meshgrid(np.arange(sample_base, sample_base + n, dtype=np.uint64), np.arange(m, dtype=np.uint64), indexing="ij")
+    k0, k1, c0, c1, o0, o1 = dense_predict_counters(seed, offset, s, r)
+    x = philox4x32(c0, c1, o0, o1, k0, k1)
+    w = r & np.uint64(3)
+    return u01(np.where(w == 0, x[0], np.where(w == 1, x[1], np.where(w == 2, x[2], x[3]))))
 
 
 def amortized_noise(seed, offset, sample_base, n, batch, dz, dtype=np.float64):

@@ -36,7 +36,55 @@ static void shape(uint32_t C, uint32_t P, uint32_t B, uint32_t N, uint32_t n_cu,
     CHECK(L.total - L.likp >= (size_t)L.splits * L.row_tiles * 4u);
 }
 
+// the shapes of tests/test_gpu_dense_local_branches.py and the branches they claim to reach: what the plan must say of each, at the 256
+// CUs of an MI355X and at 32 (the splits are the clamp ceil(N / 8) at both, so the cases reach their branches on either chip)
+struct Named { uint32_t C, P, B, N, row_tiles, k_chunks, rounds, col_tiles, CT, splits, sps; };
+static const Named NAMED[] = {
+    {2, 32, 32, 8, 1, 1, 1, 1, 4, 1, 8},            // everything exact, two dead classes of tier 4, P_pad > P
+    {4, 64, 64, 16, 2, 2, 1, 2, 4, 2, 8},           // tier 4 full, P = P_pad, B = B_pad
+    {5, 128, 96, 24, 3, 4, 1, 4, 10, 3, 8},         // lower edge of tier 10, one chunk a wave, three row tiles
+    {11, 260, 160, 81, 5, 9, 3, 9, 16, 11, 8},      // lower edge of tier 16, three rounds, wave 0 of bwd twice, the join's second group
+    {1, 40, 130, 20, 5, 2, 1, 2, 1, 3, 8},          // Bernoulli over five row tiles, split and joined
+    {3, 5, 33, 1, 2, 1, 1, 1, 4, 1, 8},             // N = 1
+    {10, 70, 64, 40, 2, 3, 1, 3, 10, 5, 8},         // the tail's shared-entry loop at R = 700
+    {11, 8, 40, 17, 2, 1, 1, 1, 16, 3, 8},          // the drawn normals against the host reference
+    {1, 8, 40, 17, 2, 1, 1, 1, 1, 3, 8},
+    {3, 5, 33, 9, 2, 1, 1, 1, 4, 2, 8},             // the training trajectory
+};
+
+static void named_shapes() {
+    for (const Named& s : NAMED) {
+        const uint32_t clamp = (s.N + LANES - 1u) / LANES;
+        for (uint32_t n_cu : {256u, 32u}) {
+            shape(s.C, s.P, s.B, s.N, n_cu, 0);
+            const Plan L = local_plan(s.C, s.P, s.B, s.N, n_cu, 2u * s.C * s.P, 0);
+            CHECK(L.row_tiles == s.row_tiles && L.k_chunks == s.k_chunks && (L.k_chunks + 3u) / 4u == s.rounds && L.col_tiles == s.col_tiles);
+            CHECK(L.CT == s.CT && L.splits == s.splits && L.samples_per_split == s.sps && L.splits == clamp);
+            if (!(L.row_tiles == s.row_tiles && L.k_chunks == s.k_chunks && L.col_tiles == s.col_tiles && L.CT == s.CT && L.splits == s.splits && L.samples_per_split == s.sps))
+                printf("  shape (%u, %u, %u, %u) at %u CUs: row_tiles %u k_chunks %u col_tiles %u CT %u splits %u sps %u\n", s.C, s.P, s.B, s.N, n_cu,
+                       L.row_tiles, L.k_chunks, L.col_tiles, L.CT, L.splits, L.samples_per_split);
+            // the knob from 1 up to the clamp: the workspace never shrinks, grows whenever the number of splits does, stays aligned
+            Plan before = local_plan(s.C, s.P, s.B, s.N, n_cu, 2u * s.C * s.P, 1);
+            CHECK(before.splits == 1u);
+            for (uint32_t forced = 1; forced <= clamp; ++forced) {
+                shape(s.C, s.P, s.B, s.N, n_cu, forced);
+                const Plan F = local_plan(s.C, s.P, s.B, s.N, n_cu, 2u * s.C * s.P, forced);
+                CHECK(F.splits >= before.splits && F.splits <= forced && F.total >= before.total && (F.splits == before.splits || F.total > before.total));
+                CHECK(F.total % 256u == 0u);
+                before = F;
+            }
+            CHECK(before.splits == clamp && before.total == L.total);
+        }
+    }
+    // the split counts the split-invariance and the workspace-cache tests ask for at (11, 260, 160, 81): 1, 3, 8, 9 -> 1, 3, 6, 6 splits
+    const uint32_t asked[] = {1, 3, 8, 9}, given[] = {1, 3, 6, 6};
+    for (int i = 0; i < 4; ++i) CHECK(local_plan(11, 260, 160, 81, 256, 0, asked[i]).splits == given[i]);
+    CHECK(local_plan(11, 260, 160, 81, 256, 0, 9).total > local_plan(11, 260, 160, 81, 256, 0, 1).total);
+    for (const Named& s : NAMED) printf("named shape %u %u %u %u\n", s.C, s.P, s.B, s.N);
+}
+
 int main() {
+    named_shapes();
     for (uint32_t n_cu : {1u, 64u, 256u}) {
         shape(1, 3, 5, 3, n_cu, 0);
         shape(3, 5, 33, 9, n_cu, 0);

@@ -56,3 +56,9 @@ def test_the_plan_function(tmp_path):
                            os.path.join(ROOT, "tests", "c_abi", "dense_local_plan.cpp")])
     out = subprocess.run([str(exe)], capture_output=True, text=True)
     assert out.returncode == 0 and "dense_local_plan: ok" in out.stdout, out.stdout + out.stderr
+    # every shape tests/test_gpu_dense_local_branches.py runs is one whose plan (tiles, chunks and rounds, tier, splits at 256 and at 32
+    # CUs) the program pinned: a change of local_plan that moves a case off the branch its comment names fails above, without a device
+    import test_gpu_dense_local_branches as branches
+    pinned = {tuple(int(v) for v in line.split()[2:]) for line in out.stdout.splitlines() if line.startswith("named shape ")}
+    run = {s[:4] for s in branches.SHAPES.values()} | {branches.SHARED, branches.DRAWN, branches.DRAWN_BERNOULLI, branches.TRAJECTORY}
+    assert len(pinned) == 10 and run == pinned, (sorted(run), sorted(pinned))

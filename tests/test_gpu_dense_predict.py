@@ -130,6 +130,44 @@ def test_draws_are_one_hot_and_follow_the_probabilities(c):
     assert (np.abs(draws.mean(0) - p64) <= 5 * np.sqrt(p64 * (1 - p64) / n)).all()
 
 
+def rule_draw(probs, u):
+    """the documented rule of the draw (include/bsvi.h, bsvi_dense_predict) on the float32 probabilities the call stored and the uniform
+    of the stream's contract -> [N, M, C] one-hot | 0 / 1.  Categorical: the first class whose float32 partial sum, in class order, is
+    >= u, the last class if none is; Bernoulli: u < p."""
+    probs = np.asarray(probs, dtype=np.float32)
+    if probs.shape[-1] == 1:
+        return (u < probs[..., 0]).astype(np.float32)[..., None]
+    cum = np.zeros(probs.shape[:-1], dtype=np.float32)
+    pick = np.full(probs.shape[:-1], probs.shape[-1] - 1)
+    found = np.zeros(probs.shape[:-1], dtype=bool)
+    for c in range(probs.shape[-1]):
+        cum = (cum + probs[..., c]).astype(np.float32)
+        hit = (cum >= u) & ~found
+        pick[hit] = c
+        found |= hit
+    return (pick[..., None] == np.arange(probs.shape[-1])).astype(np.float32)
+
+
+@pytest.mark.parametrize("n,c,p,m", [(4, 10, 68, 130), (33, 1, 3, 130)])
+@pytest.mark.parametrize("sample_base", [0, 5])
+def test_the_draw_is_its_documented_rule_on_the_streams_uniform(n, c, p, m, sample_base):
+    """u = u01(word m & 3) of Philox counter (sample_base + n, (m >> 2) | 0x20000000, offset) under the seed as it is (philox.h): rows
+    m = 0 .. 129 read all four words of 33 counters.  The draw is the rule on the probabilities the same call returned, exactly."""
+    from oracle import philox_ref as R
+    torch.manual_seed(n + c * p)
+    compiled = engine_of(c, p, False)
+    compiled.params.copy_(0.3 * torch.randn(compiled.params.numel()))
+    seed, offset = 0x1234567890ABC, (1 << 32) - 1
+    res = compiled.predict(rows_of(m, p), n, seed=seed, offset=offset, sample_base=sample_base, want_draws=True)
+    probs, draws = res["probs"].cpu().numpy(), res["draws"].cpu().numpy()
+    u = R.dense_predict_uniform(seed, offset, sample_base, n, m)
+    want = rule_draw(probs, u)
+    assert draws.shape == want.shape == (n, m, c) and np.array_equal(draws, want), np.argwhere(draws != want)[:8]
+    # the rule bites: another offset's uniforms, or the rows' words shifted by one, give other draws
+    assert not np.array_equal(rule_draw(probs, R.dense_predict_uniform(seed, offset + 1, sample_base, n, m)), draws)
+    assert not np.array_equal(rule_draw(probs, np.roll(u, 1, axis=1)), draws)
+
+
 def test_the_ensemble_of_a_batched_svgd_run_is_predicted_from_its_table_in_place():
     model = regression(3, 4, True)
     start = 0.05 * np.random.RandomState(5).normal(size=(3, 12))

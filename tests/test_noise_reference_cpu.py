@@ -201,6 +201,100 @@ def test_no_counter_is_used_twice_in_a_launch():
     assert len(np.unique(x, axis=0)) == len(c1)
 
 
+# ---- the two newer streams of the dense path: the local reparameterisation estimator's normals (tag 0x10000000) and the predictive's
+# likelihood draw (tag 0x20000000), in the manner of tests/test_bnn_predict_cpu.py's check of the BNN predictive
+SEEDS = (1234, 0x1234567890ABC)                                  # tests/test_gpu_noise.py's
+OFFSETS = (0, 7, (1 << 32) - 1, 1 << 32, (1 << 62) + 3)
+KEY_BNN_PREDICT = 0x2545f491                                     # philox.h: k0 of the BNN predictive, k1 = seed high ^ call
+GRID_SAMPLES = np.concatenate([np.arange(70), [255, 256, 65535]])
+GRID_ROWS = np.array([0, 1, 2, 3, 31, 32, 33, 69, 129, 0xFFFF, 0x10000, (1 << 22) - 1, 1 << 22, (1 << 24) - 2, (1 << 24) - 1])
+GRID_CLASSES = np.arange(16)
+
+
+def _tuples(k0, k1, c0, c1, c2, c3):
+    arrs = np.broadcast_arrays(*[np.asarray(v, dtype=np.uint64) for v in (k0, k1, c0, c1, c2, c3)])
+    return set(zip(*[a.reshape(-1).tolist() for a in arrs]))
+
+
+def _older_streams(seed, offset, c0, c1):
+    """(key, counter) tuples of every older stream of the contract at this seed and offset, its counter words taking every value of
+    c0 x c1 that the grids of the newer streams take — scalar engines (Normal rows; other draws at attempts 0 and 1, the blocks of a
+    Binomial), dense / BNN, amortised latents, the three keyed streams, and the BNN predictive (calls 0 .. 2)"""
+    (k0, k1), (o0, o1) = R.split64(seed), R.split64(offset)
+    out = set()
+    for key0 in (k0, k0 ^ R.KEY_DENSE_MINIBATCH, k0 ^ R.KEY_AMORT_MINIBATCH, k0 ^ R.KEY_REDUCE_DATA):
+        for form in (c1, c1 | R.FLAG_NORMAL, (c1 >> 2) | R.FLAG_NORMAL, c1 | R.FLAG_DENSE, (c1 >> 2) | R.FLAG_DENSE, c1 >> 1,
+                     R.raw_counter(c1, 0), R.raw_counter(c1, 1), (c1 & 3) | (c0 << 2) & R.MASK32, np.full_like(c1, R.C1_REDUCE_DATA)):
+            out |= _tuples(key0, k1, c0, form, o0, o1)
+    for call in (0, 1, 2):
+        out |= _tuples(k0 ^ KEY_BNN_PREDICT, k1 ^ call, c0, c1, o0, o1)
+    return out
+
+
+def test_no_key_counter_pair_of_the_two_newer_dense_streams_repeats_or_is_one_of_an_older_stream():
+    """as tuples (k0, k1, c0, c1, c2, c3) over SEEDS x OFFSETS, a grid of samples, rows up to b = 2^24 - 1 and the classes 0 .. 15.
+    Inside the local stream the four classes of a quad share their call BY CONTRACT (they take its four normals): distinct are the
+    calls (sample, b, c >> 2); inside the predictive's the four rows of a quad share theirs (they take its four words).
+    Not covered, and pinned below as it is: the retry counters of a scalar engine's Beta node, (row & 0xffff) | attempt << 16 with
+    attempt = (stream << 12) + try, reach bits 28 and 29 — stream 1 of row r at try 0 IS (r | 0x10000000), stream 2 (r | 0x20000000).
+    A scalar program and a dense-link program are never one launch, nor one model; the tags separate the streams of the dense path."""
+    s, b, c = [a.reshape(-1) for a in np.meshgrid(GRID_SAMPLES, GRID_ROWS, GRID_CLASSES, indexing="ij")]
+    ps, pm = [a.reshape(-1) for a in np.meshgrid(GRID_SAMPLES, GRID_ROWS, indexing="ij")]
+    quads = len(set((GRID_ROWS >> 2).tolist()))
+    for seed in SEEDS:
+        for offset in OFFSETS:
+            local = _tuples(*R.local_counters(seed, offset, s, b, c))
+            assert len(local) == len(GRID_SAMPLES) * len(GRID_ROWS) * 4, (seed, offset)
+            by_call = {}
+            for t, call in zip(zip(*[np.broadcast_to(np.asarray(v, dtype=np.uint64), s.shape).tolist() for v in R.local_counters(seed, offset, s, b, c)]),
+                               zip(s.tolist(), b.tolist(), (c >> 2).tolist())):
+                assert by_call.setdefault(t, call) == call                # a tuple belongs to ONE (sample, row, quad of classes)
+            predict = _tuples(*R.dense_predict_counters(seed, offset, ps, pm))
+            assert len(predict) == len(GRID_SAMPLES) * quads, (seed, offset)
+            assert not (local & predict)
+            # (untagged values: an older stream's own counter word — a row, a latent pair, a round — stays below 2^28)
+            c1_values = np.unique(np.concatenate([GRID_ROWS, GRID_SAMPLES, 4 * GRID_ROWS, 4 * GRID_ROWS + 3, GRID_ROWS >> 2]))
+            g0, g1 = [a.reshape(-1) for a in np.meshgrid(np.unique(np.concatenate([GRID_SAMPLES, GRID_ROWS])), c1_values, indexing="ij")]
+            older = _older_streams(seed, offset, g0, g1)
+            assert not (local & older) and not (predict & older), (seed, offset)
+    # the words differ from the dense path's weight noise at the same (seed, offset, sample, row quad)
+    (k0, k1), (o0, o1) = R.split64(SEEDS[0]), R.split64(7)
+    weights = R.philox4x32(ps, (pm >> 2) | R.FLAG_DENSE, o0, o1, k0, k1)[0]
+    for counters in (R.local_counters(SEEDS[0], 7, ps, pm >> 2, 0), R.dense_predict_counters(SEEDS[0], 7, ps, pm)):
+        k0_, k1_, c0, c1, c2, c3 = counters
+        assert (R.philox4x32(c0, c1, c2, c3, k0_, k1_)[0] != weights).mean() > 0.99
+    # the known overlap with another ENGINE's retry counters (docstring)
+    assert int(R.raw_counter(5, 1 << 12)) == 5 | R.FLAG_DENSE_LOCAL and int(R.raw_counter(5, 2 << 12)) == 5 | R.FLAG_DENSE_PREDICT
+
+
+def test_local_noise_and_the_predictive_uniform_follow_their_rules():
+    """local_noise against the rule spelled out call by call; its moments and cross-class correlation within the bounds
+    tests/test_bnn_predict_cpu.py uses for normal_noise (0.02 at 60 000 values a class; single against double precision 1e-4)"""
+    seed, offset = SEEDS[1], OFFSETS[4]
+    z = R.local_noise(seed, offset, 5, 7, 11)
+    (k0, k1), (o0, o1) = R.split64(seed), R.split64(offset)
+    for n, b, c in ((0, 0, 0), (4, 6, 10), (2, 3, 5), (1, 6, 3), (3, 1, 8)):
+        x = R.philox4x32(n, (4 * b + (c >> 2)) | 0x10000000, o0, o1, k0, k1)
+        four = R.box_muller(x[0], x[1]) + R.box_muller(x[2], x[3])
+        assert z.shape == (5, 7, 11) and z[n, b, c] == four[c & 3]
+    assert np.array_equal(R.local_noise(seed, offset, 5, 7, 3), z[:, :, :3])          # fewer classes: the same normals of the same calls
+    assert np.array_equal(R.local_noise(seed, offset, 3, 4, 11), z[:3, :4])
+    e = R.local_noise(99, 3, 20000, 3, 16)
+    assert e.shape == (20000, 3, 16) and abs(e.mean()) < 0.02 and abs(e.std() - 1) < 0.02
+    assert np.abs(np.corrcoef(e.reshape(-1, 16).T) - np.eye(16)).max() < 0.02          # sixteen classes, four calls: no value used twice
+    assert np.abs(np.corrcoef((e ** 2).reshape(-1, 16).T) - np.eye(16)).max() < 0.02
+    assert np.abs(np.corrcoef(e[:, :, 0].T) - np.eye(3)).max() < 0.02                  # neighbouring rows
+    assert ks(e[:, 1, 5], "norm") > P_MIN
+    assert np.abs(R.local_noise(99, 3, 2000, 3, 16, np.float32) - e[:2000]).max() < 1e-4
+    u = R.dense_predict_uniform(seed, offset, 3, 4, 130)
+    assert u.dtype == np.float32 and u.shape == (4, 130) and u.min() > 0 and u.max() <= 1
+    for n, m in ((0, 0), (3, 129), (2, 6), (1, 67)):
+        x = R.philox4x32(3 + n, (m >> 2) | 0x20000000, o0, o1, k0, k1)
+        assert u[n, m] == R.u01(x[m & 3])
+    assert np.array_equal(R.dense_predict_uniform(seed, offset, 0, 7, 130)[3:], u)     # the base shifts the set index, nothing else
+    assert ks(R.dense_predict_uniform(SEED, OFFSET, 0, 512, 128), "uniform") > P_MIN
+
+
 def test_predictor_is_shard_invariant():
     rows = [(0, R.NORMAL, 0, 0), (1, R.NORMAL, 0, 0), (5, R.LAPLACE, 0, 0), (6, R.BETA, 0.3, 2.0), (7, R.BINOMIAL, 7, 0.1)]
     full = R.scalar_noise(rows, SEED, OFFSET, 0, 300)
